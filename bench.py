@@ -17,12 +17,22 @@ independent problems", the only exchange is the gather of per-rank result record
                                                                 relays its JSON line and fails if fewer than N ranks report
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...     the driver's form
 
-Objects in the JSON line beside the contract's fields (N = 1; `--lean` drops the extra timed legs):
+A plain run (no --full) sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and
+prints the line: the contract's fields, `config`, `roofline` (from the HIP events of the timed steps and the traffic recorded
+under profiles/), the Newton-level rates, `occupancy` and `finite_jacobians`.
+
+  --dump-outputs DIR   after the timed steps, what the last step left in HBM -- the arrays a caller of the path receives --
+                  as float64 .npy files: DIR/residual_rows.npy [starts][15][14] (socp_fd_rows_dev) and DIR/jacobians.npy
+                  [starts][14][14] (socp_fd_diff_dev), rank 0's.  Above 64 MB in all, a fixed seeded sample of the starts is
+                  written instead, its indices in DIR/sample_starts.npy.  The inputs depend on the arguments only.
+
+What --full adds (N = 1; `--full --lean` adds only cpu_baseline): roofline.traffic measured in the run, and every object
+below the roofline:
   roofline        dominant kernel (fdrows_lane_kernel).  This path has no dense contraction and moves 224 B per
                   trajectory, so neither "mfma" nor "hbm" bounds it: the binding resource is FP64 vector issue.
                   `bound` is therefore "valu_fp64" (peak = 256 CU x 4 SIMD x 16 FP64 lanes x 2 flop x 2.4 GHz =
                   78.6 TFLOP/s, half the FP32 vector peak of MI355X_MICROARCH.md); the HBM view the contract asks for
-                  is in roofline.hbm.  `traffic` IS measured in this run (N = 1, not --lean): this file runs twice more as a
+                  is in roofline.hbm.  `traffic` IS measured in a --full run (N = 1, not --lean): this file runs twice more as a
                   child process under `rocprofv3 --pmc` (FETCH_SIZE, then WRITE_SIZE; the guide's recipe and corrections) around
                   two launches of the same kernel at the same size (live_traffic); `traffic_recorded` keeps the figure committed
                   under profiles/ beside it, and is what `traffic` falls back to if the profiler cannot run
@@ -89,8 +99,14 @@ EPSFCN = 1e-15
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the other flavour, in-run parity, single_problem, north_star_128, "
+                         "solver_kernels, the strong-scaling sweep legs, the CPU baselines and the in-run PMC traffic measurement "
+                         "(a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--starts", type=int, default=13107,
                     help="independent shooting problems per GPU; default: 15 x 13107 = 196 605 trajectories = 3072 "
                          "wavefronts = 3 per SIMD (an exactly full chip); any size >= 4096 runs within 10 %% of it")
@@ -99,7 +115,7 @@ def parse_args(argv=None):
                     help="flavour of the headline `value`.  fast: restructured arithmetic (<= 1e-8 vs the reference order "
                          "after 1e4 steps, converged solutions within 1e-8: tests/test_gpu_parity.py, test_host_flow.py); "
                          "exact: reference operation order, bit-identical.  The other flavour is reported beside it.")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="0 disables the CPU baseline legs")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="length of the CPU baseline legs of a --full run; 0 disables them")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo + --share-device0: rehearse the multi-rank path on a one-GPU box (collectives on CPU tensors)")
     ap.add_argument("--share-device0", action="store_true", help="rehearsal only: every rank uses cuda:0")
@@ -107,7 +123,7 @@ def parse_args(argv=None):
                     help="rehearsal only: initialise torch.distributed and run the barrier / all_reduce / all_gather of the N > 1 path "
                          "even with ONE rank -- exercises the RCCL (backend nccl) code path on a one-GPU box")
     ap.add_argument("--lean", action="store_true",
-                    help="N = 1: only the headline timed region, roofline and cpu_baseline (no exact / parity / "
+                    help="with --full, N = 1: only the headline timed region, roofline and cpu_baseline (no exact / parity / "
                          "single_problem / north_star_128 legs)")
     ap.add_argument("--traffic-child", nargs="?", const="headline", default=None, choices=["headline", "factor"],
                     help="internal (live_traffic): two launches of the headline kernel at the headline size and nothing else -- the program "
@@ -116,7 +132,7 @@ def parse_args(argv=None):
     ap.add_argument("--sweep-starts", type=int, default=None,
                     help="the `sweep` leg: a multi-start sweep of this many single-shooting starts IN TOTAL, sharded over the ranks "
                          "(strong scaling: what north_star's \"near-linear to 8 GPUs on the multi-start sweep\" is about); default 65536 "
-                         "(0 = skip; --lean skips it unless a count is given)")
+                         "(0 = skip; without --full, or with --lean, skipped unless a count is given)")
     ap.add_argument("--sweep-max-rounds", type=int, default=40, help="socp_chain_options.max_rounds of the sweep leg")
     ap.add_argument("--sweep-large-starts", type=int, default=None,
                     help="the `sweep_large` leg: the same sweep with this many starts in total (default 8 x --sweep-starts): enough "
@@ -128,16 +144,20 @@ def parse_args(argv=None):
                          "scaling to 8 GPUs can show at all; 0 skips it")
     ap.add_argument("--sweep-c5-starts", type=int, default=None,
                     help="the `sweep_config5` leg: this many starts IN TOTAL of the 253-unknown interceptor problem under the adaptive "
-                         "integrator (BASELINE configs[4]; parity unpinned), sharded over the ranks; default 16384 (0 = skip; --lean skips it)")
+                         "integrator (BASELINE configs[4]; parity unpinned), sharded over the ranks; default 16384 (0 = skip; without --full, or with --lean, skipped unless a count is given)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # the extra legs run by default only in a --full run; a count given explicitly is run either way
+    args.extras = args.full and not args.lean
     if args.sweep_c5_starts is None:
-        args.sweep_c5_starts = 0 if args.lean else 16384
+        args.sweep_c5_starts = 16384 if args.extras else 0
     if args.sweep_starts is None:
-        args.sweep_starts = 0 if args.lean else 65536
+        args.sweep_starts = 65536 if args.extras else 0
     if args.sweep_large_starts is None:
-        args.sweep_large_starts = 0 if args.lean else 8 * args.sweep_starts
+        args.sweep_large_starts = 8 * args.sweep_starts if args.extras else 0
     if args.sweep_xl_starts is None:
-        args.sweep_xl_starts = 0 if args.lean else 64 * args.sweep_starts
+        args.sweep_xl_starts = 64 * args.sweep_starts if args.extras else 0
     return args
 
 
@@ -355,7 +375,9 @@ def cpu_baseline_b0(steps_rk4, target_seconds):
     try:
         t = time.perf_counter()
         out = subprocess.run([exe, "stage", "2", str(steps), "1", "1e-6", zfile], capture_output=True, text=True,
-                             timeout=600, env=dict(os.environ, SOCP_FLOW_THREADS=str(threads)))
+                             timeout=600, env=dict(os.environ, SOCP_FLOW_THREADS=str(threads),
+                                                   LD_LIBRARY_PATH=os.pathsep.join(p for p in (os.path.join(ROOT, "socp_amd", "_build"),
+                                                                                               os.environ.get("LD_LIBRARY_PATH")) if p)))
         wall = time.perf_counter() - t
     finally:
         os.unlink(zfile)
@@ -404,6 +426,31 @@ def timed_region(torch, dist, ctx, stream, dev, cdev, world, P, d_Z, d_rows, d_J
     if collective:
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
     return float(t_max.item()), float(np.mean([a.elapsed_time(b) for a, b in evs]))
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(torch, directory, d_rows, d_J, seed=20250905):
+    """--dump-outputs: what the last timed step left in HBM, as float64 .npy files.  If all of it is more than 64 MB, the same
+    seeded sample of starts (sorted; fixed by the start count) is written from both arrays and its indices beside them."""
+    os.makedirs(directory, exist_ok=True)
+    sample = os.path.join(directory, "sample_starts.npy")
+    if os.path.exists(sample):
+        os.unlink(sample)                                               # (an earlier, larger run's)
+    P = d_rows.shape[0]
+    per_start = (d_rows[0].numel() + d_J[0].numel()) * 8
+    header = 3 * 128                                                    # (an .npy header is 128 bytes here)
+    if P * per_start + header > DUMP_LIMIT_BYTES:
+        K = (DUMP_LIMIT_BYTES - header) // (per_start + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(P, size=K, replace=False))
+        np.save(sample, idx.astype(np.float64))
+        sel = torch.from_numpy(idx).to(d_rows.device)
+        rows, jac = d_rows.index_select(0, sel), d_J.index_select(0, sel)
+    else:
+        rows, jac = d_rows, d_J
+    np.save(os.path.join(directory, "residual_rows.npy"), rows.cpu().numpy().astype(np.float64, copy=False))
+    np.save(os.path.join(directory, "jacobians.npy"), jac.cpu().numpy().astype(np.float64, copy=False))
 
 
 def roofline_of(traj_per_launch, kernel_ms, rk4_steps):
@@ -831,6 +878,8 @@ def main():
     elapsed_max, kernel_ms = timed_region(torch, dist, ctx, stream, dev, cdev, world, P, d_Z, d_rows, d_J, args.steps, args.warmup,
                                           collective=use_dist)
     traj_per_step_rank = P * ROWS
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, d_rows, d_J)           # (before any other leg reuses the buffers)
 
     # result record of this rank (checksum of the Jacobians, finite count): the only exchange of the
     # multi-start sweep is this small gather of per-rank records -- after the timed region.
@@ -844,11 +893,11 @@ def main():
     else:
         recs = [rec.tolist()]
 
-    # strong-scaling legs: fixed totals of starts sharded over the ranks.  At N = 1 (not --lean) one more, small sweep (an eighth
+    # strong-scaling legs: fixed totals of starts sharded over the ranks.  At N = 1 (--full, not --lean) one more, small sweep (an eighth
     # of the `sweep` leg: what a rank of 8 gets of it) completes the one-GPU curve the predictions are read from.
     legs = {}
     leg_sizes = [("sweep", args.sweep_starts), ("sweep_large", args.sweep_large_starts), ("sweep_xl", args.sweep_xl_starts)]
-    if world == 1 and not args.lean and args.sweep_starts >= 8:
+    if world == 1 and args.extras and args.sweep_starts >= 8:
         leg_sizes.insert(0, ("sweep_eighth", args.sweep_starts // 8))
     for name, total in leg_sizes:
         if total > 0 and args.sweep_starts > 0:
@@ -856,7 +905,7 @@ def main():
     # BASELINE config 5 the same way (its own one-GPU curve: the full leg and, at N = 1, the block a rank of 8 gets)
     legs_c5 = {}
     c5_sizes = [("sweep_config5", args.sweep_c5_starts)]
-    if world == 1 and not args.lean and args.sweep_c5_starts >= 8:
+    if world == 1 and args.extras and args.sweep_c5_starts >= 8:
         c5_sizes.insert(0, ("sweep_config5_eighth", args.sweep_c5_starts // 8))
     for name, total in c5_sizes:
         if total > 0:
@@ -872,8 +921,8 @@ def main():
         # (the line is built with the figure recorded under profiles/; the in-run PMC measurement -- child processes under rocprofv3 --
         # replaces it at the very end, after every timed leg: ADVICE r5)
         traffic, traffic_source, traffic_live = rec_traffic, rec_source, False
-        live_note = "not attempted (N > 1, --lean, under a profiler, or SOCP_BENCH_LIVE_PMC=0)"
-        want_live = world == 1 and not args.lean and os.environ.get("SOCP_BENCH_LIVE_PMC", "1") != "0" and "rocprof" not in os.environ.get("LD_PRELOAD", "")
+        live_note = "not attempted (no --full, N > 1, --lean, under a profiler, or SOCP_BENCH_LIVE_PMC=0)"
+        want_live = world == 1 and args.extras and os.environ.get("SOCP_BENCH_LIVE_PMC", "1") != "0" and "rocprof" not in os.environ.get("LD_PRELOAD", "")
         smooth = GODDARD_PARAMS[6] > 0
         # VGPR budget -> waves per SIMD the launcher may use: fast smooth law 156 VGPRs (3), fast general law 252-254 (2),
         # exact 248 (2) -- socp_amd/csrc/launch.hpp picks min(that, ceil(waves / 1024))
@@ -929,7 +978,7 @@ def main():
         if ranks_seen != list(range(world)):
             sys.stderr.write("bench.py: records of ranks %s, expected 0..%d\n" % (ranks_seen, world - 1))
             status = 1
-        if world == 1 and not args.lean:
+        if world == 1 and args.extras:
             rows_by_variant = {args.variant: d_rows}
             # ---- the other flavour, same workload, its own timed region --------------------------------------------
             other = "exact" if args.variant == "fast" else "fast"
@@ -968,7 +1017,7 @@ def main():
             out["single_problem"] = {"trajectories": ROWS, "unit": "trajectories/s", **single,
                                      "note": "latency-bound: one wave on one SIMD, 4e4 serially dependent RHS evaluations"}
             ctx2.close()
-        if world == 1 and args.cpu_seconds > 0:
+        if world == 1 and args.full and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(args.rk4_steps, Z_host, args.cpu_seconds)
             b0 = cpu_baseline_b0(args.rk4_steps, args.cpu_seconds)
             if b0:
@@ -987,7 +1036,7 @@ def main():
                 if "exact" in out:
                     ratios["exact_over_b0"] = out["exact"]["value"] / b0["value"]
             out["cpu_baseline"]["gpu_ratios"] = ratios
-        if world == 1 and not args.lean:
+        if world == 1 and args.extras:
             cpu_v = out.get("cpu_baseline", {}).get("value")
             p1_v = out.get("cpu_baseline", {}).get("p1", {}).get("value")
             out["north_star_128"] = north_star_128(capi, local_rank, args.rk4_steps, cpu_v, p1_v)

@@ -18,7 +18,7 @@ ln -s "$ROOT/socp_amd/host/src" "$OUT/src"
 for prog in testGoddard testDoubleIntegrator testDoubleIntegrator_WP testCovid19 testInterceptor; do
     ln -s "$REF/tests/$prog.cpp" "$OUT/tests/$prog.cpp"
     g++ -O2 -std=gnu++14 -w -I"$ROOT/include" -I"$ROOT/socp_amd/host/src/socp" -o "$OUT/bin/$prog" "$OUT/tests/$prog.cpp" \
-        -L"$ROOT/socp_amd/_build" -lsocp_host -lsocp_hip -Wl,-rpath,"$ROOT/socp_amd/_build" -lpthread
+        -L"$ROOT/socp_amd/_build" -lsocp_host -lsocp_hip -Wl,-rpath,'$ORIGIN/../../../../socp_amd/_build' -lpthread
     echo "built $OUT/bin/$prog"
 done
 # the scratch tree only existed to resolve the includes: remove the links so that nothing under oracle/_ref

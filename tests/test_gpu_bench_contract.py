@@ -18,7 +18,7 @@ def _line(out):
 
 
 def test_bench_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--starts", "4096",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--starts", "4096",
                           "--cpu-seconds", "2", "--sweep-starts", "2048", "--sweep-c5-starts", "512"], capture_output=True, text=True, timeout=900)
     d = _line(out)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -115,10 +115,40 @@ def test_bench_line_contract():
     assert isinstance(c["cpu_model"], str) and c["cpu_model"]
 
 
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline steps and nothing else; --dump-outputs writes what the last timed step left in HBM
+    -- the FD rows and the Jacobians formed from them -- and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    from socp_amd.sweep import goddard_starts
+    lines, dirs = [], []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--starts", "1024",
+                              "--rk4-steps", "1000", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        lines.append(_line(out))
+        dirs.append(d)
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 1024 * 15 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for key in ("exact", "parity", "single_problem", "north_star_128", "cpu_baseline", "solver_kernels", "sweep", "sweep_config5"):
+        assert key not in d, key
+    assert d["roofline"]["traffic_measured_in_this_run"] is False and d["roofline"]["kernel_ms"] <= d["ms_per_step"] * 1.05
+    rows, jac = (np.load(dirs[0] / n) for n in ("residual_rows.npy", "jacobians.npy"))
+    assert rows.dtype == np.float64 and rows.shape == (1024, 15, 14) and jac.dtype == np.float64 and jac.shape == (1024, 14, 14)
+    assert not (dirs[0] / "sample_starts.npy").exists()
+    assert int(np.isfinite(jac).all(axis=(1, 2)).sum()) == d["finite_jacobians"][0] == 1024
+    # jac[p][j] = (row j + 1 - row 0) / h_j, h_j = sqrt(epsfcn) |z_j| with bench's epsfcn = 1e-15 (socp_fd_diff_dev), z the run's
+    # rank-0 starts (none of them has a zero component)
+    h = np.sqrt(1e-15) * np.abs(goddard_starts(1024, 1e-3, 20250905))
+    assert np.allclose(jac, (rows[:, 1:, :] - rows[:, :1, :]) / h[:, :, None], rtol=1e-13, atol=0.0)
+    for n in ("residual_rows.npy", "jacobians.npy"):
+        assert np.array_equal(np.load(dirs[0] / n), np.load(dirs[1] / n)), n
+
+
 def test_gpus_2_really_runs_two_ranks():
     """`python bench.py --gpus 2` (no launcher): the parent starts two ranks; here both share device 0 and the collectives
     run over gloo (a one-GPU box), the code path is otherwise the N > 1 path of the driver."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device0",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--share-device0",
                           "--steps", "2", "--warmup", "1", "--starts", "1024", "--rk4-steps", "1000", "--sweep-starts", "301", "--sweep-c5-starts", "65"],
                          capture_output=True, text=True, timeout=900)
     d = _line(out)
@@ -142,7 +172,7 @@ def test_rccl_code_path_with_one_rank():
     """The N > 1 path talks to RCCL (torch.distributed backend "nccl"): process-group creation with a device id, barrier,
     all_reduce(MAX) of the timing and all_gather of the result records on DEVICE tensors.  A one-GPU box cannot host two RCCL
     ranks, so this runs that exact code with a world of one (--force-dist); the two-rank plumbing is the gloo test above."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--lean", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--lean", "--steps", "2", "--warmup", "1",
                           "--starts", "1024", "--rk4-steps", "1000", "--cpu-seconds", "0", "--sweep-starts", "200", "--sweep-c5-starts", "48"],
                          capture_output=True, text=True, timeout=900)
     d = _line(out)
@@ -163,7 +193,7 @@ def test_four_rank_rehearsal_of_the_driver_job():
     ranks of the same plumbing run on the CPU: tests/test_sweep_gloo.py; eight emulated ranks through the C++ entry points:
     test_gpu_multistart.py.)"""
     W = 4
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(W), "--backend", "gloo", "--share-device0",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(W), "--backend", "gloo", "--share-device0",
                           "--steps", "1", "--warmup", "1", "--starts", "256", "--rk4-steps", "1000", "--sweep-starts", "301", "--sweep-c5-starts", "67"],
                          capture_output=True, text=True, timeout=1200)
     d = _line(out)

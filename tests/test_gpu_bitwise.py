@@ -110,6 +110,13 @@ def test_reference_test_program_newton_history_bitwise():
         assert np.array_equal(np.array(s["z"]), np.array(g["z"])), s["stage"]
 
 
+def _dropin_env():
+    """The prebuilt drop-in programs load THIS checkout's libraries, wherever oracle/_ref was built and however it is reached
+    (their run path is relative to their own location, which a symbolic link changes)."""
+    lib = os.path.join(ROOT, "socp_amd", "_build")
+    return dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (lib, os.environ.get("LD_LIBRARY_PATH")) if p))
+
+
 def test_unmodified_reference_program_reports_success(tmp_path):
     """The reference's own tests/testGoddard.cpp, compiled unchanged against the mirror in the authoring container
     (scripts/dropin_build.sh; the binary travels, the source does not): OK = 1 for all four solves."""
@@ -119,9 +126,9 @@ def test_unmodified_reference_program_reports_success(tmp_path):
     work = tmp_path / "a" / "b"
     work.mkdir(parents=True)
     (tmp_path / "trace" / "goddard").mkdir(parents=True)
-    out = subprocess.run([exe], cwd=work, input="\n", capture_output=True, text=True, timeout=600)
+    out = subprocess.run([exe], cwd=work, input="\n", capture_output=True, text=True, timeout=600, env=_dropin_env())
     oks = [l.split("OK =")[1].strip() for l in out.stdout.splitlines() if "OK =" in l]
-    assert oks == ["1", "1", "1", "1"], out.stdout
+    assert oks == ["1", "1", "1", "1"], (out.returncode, out.stdout[-2000:], out.stderr[-2000:])
 
 
 def _run_dropin(tmp_path, prog):
@@ -132,7 +139,7 @@ def _run_dropin(tmp_path, prog):
     work.mkdir(parents=True)
     for m in ("goddard", "doubleIntegrator", "covid19", "interceptor"):
         (tmp_path / "trace" / m).mkdir(parents=True)
-    out = subprocess.run([exe], cwd=work, input="\n", capture_output=True, text=True, timeout=600)
+    out = subprocess.run([exe], cwd=work, input="\n", capture_output=True, text=True, timeout=600, env=_dropin_env())
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2000:])
     return out.stdout
 

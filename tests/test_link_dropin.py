@@ -25,6 +25,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LINK = os.path.join(ROOT, "oracle", "_ref", "link")
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "goddard_flow.json")))
 
+def _env(**extra):
+    """The prebuilt programs load THIS checkout's libraries, wherever oracle/_ref was built and however it is reached."""
+    lib = os.path.join(ROOT, "socp_amd", "_build")
+    return dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (lib, os.environ.get("LD_LIBRARY_PATH")) if p), **extra)
+
+
 needs_link = pytest.mark.skipif(not os.path.exists(os.path.join(LINK, "goddard_flow_ref")),
                                 reason="oracle/_ref/link not built (needs /root/reference: make -C oracle link)")
 
@@ -34,13 +40,13 @@ def test_reference_shooting_objects_bind_to_our_hybrd():
     for exe in ("testGoddard_linked", "goddard_flow_ref"):
         syms = subprocess.run(["nm", "-u", os.path.join(LINK, exe)], capture_output=True, text=True).stdout.split()
         assert "hybrd" in syms and "hybrj" in syms                     # resolved at load time ...
-        ldd = subprocess.run(["ldd", os.path.join(LINK, exe)], capture_output=True, text=True).stdout
+        ldd = subprocess.run(["ldd", os.path.join(LINK, exe)], capture_output=True, text=True, env=_env()).stdout
         assert "libsocp_hip.so" in ldd and "not found" not in ldd      # ... by the product library
 
 
 @needs_link
 def test_reference_testGoddard_unmodified_converges_four_times(tmp_path):
-    out = subprocess.run([os.path.join(LINK, "testGoddard_linked")], capture_output=True, text=True, timeout=300, cwd=tmp_path)
+    out = subprocess.run([os.path.join(LINK, "testGoddard_linked")], capture_output=True, text=True, timeout=300, cwd=tmp_path, env=_env())
     assert out.returncode == 0, out.stderr
     assert out.stdout.count("OK = 1") == 4, out.stdout
 
@@ -50,7 +56,7 @@ def test_reference_testGoddard_unmodified_converges_four_times(tmp_path):
 def test_call_numbers_and_solutions_of_the_reference_flow(threads):
     """GetCallNumber per solve and the converged unknowns; numThread = 2 goes through the reference's
     ShootingFunctionParallel (shooting.cpp:1133-1158) and must not change a bit."""
-    env = dict(os.environ, SOCP_FLOW_THREADS=str(threads))
+    env = _env(SOCP_FLOW_THREADS=str(threads))
     out = subprocess.run([os.path.join(LINK, "goddard_flow_ref"), "full", "10", "1", "1e-6"], capture_output=True, text=True,
                          timeout=300, env=env)
     assert out.returncode == 0, out.stderr
