@@ -36,6 +36,10 @@ extern "C" {
 #define SOCP_MODEL_COVID19            3   /* dim 4, covid19.cpp:53-165 (control dimension 1) */
 #define SOCP_MODEL_INTERCEPTOR        4   /* dim 6, interceptor.cpp:69-998: two charts, two stages, own ComputeTraj and
                                              final rows (control dimension 2: u, beta) */
+#define SOCP_MODEL_VTOLUAV            5   /* dim 6, vtolUAV.cpp:58-278 + obstacle.cpp:155-319: the right-hand side reads a
+                                             device-resident obstacle table (socp_ctx_set_map); state-only (modelOrder 0).
+                                             LANE_EXACT follows the reference's operation order but uses the device library's
+                                             tanh: NOT bit-identical to the CPU path (rows 6-8 of the RHS, the Hamiltonian) */
 
 /* packed parameter block, refreshed before every Newton solve (parameters are mutated by the
  * continuation loop through a raw real&, shooting.cpp:695-707) */
@@ -46,7 +50,15 @@ extern "C" {
  * data->chartLimit (interceptor.cpp:52-58):  c0, hr, d0, eta, propellant_mass, empty_mass, q, ve, alpha_max, u_max,
  * a_max, mu_gft, muT, muV, muC, R_Earth, mu0, chartLimit */
 #define SOCP_INTERCEPTOR_NPARAMS 18
+/* vtolUAV.hpp parameters_struct in declaration order (nWP_tot, nWP as doubles), then the map's obstacle.hpp
+ * parameters_struct: u_max, a_max, alphaT, alphaV, invSigmaXwp, Vd, ca, nWP_tot, nWP, phiObs, psiWP, muObs, sigmaWP.
+ * The map's scalars are parameters, not table entries: continuation moves muObs, and chains carry per-problem blocks. */
+#define SOCP_VTOL_NPARAMS 13
 #define SOCP_MAX_NPARAMS         24   /* capacity of a packed parameter block */
+/* obstacle table of SOCP_MODEL_VTOLUAV: SOCP_MAP_STRIDE doubles per obstacle -- type (0 ellipsoid, 1 box, anything else
+ * contributes nothing), centre x y z, radii x y z -- at most SOCP_MAX_OBSTACLES rows */
+#define SOCP_MAP_STRIDE     7
+#define SOCP_MAX_OBSTACLES  256
 
 /* time / state modes, model.hpp:34-38 */
 #define SOCP_FIXED      0
@@ -83,6 +95,14 @@ int socp_ctx_set_params(socp_ctx *ctx, const double *params, int nparams);
 int socp_ctx_get_params(const socp_ctx *ctx, double *params, int nparams);
 int socp_ctx_num_params(const socp_ctx *ctx);        /* length of the model's packed parameter block (< 0: error) */
 int socp_ctx_set_step_number(socp_ctx *ctx, int step_nbr);      /* model::stepNbr, model.hpp:367 */
+/* replaces: the obstacle arrays an `obstacle` map reads from its file (obstacle.cpp:69-109) and every later
+ * map::Gradient / map::Function call of the model (vtolUAV.cpp:84-90, :172-177).  table[n_obs][SOCP_MAP_STRIDE] is copied to a
+ * device buffer the context owns; every kernel of the model reads it from there.  n_obs = 0 is free space; more than
+ * SOCP_MAX_OBSTACLES is SOCP_ERR_ARG (the context keeps its previous table); a context of another model: SOCP_ERR_UNSUPPORTED.
+ * A fresh context has no obstacles.  socp_ctx_clone copies the table to the clone's device. */
+int socp_ctx_set_map(socp_ctx *ctx, int n_obs, const double *table);
+/* *n_obs = rows in force; table (may be NULL) receives them, read back from the device; cap_obs = rows `table` can hold */
+int socp_ctx_get_map(const socp_ctx *ctx, int *n_obs, double *table, int cap_obs);
 /* integrator of every later call: SOCP_INT_RK4 = the reference's default fixed-step loop
  * (odeTools.cpp:135-145); SOCP_INT_DOPRI5 = what it runs when built with -D_USE_BOOST (odeTools.cpp:129-134),
  * abs = rel tolerance `tol` = odeTools::odeIntTol (set from the solver's xtol by shooting::SetPrecision,

@@ -204,7 +204,8 @@ double socp_workspace_cached_bytes(int device);
 void socp_sweep_shard(int P, int rank, int world, int *lo, int *hi);
 
 /* A copy of `proto` on another device: same model, packed parameters, switching times, step number, integrator, arithmetic
- * flavour and shooting problem (its tables are rebuilt there).  device < 0: the calling thread's current device. */
+ * flavour, obstacle table (socp_ctx_set_map) and shooting problem (their tables are rebuilt there).  device < 0: the calling
+ * thread's current device. */
 int socp_ctx_clone(const struct socp_ctx *proto, int device, struct socp_ctx **out);
 
 typedef struct socp_sweep_stats {

@@ -34,6 +34,8 @@ UNITS = {
     "kernels_fast": ("socp_amd/csrc/kernels_fast.hip", ["-ffp-contract=fast"]),
     "kernels_interceptor": ("socp_amd/csrc/kernels_interceptor.hip", ["-ffp-contract=off"]),
     "kernels_interceptor_fast": ("socp_amd/csrc/kernels_interceptor_fast.hip", ["-ffp-contract=fast"]),
+    "kernels_vtol": ("socp_amd/csrc/kernels_vtol.hip", ["-ffp-contract=off"]),
+    "kernels_vtol_fast": ("socp_amd/csrc/kernels_vtol_fast.hip", ["-ffp-contract=fast"]),
     "kernels_solver": ("socp_amd/csrc/kernels_solver.hip", ["-ffp-contract=off"]),
     "kernels_factor_fast": ("socp_amd/csrc/kernels_factor_fast.hip", ["-ffp-contract=fast"]),
     "capi": ("socp_amd/csrc/capi.cpp", ["-ffp-contract=off", "-x", "hip"]),

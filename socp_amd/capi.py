@@ -13,6 +13,11 @@ LIB_PATH = os.environ.get("SOCP_LIB_PATH") or os.path.join(_HERE, "_build", "lib
 
 OK, ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 MODEL_GODDARD, MODEL_DOUBLE_INTEGRATOR, MODEL_COVID19, MODEL_INTERCEPTOR = 1, 2, 3, 4
+MODEL_VTOLUAV = 5
+# packed block of the vtolUAV model: its own nine parameters, then the four scalars of its obstacle map (SOCP_VTOL_NPARAMS)
+VTOL_PARAM_NAMES = ["u_max", "a_max", "alphaT", "alphaV", "invSigmaXwp", "Vd", "ca", "nWP_tot", "nWP",
+                    "phiObs", "psiWP", "muObs", "sigmaWP"]
+MAP_STRIDE, MAX_OBSTACLES = 7, 256      # obstacle table: rows of (type, centre xyz, radii xyz)
 INTERCEPTOR_PARAM_NAMES = ["c0", "hr", "d0", "eta", "propellant_mass", "empty_mass", "q", "ve", "alpha_max", "u_max",
                            "a_max", "mu_gft", "muT", "muV", "muC", "R_Earth", "mu0", "chartLimit"]
 FIXED, FREE, CONTINUOUS = 0, 1, 2
@@ -86,6 +91,8 @@ def lib():
         L.socp_ctx_set_params.argtypes = [_vp, _dp, C.c_int]
         L.socp_ctx_get_params.argtypes = [_vp, _dp, C.c_int]
         L.socp_ctx_set_step_number.argtypes = [_vp, C.c_int]
+        L.socp_ctx_set_map.argtypes = [_vp, C.c_int, _dp]
+        L.socp_ctx_get_map.argtypes = [_vp, _ip, _dp, C.c_int]
         L.socp_ctx_set_integrator.argtypes = [_vp, C.c_int, C.c_double]
         L.socp_ctx_set_switching_times.argtypes = [_vp, _dp, C.c_int]
         L.socp_ctx_set_variant.argtypes = [_vp, C.c_int]
@@ -225,6 +232,8 @@ class Context:
         self.nparams = nparams
         if nparams is None and model_id == MODEL_INTERCEPTOR:
             self.nparams = len(INTERCEPTOR_PARAM_NAMES)
+        if nparams is None and model_id == MODEL_VTOLUAV:
+            self.nparams = len(VTOL_PARAM_NAMES)
 
     def close(self):
         if self.h:
@@ -267,9 +276,23 @@ class Context:
 
     def set_param(self, name, value):
         p = self.get_params()
-        names = INTERCEPTOR_PARAM_NAMES if self.model_id == MODEL_INTERCEPTOR else GODDARD_PARAM_NAMES
+        names = {MODEL_INTERCEPTOR: INTERCEPTOR_PARAM_NAMES, MODEL_VTOLUAV: VTOL_PARAM_NAMES}.get(self.model_id, GODDARD_PARAM_NAMES)
         p[names.index(name)] = value
         self.set_params(p)
+
+    def set_map(self, table):
+        """Obstacle table of the vtolUAV model (socp_ctx_set_map): rows of (type, centre xyz, radii xyz); an empty table is free space."""
+        t = _f64(table).reshape(-1, MAP_STRIDE)
+        self._chk(self.L.socp_ctx_set_map(self.h, t.shape[0], _d(t) if t.shape[0] else None))
+
+    def get_map(self):
+        """The table in force, read back from the device: array [n_obs][7]."""
+        n = C.c_int()
+        self._chk(self.L.socp_ctx_get_map(self.h, C.byref(n), None, 0))
+        t = np.empty((n.value, MAP_STRIDE))
+        if n.value:
+            self._chk(self.L.socp_ctx_get_map(self.h, C.byref(n), _d(t), n.value))
+        return t
 
     def set_step_number(self, n):
         self._chk(self.L.socp_ctx_set_step_number(self.h, int(n)))

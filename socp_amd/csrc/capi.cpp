@@ -22,6 +22,8 @@
 
 using namespace socp;
 
+static_assert(socp::kMaxObstacles == SOCP_MAX_OBSTACLES && socp::kMapStride == SOCP_MAP_STRIDE && SOCP_VTOL_NPARAMS <= socp::kMaxParams, "socp_hip.h and dev_common.hpp disagree");
+
 namespace {
 
 // socp_last_error(NULL) reports the calling thread's last creation failure: concurrent socp_ctx_create calls may fail at once
@@ -67,6 +69,10 @@ struct socp_ctx {
     ProblemDev pb{};
     DevBuf d_pairs_full, d_pairs_dedup;
     int T_full = 0, T_dedup = 0;
+
+    // obstacle table of the vtolUAV model (socp_ctx_set_map): host copy + the device buffer P.map points into
+    std::vector<double> map_table;
+    DevBuf d_map;
 
     // grow-only staging for the host-pointer entry points
     DevBuf s_t0, s_tf, s_sw, s_in, s_out, s_aux, s_var;
@@ -181,6 +187,7 @@ int socp_ctx_create(socp_ctx **out, int model_id, int device)
         if (it != plugins().end()) vt = &it->second;
     }
     if (model_id == SOCP_MODEL_INTERCEPTOR) vt = interceptor_launchers();   // in-tree, table-driven (kernels_interceptor.hip)
+    if (model_id == SOCP_MODEL_VTOLUAV) vt = vtol_launchers();              // in-tree, table-driven (kernels_vtol.hip)
     if (!vt && model_id != SOCP_MODEL_GODDARD && model_id != SOCP_MODEL_DOUBLE_INTEGRATOR && model_id != SOCP_MODEL_COVID19)
         return fail(nullptr, SOCP_ERR_UNSUPPORTED, "socp_ctx_create: unknown model id (no device dynamics; plugins: socp_plugin_load)");
     int ndev = 0;
@@ -197,6 +204,7 @@ int socp_ctx_create(socp_ctx **out, int model_id, int device)
     c->model_id = model_id;
     c->vt = vt;
     if (model_id == SOCP_MODEL_INTERCEPTOR) c->vt_fast = interceptor_launchers_fast();
+    if (model_id == SOCP_MODEL_VTOLUAV) c->vt_fast = vtol_launchers_fast();
     c->device = device;
     if (vt) {
         c->dim = vt->dim; c->nparams = vt->nparams; c->nu = vt->control_dim;
@@ -244,7 +252,11 @@ int socp_ctx_clone(const socp_ctx *proto, int device, socp_ctx **out)
     int rc = socp_ctx_create(&c, proto->model_id, device);
     if (rc != SOCP_OK) return rc;
     c->P = proto->P;                                   // parameters, switching times, step number, integrator, tolerance
+    c->P.map = nullptr; c->P.n_map = 0;                // the table pointer is the prototype's: the clone gets its own copy
     c->variant = proto->variant;
+    if (!proto->map_table.empty())
+        rc = socp_ctx_set_map(c, (int)(proto->map_table.size() / kMapStride), proto->map_table.data());
+    if (rc != SOCP_OK) { g_create_error = c->err; socp_ctx_destroy(c); return rc; }
     if (proto->has_problem)
         rc = socp_problem_set(c, proto->M, proto->mode_t.data(), proto->mode_x.data(), proto->time.data(), proto->xnode.data());
     if (rc != SOCP_OK) { g_create_error = c->err; socp_ctx_destroy(c); return rc; }
@@ -257,7 +269,7 @@ int socp_ctx_destroy(socp_ctx *c)
     if (!c) return SOCP_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    c->d_tables.release(); c->d_pairs_full.release(); c->d_pairs_dedup.release();
+    c->d_tables.release(); c->d_pairs_full.release(); c->d_pairs_dedup.release(); c->d_map.release();
     c->s_t0.release(); c->s_tf.release(); c->s_sw.release(); c->s_in.release(); c->s_out.release(); c->s_aux.release(); c->s_var.release();
     if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -281,6 +293,45 @@ int socp_ctx_get_params(const socp_ctx *c, double *params, int nparams)
 }
 
 int socp_ctx_num_params(const socp_ctx *c) { return c ? c->nparams : SOCP_ERR_ARG; }
+
+int socp_ctx_set_map(socp_ctx *c, int n_obs, const double *table)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (c->model_id != SOCP_MODEL_VTOLUAV) return fail(c, SOCP_ERR_UNSUPPORTED, "set_map: this model reads no map");
+    if (n_obs < 0 || (n_obs > 0 && !table)) return fail(c, SOCP_ERR_ARG, "set_map: null table / negative count");
+    if (n_obs > kMaxObstacles)
+        return fail(c, SOCP_ERR_ARG, "set_map: too many obstacles (" + std::to_string(n_obs) + " > SOCP_MAX_OBSTACLES = " + std::to_string(kMaxObstacles) + ")");
+    const size_t count = (size_t)n_obs * kMapStride;
+    if (count == c->map_table.size() && (count == 0 || std::memcmp(c->map_table.data(), table, sizeof(double) * count) == 0)) return SOCP_OK;
+    if (n_obs > 0) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        // one buffer of the full capacity, overwritten in place: in order behind everything on the context's stream; what an engine
+        // may still have in flight on the context's second stream is waited for first
+        if (c->aux_stream) HIP_TRY(c, hipStreamSynchronize(c->aux_stream));
+        HIP_TRY(c, c->d_map.reserve(sizeof(double) * kMaxObstacles * kMapStride));
+        HIP_TRY(c, hipMemcpyAsync(c->d_map.p, table, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    c->map_table.assign(table, table + count);
+    c->P.map = n_obs > 0 ? c->d_map.as<double>() : nullptr;
+    c->P.n_map = n_obs;
+    return SOCP_OK;
+}
+
+int socp_ctx_get_map(const socp_ctx *c, int *n_obs, double *table, int cap_obs)
+{
+    if (!c || !n_obs) return SOCP_ERR_ARG;
+    *n_obs = c->P.n_map;
+    if (!table) return SOCP_OK;
+    if (cap_obs < c->P.n_map) return SOCP_ERR_ARG;
+    if (c->P.n_map > 0) {
+        // read back what the kernels read, not the host copy
+        if (hipSetDevice(c->device) != hipSuccess ||
+            hipMemcpy(table, c->P.map, sizeof(double) * c->P.n_map * kMapStride, hipMemcpyDeviceToHost) != hipSuccess)
+            return SOCP_ERR_HIP;
+    }
+    return SOCP_OK;
+}
 
 int socp_ctx_set_step_number(socp_ctx *c, int step_nbr)
 {

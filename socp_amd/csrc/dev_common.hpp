@@ -14,7 +14,14 @@ struct ModelParams {
     int step_nbr;                      // model::stepNbr (model.hpp:367)
     int integrator;                    // 0 = fixed-step RK4 (odeTools.cpp:135-145), 1 = adaptive Dormand-Prince (:129-134)
     double tol;                        // odeTools::odeIntTol: abs = rel tolerance of the adaptive integrator
+    // vtolUAV only: the context's device-resident obstacle table (socp_ctx_set_map), kMapStride doubles per obstacle.  Kernel
+    // arguments, hence wave-invariant; the model reads the table through the constant address space, which is what makes the
+    // reads scalar loads in kernels that also store (models_vtol.hpp: MapTable).  Nothing writes the table during a launch.
+    const double *map;
+    int n_map;
 };
+constexpr int kMapStride = 7;          // type, centre xyz, radii xyz (SOCP_MAP_STRIDE)
+constexpr int kMaxObstacles = 256;     // upper bound of socp_ctx_set_map (SOCP_MAX_OBSTACLES)
 
 // Shooting problem tables (device pointers), built by socp_problem_set.
 // node_kind[k]:  >=0 -> FREE junction, value = index into z of its time unknown

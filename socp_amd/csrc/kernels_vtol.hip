@@ -1,0 +1,15 @@
+// kernels_vtol.hip -- the vtolUAV waypoint model's kernels (models_vtol.hpp), reference operation order:
+// MUST be compiled with -ffp-contract=off.  Table-driven like the interceptor (plugin_impl.hpp); capi.cpp binds
+// the table to SOCP_MODEL_VTOLUAV and fills ModelParams::map / n_map from the context's obstacle table.
+#include "models_vtol.hpp"
+#include "plugin_impl.hpp"
+
+namespace socp {
+
+const ModelLaunchers *vtol_launchers()
+{
+    static const ModelLaunchers t = plugin::table<VtolExact>(VP_COUNT, 100, SOCP_VTOL_DEFAULTS);
+    return &t;
+}
+
+}  // namespace socp

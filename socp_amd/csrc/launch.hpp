@@ -56,7 +56,7 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of an out-of-tree model (include/socp_plugin.h, plugin_impl.hpp): what the C-ABI layer calls
 // instead of the built-in flavour launchers when a context is created with a registered model id.
-constexpr int kPluginAbi = 4;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers
+constexpr int kPluginAbi = 5;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -88,5 +88,7 @@ SOCP_DECLARE_LAUNCHERS(fast)
 // in-tree models that live in their own translation unit behind a launch table, like an out-of-tree plugin
 const ModelLaunchers *interceptor_launchers();      // kernels_interceptor.hip      (reference operation order)
 const ModelLaunchers *interceptor_launchers_fast(); // kernels_interceptor_fast.hip (restructured, contraction on)
+const ModelLaunchers *vtol_launchers();             // kernels_vtol.hip             (reference operation order)
+const ModelLaunchers *vtol_launchers_fast();        // kernels_vtol_fast.hip        (restructured, contraction on)
 
 }  // namespace socp

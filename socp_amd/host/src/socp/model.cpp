@@ -39,6 +39,7 @@ socp_ctx *model::DeviceContext() const
         throw std::runtime_error(std::string("model: ") + socp_last_error(deviceCtx_));
     const std::vector<real> sw = DeviceSwitchingTimes();
     socp_ctx_set_switching_times(deviceCtx_, sw.data(), (int)sw.size());
+    DeviceConfigure(deviceCtx_);
     return deviceCtx_;
 }
 

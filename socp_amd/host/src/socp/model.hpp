@@ -68,6 +68,8 @@ public:
     virtual int DeviceStepNumber() const { return stepNbr; }
     // switching times the control law reads (goddard); empty otherwise
     virtual std::vector<real> DeviceSwitchingTimes() const { return std::vector<real>(); }
+    // anything else the device twin reads, sent on every use like the parameters (vtolUAV: its map's obstacle table)
+    virtual void DeviceConfigure(socp_ctx *ctx) const { (void)ctx; }
     // arithmetic flavour of this model's device kernels: SOCP_VARIANT_AUTO (default: the reference operation order,
     // bit-identical to the CPU path), SOCP_VARIANT_LANE_EXACT, or SOCP_VARIANT_LANE_FAST (restructured arithmetic, within
     // north_star's 1e-8 of it, ~3.6x the throughput -- bench.py reports both).  Without a call the environment variable
