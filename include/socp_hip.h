@@ -110,6 +110,8 @@ int socp_ctx_get_map(const socp_ctx *ctx, int *n_obs, double *table, int cap_obs
 #define SOCP_INT_RK4    0
 #define SOCP_INT_DOPRI5 1
 int socp_ctx_set_integrator(socp_ctx *ctx, int kind, double tol);
+/* the step number, integrator and tolerance in force (any pointer may be NULL): what sizes the rows of a trace */
+int socp_ctx_get_integrator(const socp_ctx *ctx, int *step_nbr, int *kind, double *tol);
 int socp_ctx_set_switching_times(socp_ctx *ctx, const double *sw, int nsw);  /* goddard.cpp:373-377 */
 int socp_ctx_get_switching_times(const socp_ctx *ctx, double *sw2);          /* the two values the control law reads */
 int socp_ctx_set_variant(socp_ctx *ctx, int variant);
@@ -239,6 +241,33 @@ int socp_fd_rows_dev(socp_ctx *ctx, int np, const double *d_Z, double epsfcn, do
 int socp_fd_rows(socp_ctx *ctx, int np, const double *Z, double epsfcn, double *Rows);
 int socp_fd_diff_dev(socp_ctx *ctx, int np, const double *d_Z, double epsfcn, const double *d_Rows,
                      double *d_Fjac);
+
+/* replaces: shooting::Trace (shooting.cpp:496-544; model.hpp:422-462) for a whole batch of unknown vectors: the sampled rows
+ * t, X, u, H of every segment, device-resident.
+ * width of a trace row of this context's model: W = 1 + 2d + NU + 1 + 2  (t, X[2d], u[NU], H, aux0, aux1) */
+int socp_trace_width(const socp_ctx *ctx);
+/* Z[B][n] -> rows[B][M][cap][W], count[B][M].  Segment i of row b is integrated exactly as the residual integrates it
+ * (same timeline, switching times, start state z[s i .. s i + s), integrator, per-problem blocks of
+ * socp_problem_set_blocks_dev: row b reads block b).  Let R be the number of rows socp_integrate_dense_aux reports for
+ * that segment and k = 0 .. R-1 their indices: row k is KEPT iff k % stride == 0 or k == R-1.  Kept rows are stored in
+ * order; count[b][i] = number of kept rows (kept rows beyond cap are counted, not stored, nothing is written past
+ * slab [b][i]; rows at or beyond min(count, cap) keep what the buffer held).  stride >= 1, cap >= 1.
+ * t, X, aux0, aux1 of a row are what socp_integrate_dense_aux gives for (t1, t2, switching times, X_start) of the segment
+ * (a model with its own ComputeTraj: its traced rows and the extra final row, which is row R-1; a zero-length or backward
+ * segment: R = 1); u and H are what socp_eval_batch(SOCP_EVAL_CONTROL / SOCP_EVAL_HAMILTONIAN) returns at the row's (t, X)
+ * with the row's aux pair as sw.  The variational state is not traced (neither does the reference: odeTools.cpp:242).
+ * Under SOCP_INT_DOPRI5 a trajectory whose integration fails (NaN result) shows the NaN state in its last row unless the
+ * stride kept the last accepted step.
+ * SOCP_ERR_ARG: stride < 1, cap < 1, B < 0, no problem set; B == 0: SOCP_OK without a launch; a model whose launch table
+ * has no trace entry: SOCP_ERR_UNSUPPORTED.  Two launches (integration; u and H of the stored rows); socp_ctx_counters
+ * advances by B M trajectories.  The _dev form takes device pointers, enqueues on the context's stream and neither copies nor
+ * synchronises; the host form stages through that stream (rows travels both ways).  When count exceeds cap, call again
+ * with cap >= the largest count. */
+int socp_trace_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int stride, int cap, double *d_rows, int *d_count);
+int socp_trace_batch(socp_ctx *ctx, int B, const double *Z, int stride, int cap, double *rows, int *count);
+/* host-pointer form with per-row blocks, like socp_residual_batch_blocks (any of params / time / xnode may be NULL) */
+int socp_trace_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
+                            const double *time, const double *xnode, int stride, int cap, double *rows, int *count);
 
 /* replaces: shooting::ShootingFunctionJacobian (shooting.cpp:996-1130), variational Jacobian
  * for models with modelOrder == 1 (socp_ctx_has_variational); fjac column-major as handed to hybrj (shooting.cpp:889-893).

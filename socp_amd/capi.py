@@ -94,6 +94,7 @@ def lib():
         L.socp_ctx_set_map.argtypes = [_vp, C.c_int, _dp]
         L.socp_ctx_get_map.argtypes = [_vp, _ip, _dp, C.c_int]
         L.socp_ctx_set_integrator.argtypes = [_vp, C.c_int, C.c_double]
+        L.socp_ctx_get_integrator.argtypes = [_vp, _ip, _ip, _dp]
         L.socp_ctx_set_switching_times.argtypes = [_vp, _dp, C.c_int]
         L.socp_ctx_set_variant.argtypes = [_vp, C.c_int]
         L.socp_ctx_set_stream.argtypes = [_vp, _vp, C.c_int]
@@ -126,6 +127,10 @@ def lib():
         L.socp_problem_set_blocks_dev.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
         L.socp_residual_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp]
         L.socp_problem_num_nodes.argtypes = [_vp]
+        L.socp_trace_width.argtypes = [_vp]
+        L.socp_trace_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]
+        L.socp_trace_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip]
+        L.socp_trace_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip]
         L.socp_ctx_get_switching_times.argtypes = [_vp, _dp]
         L.socp_chains_solve.argtypes = [_vp, C.c_int, C.POINTER(ChainOptions), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip,
                                         _ip, _dp, _dp, _dp, C.POINTER(ChainStats)]
@@ -205,6 +210,18 @@ def plugin_load(path):
     rc = lib().socp_plugin_load(os.fsencode(path))
     if rc != OK:
         raise SocpError(rc, lib().socp_last_error(None).decode())
+
+
+def trace_kept_rows(R, stride):
+    """Indices of the rows a batched trace keeps of the R rows integrate_dense_aux reports for a segment: every stride-th from
+    row 0, and the last one (socp_trace_batch_dev).  The definition callers and tests share."""
+    R, stride = int(R), int(stride)
+    if R < 1 or stride < 1:
+        raise ValueError("trace_kept_rows: R >= 1 and stride >= 1 are required")
+    kept = list(range(0, R, stride))
+    if kept[-1] != R - 1:
+        kept.append(R - 1)
+    return kept
 
 
 def _d(a):
@@ -472,6 +489,43 @@ class Context:
                                                     pp.shape[1] if pp is not None else 0, _d(tt) if tt is not None else None,
                                                     _d(xx) if xx is not None else None, _d(F)))
         return F
+
+    # -- batched trace
+    def trace_width(self):
+        """Doubles per trace row of this model: t, X[2d], u[NU], H, aux0, aux1 (socp_trace_width)."""
+        return self.L.socp_trace_width(self.h)
+
+    def trace_batch_dev(self, B, d_Z, stride, cap, d_rows, d_count):
+        """Device pointers (ints); enqueue only, no copy, no synchronise (socp_trace_batch_dev)."""
+        self._chk(self.L.socp_trace_batch_dev(self.h, int(B), _vp(d_Z), int(stride), int(cap), _vp(d_rows), _vp(d_count)))
+
+    def trace_batch(self, Z, stride=1, cap=None, params=None, time=None, xnode=None, fill=None):
+        """Sampled trace rows of every segment of every row of Z: returns (rows[B][M][cap][W], count[B][M]); rows[b][i][k] for
+        k < count[b][i] are row trace_kept_rows(R, stride)[k] of segment i (t, X, u, H, aux0, aux1), the rest holds `fill` (NaN).
+        params / time / xnode: per-row blocks as in residual_batch_blocks.  cap=None runs the two-call protocol: a first call with
+        step_nbr // stride + 3 rows per segment (64 under the adaptive integrator, whose row count is only known afterwards), and
+        one more with cap = count.max() when a segment had more."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B, W = Z.shape[0], self.trace_width()
+        pp = _f64(params).reshape(B, -1) if params is not None else None
+        tt = _f64(time).reshape(B, -1) if time is not None else None
+        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
+        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+
+        def call(c):
+            rows = np.full((B, self.M, c, W), np.nan if fill is None else fill)
+            count = np.zeros((B, self.M), dtype=np.int32)
+            self._chk(self.L.socp_trace_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
+                                                     int(stride), int(c), _d(rows), count.ctypes.data_as(_ip)))
+            return rows, count
+        if cap is not None:
+            return call(int(cap))
+        step_nbr, integrator = C.c_int(), C.c_int()
+        self._chk(self.L.socp_ctx_get_integrator(self.h, C.byref(step_nbr), C.byref(integrator), None))
+        rows, count = call(64 if integrator.value == INT_DOPRI5 else step_nbr.value // int(stride) + 3)
+        if B and count.max() > rows.shape[2]:
+            rows, count = call(int(count.max()))
+        return rows, count
 
     def chains_solve(self, Z0, kind=CHAIN_PLAIN, param_index=0, step=1.0, step_min=1e-12, goal=None, params=None,
                      time_prev=None, x_prev=None, time_goal=None, x_goal=None, xtol=1e-8, maxfev=10000, epsfcn=1e-15,

@@ -351,6 +351,15 @@ int socp_ctx_set_integrator(socp_ctx *c, int kind, double tol)
     return SOCP_OK;
 }
 
+int socp_ctx_get_integrator(const socp_ctx *c, int *step_nbr, int *kind, double *tol)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (step_nbr) *step_nbr = c->P.step_nbr;
+    if (kind) *kind = c->P.integrator;
+    if (tol) *tol = c->P.tol;
+    return SOCP_OK;
+}
+
 int socp_ctx_set_switching_times(socp_ctx *c, const double *sw, int nsw)
 {
     if (!c || (nsw > 0 && !sw)) return fail(c, SOCP_ERR_ARG, "set_switching_times: null argument");
@@ -820,6 +829,94 @@ int socp_residual_batch(socp_ctx *c, int B, const double *Z, double *F)
     HIP_TRY(c, hipMemcpyAsync(F, c->s_out.p, nb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
+}
+
+/* ---- batched trace ------------------------------------------------------------------------- */
+
+int socp_trace_width(const socp_ctx *c) { return c ? 1 + c->S + c->nu + 1 + 2 : SOCP_ERR_ARG; }
+
+namespace {
+int trace_args(socp_ctx *c, int B, int stride, int cap)
+{
+    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "trace_batch: no problem set");
+    if (B < 0 || stride < 1 || cap < 1) return fail(c, SOCP_ERR_ARG, "trace_batch: B >= 0, stride >= 1 and cap >= 1 are required");
+    if (c->vt && !(table_of(c)->trace && table_of(c)->trace_fill))
+        return fail(c, SOCP_ERR_UNSUPPORTED, "trace_batch: this model's launch table has no trace entry");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_trace_batch_dev(socp_ctx *c, int B, const double *d_Z, int stride, int cap, double *d_rows, int *d_count)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc = trace_args(c, B, stride, cap);
+    if (rc != SOCP_OK) return rc;
+    if (B > 0 && (!d_Z || !d_rows || !d_count)) return fail(c, SOCP_ERR_ARG, "trace_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_traj += (long long)B * c->M; c->n_launch += 2;
+    if (c->vt) {
+        HIP_TRY(c, table_of(c)->trace(c->stream, c->P, c->pb, B, d_Z, stride, cap, d_rows, d_count));
+        HIP_TRY(c, table_of(c)->trace_fill(c->stream, c->P, c->pb, B, cap, d_rows, d_count));
+    } else if (use_fast(c)) {
+        HIP_TRY(c, trace_fast(c->model_id, c->stream, c->P, c->pb, B, d_Z, stride, cap, d_rows, d_count));
+        HIP_TRY(c, trace_fill_fast(c->model_id, c->stream, c->P, c->pb, B, cap, d_rows, d_count));
+    } else {
+        HIP_TRY(c, trace_exact(c->model_id, c->stream, c->P, c->pb, B, d_Z, stride, cap, d_rows, d_count));
+        HIP_TRY(c, trace_fill_exact(c->model_id, c->stream, c->P, c->pb, B, cap, d_rows, d_count));
+    }
+    return SOCP_OK;
+}
+
+int socp_trace_batch(socp_ctx *c, int B, const double *Z, int stride, int cap, double *rows, int *count)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = trace_args(c, B, stride, cap);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B > 0 && (!Z || !rows || !count)) return fail(c, SOCP_ERR_ARG, "trace_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t segs = (size_t)B * c->M;
+    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbC = sizeof(int) * segs,
+                 nbR = sizeof(double) * segs * cap * socp_trace_width(c);
+    HIP_TRY(c, c->s_in.reserve(nbZ));
+    HIP_TRY(c, c->s_out.reserve(nbR));
+    HIP_TRY(c, c->s_var.reserve(nbC));
+    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nbZ, hipMemcpyHostToDevice, c->stream));
+    // the caller's buffers travel both ways: what the kernels leave untouched (rows at or beyond min(count, cap)) comes back as it went
+    HIP_TRY(c, hipMemcpyAsync(c->s_out.p, rows, nbR, hipMemcpyHostToDevice, c->stream));
+    const int rc = socp_trace_batch_dev(c, B, c->s_in.as<double>(), stride, cap, c->s_out.as<double>(), c->s_var.as<int>());
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rows, c->s_out.p, nbR, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(count, c->s_var.p, nbC, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_trace_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                            const double *xnode, int stride, int cap, double *rows, int *count)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "trace_batch_blocks: no problem set");
+    if (B < 0) return fail(c, SOCP_ERR_ARG, "trace_batch_blocks: B >= 0 is required");
+    // before anything is sized or copied from it: a wrong stride would read past the caller's array
+    if (params && pstride != c->nparams + 2)
+        return fail(c, SOCP_ERR_ARG, "trace_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nodes = (size_t)c->M + 1;
+    const size_t nbP = params ? sizeof(double) * (size_t)B * pstride : 0, nbT = time ? sizeof(double) * B * nodes : 0,
+                 nbX = xnode ? sizeof(double) * B * nodes * c->S : 0;
+    HIP_TRY(c, c->s_aux.reserve(nbP + nbT + nbX + 64));
+    char *base = c->s_aux.as<char>();
+    double *dP = reinterpret_cast<double *>(base), *dT = reinterpret_cast<double *>(base + nbP), *dX = reinterpret_cast<double *>(base + nbP + nbT);
+    if (nbP) HIP_TRY(c, hipMemcpyAsync(dP, params, nbP, hipMemcpyHostToDevice, c->stream));
+    if (nbT) HIP_TRY(c, hipMemcpyAsync(dT, time, nbT, hipMemcpyHostToDevice, c->stream));
+    if (nbX) HIP_TRY(c, hipMemcpyAsync(dX, xnode, nbX, hipMemcpyHostToDevice, c->stream));
+    const ProblemDev saved = c->pb;
+    int rc = socp_problem_set_blocks_dev(c, params ? dP : nullptr, pstride, time ? dT : nullptr, xnode ? dX : nullptr);
+    if (rc == SOCP_OK) rc = socp_trace_batch(c, B, Z, stride, cap, rows, count);
+    c->pb = saved;
+    return rc;
 }
 
 int socp_fd_jacobian_multi_dev(socp_ctx *c, int np, const double *d_Z, const double *d_Fvec, double epsfcn,

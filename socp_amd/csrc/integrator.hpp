@@ -210,8 +210,10 @@ struct Lane {
     // model.hpp:395-414 / goddard.cpp:298-317 (dt) + odeTools.cpp:128-146 (loop): t is
     // accumulated by t += dt, the last step is clamped to tf - t, and a segment with
     // tf <= t0 + dt/2 (zero length or backward) takes no step at all.
+    // `after(t, X)` sees the accumulated time and the state after every step (the observer form, odeTools.cpp:103-123).
+    template <class After = NoObserver>
     __device__ static __forceinline__ void integrate(const ModelParams &P, double sw0, double sw1,
-                                                    double t0, double tf, double (&X)[S])
+                                                    double t0, double tf, double (&X)[S], After &&after = After())
     {
         const double dt = (tf - t0) / P.step_nbr;
         double t = t0;
@@ -223,6 +225,7 @@ struct Lane {
             const double step = (t + dt > tf) ? (tf - t) : dt;
             rk4(P, sw0, sw1, t, X, step);
             t += dt;
+            after(t, X);
         }
     }
 };
@@ -326,15 +329,7 @@ __global__ __launch_bounds__(64) void traj_dense_kernel(ModelParams P, double t0
         // the adaptive integrator's own steps: row k = time and state at the end of the k-th accepted step
         Lane<Mdl>::integrate_dopri5(P, sw0, sw1, t0, tf, X, NoStepHook(), keep);
     } else {
-        const double dt = (tf - t0) / P.step_nbr;
-        double t = t0;
-        int guard = P.step_nbr + 8;
-        while (t < (tf - dt / 2) && guard-- > 0) {
-            const double step = (t + dt > tf) ? (tf - t) : dt;
-            Lane<Mdl>::rk4(P, sw0, sw1, t, X, step);
-            t += dt;
-            keep(t, X);
-        }
+        Lane<Mdl>::integrate(P, sw0, sw1, t0, tf, X, keep);
     }
     *rows = r;
 }
@@ -347,6 +342,45 @@ __global__ __launch_bounds__(64) void traj_dense_kernel(ModelParams P, double t0
 //   i == M-1   : F[d..2d)           final rows (+ H row when tf is FREE)
 // `Emit` receives (row index, value).
 // ---------------------------------------------------------------------------------------------
+// What the integration of segment i starts from -- shared by the residual kernels and the trace kernel, so that a traced
+// segment IS the segment the residual integrates: its timeline entries, the model's two auxiliary scalars, and
+// (segment_start) its start state z[S i .. S i + S).
+// Plain member functions on purpose, like the local closures they replace: written as a __forceinline__ helper that hands the
+// four values back (through references or in a struct) the same arithmetic moved 47 of the throughput flavour's 122 hot kernels
+// by one or two VGPRs; in this form every existing kernel keeps its registers, spills and scratch (profiles/trace_kernel_meta.txt).
+template <class ZRead>
+struct Timeline {
+    const ProblemDev &pb;
+    const ZRead &z;
+    // timeline entries (shooting.cpp:1579-1617)
+    __device__ double jt(int j) const { const int kind = pb.node_kind[j]; return kind >= 0 ? z(kind) : pb.time[j]; }
+    __device__ double nt(int k) const
+    {
+        const int kind = pb.node_kind[k];
+        if (kind >= -1) return jt(k);
+        const int a = pb.lo[k], b = pb.hi[k];
+        const double ta = jt(a), tb = jt(b);
+        return ta + (k - a) * (tb - ta) / (b - a);
+    }
+    // model switching times = FREE node times with index < M, in node order (:1604,1615); `node` = pb.sw_node0 / sw_node1
+    // (a model with its own ComputeTraj keeps its two auxiliary scalars for itself: they are not switching times)
+    template <class Mdl>
+    __device__ double switching_time(double dflt, int node) const
+    {
+        if constexpr (!has_custom_traj<Mdl>::value) {
+            if (node >= 0) return nt(node);
+        }
+        return dflt;
+    }
+};
+
+template <int S, class ZRead>
+__device__ __forceinline__ void segment_start(const ZRead &z, int first, double (&X)[S])
+{
+#pragma unroll
+    for (int k = 0; k < S; k++) X[k] = z(first + k);
+}
+
 template <class Mdl, int INTEG, class ZRead, class Emit>
 __device__ __forceinline__ void segment_residual(const ModelParams &P, const ProblemDev &pb,
                                                  const ZRead &z, int i, Emit &&emit)
@@ -355,30 +389,15 @@ __device__ __forceinline__ void segment_residual(const ModelParams &P, const Pro
     constexpr int D = Mdl::D;
     const int M = pb.M;
 
-    // timeline entries this segment needs (shooting.cpp:1579-1617)
-    auto jt = [&](int j) -> double { const int kind = pb.node_kind[j]; return kind >= 0 ? z(kind) : pb.time[j]; };
-    auto nt = [&](int k) -> double {
-        const int kind = pb.node_kind[k];
-        if (kind >= -1) return jt(k);
-        const int a = pb.lo[k], b = pb.hi[k];
-        const double ta = jt(a), tb = jt(b);
-        return ta + (k - a) * (tb - ta) / (b - a);
-    };
-    const double t1 = nt(i), t2 = nt(i + 1);
-    // model switching times = FREE node times with index < M, in node order (:1604,1615)
-    // (a model with its own ComputeTraj keeps its two auxiliary scalars for itself: they are not switching times)
-    double sw0 = P.sw0, sw1 = P.sw1;
-    if constexpr (!has_custom_traj<Mdl>::value) {
-        if (pb.sw_node0 >= 0) sw0 = nt(pb.sw_node0);
-        if (pb.sw_node1 >= 0) sw1 = nt(pb.sw_node1);
-    }
+    const Timeline<ZRead> tl{pb, z};
+    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
+    double sw0 = tl.template switching_time<Mdl>(P.sw0, pb.sw_node0), sw1 = tl.template switching_time<Mdl>(P.sw1, pb.sw_node1);
 
     double X[S];
     if (i == 0) {
         // model.hpp:196-228 InitialFunction / :239-290 InitialHFunction, isJac == 0.
         // Done BEFORE the integration so the node state is not live across it (register budget).
-#pragma unroll
-        for (int k = 0; k < S; k++) X[k] = z(k);
+        segment_start(z, 0, X);
 #pragma unroll
         for (int j = 0; j < D; j++) {
             const bool fr = pb.mode_x[j] == 1;
@@ -386,8 +405,7 @@ __device__ __forceinline__ void segment_residual(const ModelParams &P, const Pro
         }
         if (pb.ft_row[0] >= 0) emit(pb.ft_row[0], Mdl::hamiltonian(P, sw0, sw1, t1, X));
     } else {
-#pragma unroll
-        for (int k = 0; k < S; k++) X[k] = z(S * i + k);
+        segment_start(z, S * i, X);
     }
     Lane<Mdl>::template integrate_with<INTEG>(P, sw0, sw1, t1, t2, X);     // shooting.cpp:943 Move(t1, X1, t2)
 
@@ -641,6 +659,127 @@ __global__ __launch_bounds__(64) void eval_lane_kernel(ModelParams P, int what, 
     } else {
         out[b] = Mdl::hamiltonian(P, s0, s1, t[b], X);
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// K_trace: the sampled trace rows of every segment of B unknown vectors (shooting::Trace, shooting.cpp:496-544, for a
+// whole batch).  Z[B][n] -> rows[B][M][cap][W], count[B][M];  W = 1 + S + NU + 1 + 2:  t, X[S], u[NU], H, aux0, aux1.
+// One lane = (row, segment), the lane mapping of K_res with direct stores.  Segment i is integrated from the shared
+// prologue (Timeline / segment_start) by the SAME loops the residual runs -- the rows leave through their step
+// hooks -- so row k is what traj_dense_kernel reports for that segment, and row k is KEPT iff k % stride == 0 or it is
+// the last one.  This launch stores t, X and the aux pair of the kept rows; trace_fill_kernel adds u and H, one lane
+// per kept row, which keeps control_only / hamiltonian out of this kernel's register budget.
+// A lane carries across the integration only two counters beside what the residual lane carries; the row address is
+// formed from them at the store.  Every store site is ONE block under ONE computed predicate (see the note in
+// segment_residual).  A kept row is W consecutive doubles and a segment's rows are adjacent.
+// An adaptive trajectory that fails (NaN result, integrate_dopri5) has no row for the failed step: its last row
+// reports the NaN state, unless the stride had already kept the last accepted step.
+// ---------------------------------------------------------------------------------------------
+template <class Mdl>
+constexpr int trace_width() { return 1 + Mdl::S + Mdl::NU + 1 + 2; }
+
+template <class Mdl, int INTEG, class ZRead>
+__device__ __forceinline__ void segment_trace(const ModelParams &P, const ProblemDev &pb, const ZRead &z, int i,
+                                              int stride, int cap, double *__restrict__ slab, int *__restrict__ count)
+{
+    constexpr int S = Mdl::S;
+    constexpr int W = trace_width<Mdl>();
+    const Timeline<ZRead> tl{pb, z};
+    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
+    double sw0 = tl.template switching_time<Mdl>(P.sw0, pb.sw_node0), sw1 = tl.template switching_time<Mdl>(P.sw1, pb.sw_node1);
+    double X[S];
+    segment_start(z, S * i, X);
+
+    int kept = 0;       // rows kept so far (those beyond cap are counted, not stored)
+    int left = 1;       // rows until the next one the stride keeps; == stride right after a kept row
+    auto put = [&](bool want, double t, const double (&Xr)[S], double b0, double b1) {
+        const bool st = want && kept < cap;
+        if (st) {
+            double *row = slab + (long)kept * W;
+            row[0] = t;
+#pragma unroll
+            for (int k = 0; k < S; k++) row[1 + k] = Xr[k];
+            row[W - 2] = b0;
+            row[W - 1] = b1;
+        }
+        kept += want ? 1 : 0;
+    };
+    auto sample = [&](double t, const double (&Xr)[S], double b0, double b1) {
+        const bool due = --left == 0;
+        put(due, t, Xr, b0, b1);
+        left = due ? stride : left;
+    };
+
+    if constexpr (has_custom_traj<Mdl>::value) {
+        Mdl::template compute_traj<INTEG>(P, sw0, sw1, t1, t2, X, sample);
+        // the extra row of traj_dense_kernel -- the state as ComputeTraj returns it and the flags it leaves -- is the last: always kept
+        put(true, t2, X, sw0, sw1);
+    } else {
+        sample(t1, X, sw0, sw1);                                         // row 0 = (t1, X_start)
+        double tl = t1;
+        auto after = [&](double t, const double (&Xr)[S]) { tl = t; sample(t, Xr, sw0, sw1); };
+        if constexpr (INTEG == 1) Lane<Mdl>::integrate_dopri5(P, sw0, sw1, t1, t2, X, NoStepHook(), after);
+        else Lane<Mdl>::integrate(P, sw0, sw1, t1, t2, X, after);
+        put(left != stride, tl, X, sw0, sw1);                            // the last row, when the stride passed over it
+    }
+    *count = kept;
+}
+
+template <class Mdl, int WPE, int INTEG = 0, bool PERPROB = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) void trace_lane_kernel(ModelParams P, ProblemDev pb, int B,
+                                                           const double *__restrict__ Z, int stride, int cap,
+                                                           double *__restrict__ rows, int *__restrict__ count)
+{
+    const long T = (long)blockIdx.x * 64 + threadIdx.x;              // = b * M + i: slab and count index
+    if (T >= (long)B * pb.M) return;
+    const long b = T / pb.M;
+    const int i = (int)(T - b * pb.M);
+    const double *zr = Z + b * pb.n;
+    auto z = [=](int k) -> double { return zr[k]; };
+    double *slab = rows + T * cap * trace_width<Mdl>();
+    if constexpr (PERPROB) {
+        ModelParams Pq = P;
+        ProblemDev pq = pb;
+        load_problem_block(pb, b, Pq, pq);
+        segment_trace<Mdl, INTEG>(Pq, pq, z, i, stride, cap, slab, count + T);
+    } else {
+        segment_trace<Mdl, INTEG>(P, pb, z, i, stride, cap, slab, count + T);
+    }
+}
+
+// K_trace_fill: u and H of every stored row, in place; one lane = (row b, segment i, kept row k), the rows at or beyond
+// min(count, cap) untouched.  Evaluated like eval_lane_kernel evaluates them: at the row's (t, X) with the row's aux pair.
+template <class Mdl, bool PERPROB>
+__global__ __launch_bounds__(64) void trace_fill_kernel(ModelParams P, ProblemDev pb, int B, int cap,
+                                                        double *__restrict__ rows, const int *__restrict__ count)
+{
+    constexpr int S = Mdl::S;
+    constexpr int W = trace_width<Mdl>();
+    const long T = (long)blockIdx.x * 64 + threadIdx.x;              // = (b * M + i) * cap + k
+    if (T >= (long)B * pb.M * cap) return;
+    const long seg = T / cap;
+    const int k = (int)(T - seg * cap);
+    if (k >= count[seg]) return;
+    double *row = rows + T * W;
+    double X[S];
+#pragma unroll
+    for (int j = 0; j < S; j++) X[j] = row[1 + j];
+    const double t = row[0], a0 = row[W - 2], a1 = row[W - 1];
+    double u[3];
+    double H;
+    if constexpr (PERPROB) {
+        ModelParams Pq = P;
+        ProblemDev pq = pb;
+        load_problem_block(pb, seg / pb.M, Pq, pq);
+        Mdl::control_only(Pq, a0, a1, t, X, u);
+        H = Mdl::hamiltonian(Pq, a0, a1, t, X);
+    } else {
+        Mdl::control_only(P, a0, a1, t, X, u);
+        H = Mdl::hamiltonian(P, a0, a1, t, X);
+    }
+#pragma unroll
+    for (int j = 0; j < Mdl::NU; j++) row[1 + S + j] = u[j];
+    row[1 + S + Mdl::NU] = H;
 }
 
 }  // namespace socp

@@ -52,11 +52,18 @@ inline int rows_per_block(int M, int n)
                                double tf, double sw0, double sw1, const double *X0, double *dense,   \
                                double *times, int cap, int *rows, double *aux);                      \
     hipError_t eval_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P, int what, int B,   \
-                              const double *t, const double *sw, const double *X, double *out);
+                              const double *t, const double *sw, const double *X, double *out);      \
+    hipError_t trace_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                   \
+                               const ProblemDev &pb, int B, const double *Z, int stride, int cap,    \
+                               double *rows, int *count);                                            \
+    hipError_t trace_fill_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,              \
+                                    const ProblemDev &pb, int B, int cap, double *rows,              \
+                                    const int *count);
 
 // Launch table of an out-of-tree model (include/socp_plugin.h, plugin_impl.hpp): what the C-ABI layer calls
 // instead of the built-in flavour launchers when a context is created with a registered model id.
-constexpr int kPluginAbi = 5;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table
+constexpr int kPluginAbi = 6;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+                                   // 6: batched trace launchers
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -70,6 +77,9 @@ struct ModelLaunchers {
     hipError_t (*var_traj)(hipStream_t, const ModelParams &, int, const double *, const double *, const double *, double *);
     hipError_t (*var_jacobian)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *, double *, double *, double *);
     hipError_t (*var_eval)(hipStream_t, const ModelParams &, int, int, const double *, const double *, int, double *);
+    // batched trace (socp_trace_batch): kept rows' t, X, aux and their number; then u and H of the stored rows in place
+    hipError_t (*trace)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, int, double *, int *);
+    hipError_t (*trace_fill)(hipStream_t, const ModelParams &, const ProblemDev &, int, int, double *, const int *);
 };
 
 SOCP_DECLARE_LAUNCHERS(exact)

@@ -103,6 +103,34 @@ hipError_t SOCP_CAT(fdrows_, SOCP_FLAVOUR)(int model_id, hipStream_t st, const M
     return hipGetLastError();
 }
 
+// Batched trace: launch 1 integrates and stores t, X, aux of the kept rows and their number (the residual's lane mapping and
+// occupancy rule); launch 2 adds u and H, one lane per stored row.  The fill takes the Goddard law the way the evaluation
+// kernel does (from the context's mu2), and the general law when every problem brings its own parameters.
+hipError_t SOCP_CAT(trace_, SOCP_FLAVOUR)(int model_id, hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B,
+                                          const double *Z, int stride, int cap, double *rows, int *count)
+{
+    if (B <= 0) return hipSuccess;
+    SOCP_DISPATCH_PB(trace_lane_kernel, blocks_for((long)B * pb.M), st, P, pb, B, Z, stride, cap, rows, count);
+    return hipGetLastError();
+}
+
+hipError_t SOCP_CAT(trace_fill_, SOCP_FLAVOUR)(int model_id, hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B,
+                                               int cap, double *rows, const int *count)
+{
+    if (B <= 0) return hipSuccess;
+    const unsigned grid = blocks_for((long)B * pb.M * cap);
+#define SOCP_FILL_LAUNCH(MDL, PP) hipLaunchKernelGGL((trace_fill_kernel<MDL, PP>), dim3(grid), dim3(64), 0, st, P, pb, B, cap, rows, count)
+    if (model_id == 1 && pb.pp_params) SOCP_FILL_LAUNCH(SOCP_GODDARD, true);
+    else if (model_id == 1 && P.p[6] > 0) SOCP_FILL_LAUNCH(SOCP_GODDARD_SMOOTH, false);
+    else if (model_id == 1) SOCP_FILL_LAUNCH(SOCP_GODDARD, false);
+    else if (model_id == 3 && pb.pp_params) SOCP_FILL_LAUNCH(SOCP_COVID, true);
+    else if (model_id == 3) SOCP_FILL_LAUNCH(SOCP_COVID, false);
+    else if (pb.pp_params) SOCP_FILL_LAUNCH(SOCP_DINT, true);
+    else SOCP_FILL_LAUNCH(SOCP_DINT, false);
+#undef SOCP_FILL_LAUNCH
+    return hipGetLastError();
+}
+
 #ifdef SOCP_DEFINE_COMMON
 hipError_t fd_diff(hipStream_t st, int n, int np, const double *z, double eps, const double *rows, double *fjac)
 {

@@ -38,7 +38,7 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
 #include "launch.hpp"
@@ -126,6 +126,24 @@ hipError_t eval(hipStream_t st, const ModelParams &P, int what, int B, const dou
     return hipGetLastError();
 }
 
+template <class Mdl>
+hipError_t trace(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *rows,
+                 int *count)
+{
+    if (B <= 0) return hipSuccess;
+    SOCP_PLUGIN_LAUNCH_PB(trace_lane_kernel, blocks_for((long)B * pb.M), st, P, pb, B, Z, stride, cap, rows, count);
+    return hipGetLastError();
+}
+template <class Mdl>
+hipError_t trace_fill(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, int cap, double *rows, const int *count)
+{
+    if (B <= 0) return hipSuccess;
+    const unsigned grid = blocks_for((long)B * pb.M * cap);
+    if (pb.pp_params) hipLaunchKernelGGL((trace_fill_kernel<Mdl, true>), dim3(grid), dim3(64), 0, st, P, pb, B, cap, rows, count);
+    else hipLaunchKernelGGL((trace_fill_kernel<Mdl, false>), dim3(grid), dim3(64), 0, st, P, pb, B, cap, rows, count);
+    return hipGetLastError();
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -143,7 +161,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     int i = 0;
     for (double v : defaults) if (i < kMaxParams) t.default_params[i++] = v;
     t.traj = &traj<Mdl>; t.residual = &residual<Mdl>; t.fdjac = &fdjac<Mdl>; t.fdrows = &fdrows<Mdl>;
-    t.dense = &dense<Mdl>; t.eval = &eval<Mdl>;
+    t.dense = &dense<Mdl>; t.eval = &eval<Mdl>; t.trace = &trace<Mdl>; t.trace_fill = &trace_fill<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

@@ -277,6 +277,21 @@ def warm_up(ctx, args, solve_first):
     return ctx.counters()[0]
 
 
+def trace_local(ctx, args, local, lo, rank, params=None):
+    """--trace-stride / --trace-out: the sampled trajectories (socp_trace_batch) of this rank's CONVERGED chains, each with its own
+    parameter block when the chains have one, written to PATH.rank<r>.npz: rows [k][M][cap][W] (t, X, u, H, aux0, aux1),
+    count [k][M], index [k] = position of the chain in the sweep's start table.  Runs after the timed solve; trajectories stay on
+    the rank that solved them (a 4096-start sweep at stride 100 is 70 MB).  Returns the record entry of this rank."""
+    conv = np.where(np.asarray(local["info"]) == 1)[0]
+    t0 = time.perf_counter()
+    rows, count = ctx.trace_batch(np.asarray(local["z"])[conv], stride=args.trace_stride, params=None if params is None else params[conv])
+    wall = time.perf_counter() - t0
+    path = "%s.rank%d.npz" % (args.trace_out, rank)
+    np.savez(path, rows=rows, count=count, index=lo + conv)
+    return {"stride": args.trace_stride, "chains": int(len(conv)), "rows_per_segment_max": int(count.max()) if len(conv) else 0,
+            "wall_s": wall, "file": path}
+
+
 def interceptor_sweep(args, torch, dist, capi, world, rank, local_rank, dev, record_fd):
     eps = args.eps if args.eps is not None else 1e-3
     ctx, Z0, _kw = interceptor_config5_sweep(args.starts, variant=args.variant, eps=eps, ode_tol=args.ode_tol, fixed_step=args.fixed_step,
@@ -307,10 +322,11 @@ def interceptor_sweep(args, torch, dist, capi, world, rank, local_rank, dev, rec
     traj = torch.tensor([float(ctx.counters()[0] - c0)], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(traj)
+    extra = {"trace_rank%d" % rank: trace_local(ctx, args, local, shard(args.starts, rank, world)[0], rank)} if args.trace_out else {}
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n]
-        record = json.dumps({"sweep": "interceptor_config5_M21_n%d_%s" % (n, "rk4" if args.fixed_step else "dopri5_tol%g" % args.ode_tol),
+        record = json.dumps({**extra, "sweep": "interceptor_config5_M21_n%d_%s" % (n, "rk4" if args.fixed_step else "dopri5_tol%g" % args.ode_tol),
                              "starts": args.starts, "eps": eps, "n_gpus": world, "variant": args.variant, "solver": args.solver, "xtol": args.xtol, "wall_s": wall,
                              "warmup_starts": args.warmup,
                              "converged": int(np.sum(info == 1)), "info_histogram": {str(k): int(np.sum(info == k)) for k in np.unique(info)},
@@ -353,7 +369,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=8, help="starts of one untimed solve before the timed one (what a process pays once: the "
                     "context's second stream ~6 ms, first-launch code-object loads ~9 ms); 0: the timed call includes them")
     ap.add_argument("--solver", choices=sorted(SOLVERS), default="auto", help=SOLVER_HELP)
+    ap.add_argument("--trace-stride", type=int, default=100, help="with --trace-out: keep every K-th row of each segment's trace (and the last)")
+    ap.add_argument("--trace-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank traces the converged chains of its own block in one batch (socp_trace_batch), with the "
+                         "chains' own parameter blocks, and writes PATH.rank<r>.npz (rows, count, index of the chains).  Trajectories are "
+                         "NOT gathered across ranks.  Absent: the timed wall and the printed record are unchanged")
     args = ap.parse_args()
+    if args.trace_stride < 1:
+        ap.error("--trace-stride must be >= 1")
 
     # stdout carries only the JSON record: RCCL prints a version banner to file descriptor 1 when a process group is created
     import sys
@@ -433,11 +456,18 @@ def main():
     traj = torch.tensor([float(ctx.counters()[0] - c0)], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(traj)
+    extra = {}
+    if args.trace_out:
+        blocks = None
+        if chain_kw is not None:                        # every chain at the KD it reached, then the context's two switching times
+            blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
+            blocks[:, 2] = local["param_final"]
+        extra = {"trace_rank%d" % rank: trace_local(ctx, args, local, lo_w, rank, blocks)}
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
         spread = float(np.max(np.abs(conv - np.median(conv, axis=0))) / np.max(np.abs(conv))) if len(conv) else None
-        record = json.dumps({"solution_spread_rel": spread, "max_fnorm_converged": float(np.max(table[info == 1, -3])) if len(conv) else None,
+        record = json.dumps({**extra, "solution_spread_rel": spread, "max_fnorm_converged": float(np.max(table[info == 1, -3])) if len(conv) else None,
                           "sweep": ("goddard_kd_continuation_chains_M6_n85" if chain_kw is not None else
                                     "goddard_single_shooting_n14" if args.segments == 1 else "goddard_multiple_shooting_M%d_n%d" % (args.segments, n_unknown)),
                           "chains_per_s": (args.starts / wall) if chain_kw is not None else None,
