@@ -269,6 +269,32 @@ int socp_trace_batch(socp_ctx *ctx, int B, const double *Z, int stride, int cap,
 int socp_trace_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
                             const double *time, const double *xnode, int stride, int cap, double *rows, int *count);
 
+/* Integrated running cost of a whole batch of unknown vectors: what ranks the extremals a multi-start sweep ends in.  [ext] The
+ * reference never computes it.  Every in-tree Hamiltonian (and the example plugin's) has the form H = L + <p, f_x>, so the running
+ * cost is L(t, X) = H(t, X) - sum_k p_k f_k(t, X), from the model's Hamiltonian and right-hand side; the sum runs over the d
+ * state components, left to right.  H - p.f carries an absolute rounding error of the order of eps |p.f| per evaluation.
+ * Z[B][n] -> cost[B][M]: segment i of row b is integrated exactly as the residual integrates it (same timeline, switching times,
+ * start state z[s i .. s i + s), per-problem blocks of socp_problem_set_blocks_dev: row b reads block b) with the fixed-step RK4
+ * steps of the residual, and q' = L is carried through those steps as a quadrature variable: q = 0.0 at the segment's start,
+ * q <- q + (step/6)(L1 + (L4 + 2 (L2 + L3))) with L1..L4 at the four stage points (t, X) of the step; cost[b][i] = q at the
+ * segment's end.  A zero-length or backward segment takes no step: cost = 0.0 (+0.0) and Xend = the start state.
+ * total[b] (may be NULL) = cost[b][0] + cost[b][1] + ... + cost[b][M-1], summed in that order; Xend[b][i][s] (may be NULL) = the
+ * state at the end of segment i, what socp_integrate_batch gives for the segment.  Terminal cost terms are not included.
+ * socp_ctx_has_cost: 1 when the context's model has a cost kernel, 0 when not (a model with its own ComputeTraj -- the
+ * interceptor: its chart changes rewrite the costate in mid-trajectory).
+ * SOCP_ERR_ARG: no problem set, B < 0, B > 0 with Z or cost NULL, _blocks with params and param_stride != nparams + 2;
+ * B == 0: SOCP_OK without a launch; SOCP_ERR_UNSUPPORTED: the context's integrator is SOCP_INT_DOPRI5 (the message says so), or
+ * the model's launch table has no cost entry.  An error leaves the context unchanged.
+ * One launch, one more with total; socp_ctx_counters advances by B M trajectories.  The _dev form takes device pointers,
+ * enqueues on the context's stream and neither copies nor synchronises; the host forms stage through that stream and return
+ * when the results are in the caller's arrays.  _blocks: per-row blocks like socp_residual_batch_blocks (any of params / time /
+ * xnode may be NULL); the context's own blocks are restored afterwards. */
+int socp_ctx_has_cost(const socp_ctx *ctx);   /* 1 / 0 */
+int socp_cost_batch_dev(socp_ctx *ctx, int B, const double *d_Z, double *d_cost, double *d_total, double *d_Xend);
+int socp_cost_batch(socp_ctx *ctx, int B, const double *Z, double *cost, double *total, double *Xend);
+int socp_cost_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
+                           const double *time, const double *xnode, double *cost, double *total, double *Xend);
+
 /* replaces: shooting::ShootingFunctionJacobian (shooting.cpp:996-1130), variational Jacobian
  * for models with modelOrder == 1 (socp_ctx_has_variational); fjac column-major as handed to hybrj (shooting.cpp:889-893).
  * The variational state follows the context's integrator (socp_ctx_set_integrator): fixed-step RK4, or -- as the reference does

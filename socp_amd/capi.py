@@ -131,6 +131,10 @@ def lib():
         L.socp_trace_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]
         L.socp_trace_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip]
         L.socp_trace_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _ip]
+        L.socp_ctx_has_cost.argtypes = [_vp]
+        L.socp_cost_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
+        L.socp_cost_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
+        L.socp_cost_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]
         L.socp_ctx_get_switching_times.argtypes = [_vp, _dp]
         L.socp_chains_solve.argtypes = [_vp, C.c_int, C.POINTER(ChainOptions), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip,
                                         _ip, _dp, _dp, _dp, C.POINTER(ChainStats)]
@@ -526,6 +530,32 @@ class Context:
         if B and count.max() > rows.shape[2]:
             rows, count = call(int(count.max()))
         return rows, count
+
+    # -- batched cost
+    def has_cost(self):
+        """Whether this model has a running-cost kernel (socp_ctx_has_cost); the interceptor has none."""
+        return self.L.socp_ctx_has_cost(self.h) == 1
+
+    def cost_batch_dev(self, B, d_Z, d_cost, d_total=None, d_Xend=None):
+        """Device pointers (ints; d_total / d_Xend may be None); enqueue only, no copy, no synchronise (socp_cost_batch_dev)."""
+        self._chk(self.L.socp_cost_batch_dev(self.h, int(B), _vp(d_Z), _vp(d_cost), _vp(d_total), _vp(d_Xend)))
+
+    def cost_batch(self, Z, params=None, time=None, xnode=None, total=True, xend=False):
+        """Integrated running cost L = H - <p, f_x> of every segment of every row of Z, along the residual's fixed RK4 steps:
+        returns dict(cost[B][M], total[B] or None, xend[B][M][2d] or None).  params / time / xnode: per-row blocks as in
+        residual_batch_blocks.  Fixed-step integrator only; not for the interceptor (has_cost)."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        pp = _f64(params).reshape(B, -1) if params is not None else None
+        tt = _f64(time).reshape(B, -1) if time is not None else None
+        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
+        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+        cost = np.empty((B, self.M))
+        tot = np.empty(B) if total else None
+        xe = np.empty((B, self.M, self.s)) if xend else None
+        self._chk(self.L.socp_cost_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
+                                                _d(cost), ptr(tot), ptr(xe)))
+        return dict(cost=cost, total=tot, xend=xe)
 
     def chains_solve(self, Z0, kind=CHAIN_PLAIN, param_index=0, step=1.0, step_min=1e-12, goal=None, params=None,
                      time_prev=None, x_prev=None, time_goal=None, x_goal=None, xtol=1e-8, maxfev=10000, epsfcn=1e-15,

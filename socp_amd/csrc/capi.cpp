@@ -919,6 +919,91 @@ int socp_trace_batch_blocks(socp_ctx *c, int B, const double *Z, const double *p
     return rc;
 }
 
+/* ---- batched cost -------------------------------------------------------------------------- */
+
+int socp_ctx_has_cost(const socp_ctx *c) { return c ? ((c->vt && !table_of(c)->cost) ? 0 : 1) : SOCP_ERR_ARG; }
+
+namespace {
+// every refusal comes before anything is counted, reserved or enqueued: an error leaves the context as it was
+int cost_args(socp_ctx *c, int B, const void *Z, const void *cost)
+{
+    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "cost_batch: no problem set");
+    if (B < 0) return fail(c, SOCP_ERR_ARG, "cost_batch: B >= 0 is required");
+    if (B > 0 && (!Z || !cost)) return fail(c, SOCP_ERR_ARG, "cost_batch: null argument");
+    if (c->vt && !table_of(c)->cost)
+        return fail(c, SOCP_ERR_UNSUPPORTED, "cost_batch: this model's launch table has no cost entry");
+    if (c->P.integrator == SOCP_INT_DOPRI5)
+        return fail(c, SOCP_ERR_UNSUPPORTED, "cost_batch: the running cost is integrated with the fixed-step integrator only "
+                                             "(this context is set to SOCP_INT_DOPRI5)");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_cost_batch_dev(socp_ctx *c, int B, const double *d_Z, double *d_cost, double *d_total, double *d_Xend)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc = cost_args(c, B, d_Z, d_cost);
+    if (rc != SOCP_OK) return rc;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_traj += (long long)B * c->M; c->n_launch += d_total ? 2 : 1;
+    if (c->vt) HIP_TRY(c, table_of(c)->cost(c->stream, c->P, c->pb, B, d_Z, d_cost, d_Xend));
+    else if (use_fast(c)) HIP_TRY(c, cost_fast(c->model_id, c->stream, c->P, c->pb, B, d_Z, d_cost, d_Xend));
+    else HIP_TRY(c, cost_exact(c->model_id, c->stream, c->P, c->pb, B, d_Z, d_cost, d_Xend));
+    if (d_total) HIP_TRY(c, cost_total(c->stream, B, c->M, d_cost, d_total));
+    return SOCP_OK;
+}
+
+int socp_cost_batch(socp_ctx *c, int B, const double *Z, double *cost, double *total, double *Xend)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = cost_args(c, B, Z, cost);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t segs = (size_t)B * c->M;
+    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbC = sizeof(double) * segs, nbT = total ? sizeof(double) * (size_t)B : 0,
+                 nbX = Xend ? sizeof(double) * segs * c->S : 0;
+    HIP_TRY(c, c->s_in.reserve(nbZ));
+    HIP_TRY(c, c->s_out.reserve(nbC + nbT + nbX));
+    double *dC = c->s_out.as<double>(), *dT = dC + segs, *dX = dT + (total ? B : 0);
+    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nbZ, hipMemcpyHostToDevice, c->stream));
+    const int rc = socp_cost_batch_dev(c, B, c->s_in.as<double>(), dC, total ? dT : nullptr, Xend ? dX : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(cost, dC, nbC, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIP_TRY(c, hipMemcpyAsync(total, dT, nbT, hipMemcpyDeviceToHost, c->stream));
+    if (Xend) HIP_TRY(c, hipMemcpyAsync(Xend, dX, nbX, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_cost_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                           const double *xnode, double *cost, double *total, double *Xend)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = cost_args(c, B, Z, cost);
+    if (rc0 != SOCP_OK) return rc0;
+    // before anything is sized or copied from it: a wrong stride would read past the caller's array
+    if (params && pstride != c->nparams + 2)
+        return fail(c, SOCP_ERR_ARG, "cost_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nodes = (size_t)c->M + 1;
+    const size_t nbP = params ? sizeof(double) * (size_t)B * pstride : 0, nbT = time ? sizeof(double) * B * nodes : 0,
+                 nbX = xnode ? sizeof(double) * B * nodes * c->S : 0;
+    HIP_TRY(c, c->s_aux.reserve(nbP + nbT + nbX + 64));
+    char *base = c->s_aux.as<char>();
+    double *dP = reinterpret_cast<double *>(base), *dT = reinterpret_cast<double *>(base + nbP), *dX = reinterpret_cast<double *>(base + nbP + nbT);
+    if (nbP) HIP_TRY(c, hipMemcpyAsync(dP, params, nbP, hipMemcpyHostToDevice, c->stream));
+    if (nbT) HIP_TRY(c, hipMemcpyAsync(dT, time, nbT, hipMemcpyHostToDevice, c->stream));
+    if (nbX) HIP_TRY(c, hipMemcpyAsync(dX, xnode, nbX, hipMemcpyHostToDevice, c->stream));
+    const ProblemDev saved = c->pb;
+    int rc = socp_problem_set_blocks_dev(c, params ? dP : nullptr, pstride, time ? dT : nullptr, xnode ? dX : nullptr);
+    if (rc == SOCP_OK) rc = socp_cost_batch(c, B, Z, cost, total, Xend);
+    c->pb = saved;
+    return rc;
+}
+
 int socp_fd_jacobian_multi_dev(socp_ctx *c, int np, const double *d_Z, const double *d_Fvec, double epsfcn,
                                double *d_Fjac, int dedup)
 {

@@ -228,6 +228,87 @@ struct Lane {
             after(t, X);
         }
     }
+
+    // ---- integrated running cost (socp_cost_batch): q' = L carried as a quadrature variable through the steps of rk4().
+    // Every in-tree Hamiltonian has the form H = L + <p, f_x>, so the running cost at a stage (t, Y) with F = rhs(t, Y) is
+    // L = H(t, Y) - sum_k Y[D+k] F[k], the sum taken left to right.  The difference carries an absolute rounding error of the
+    // order of eps |p . f| per evaluation.
+    __device__ static __forceinline__ double lagrangian(const ModelParams &P, double sw0, double sw1, double t,
+                                                        const double (&Y)[S], const double (&F)[S])
+    {
+        double s = Y[D] * F[0];
+#pragma unroll
+        for (int k = 1; k < D; k++) s = s + Y[D + k] * F[k];
+        return Mdl::hamiltonian(P, sw0, sw1, t, Y) - s;
+    }
+
+    // rk4() with the quadrature: the state update is the one of rk4(), expression for expression, and
+    // q + (step/6.0)*(L1 + (L4 + 2.0*(L2 + L3))) is the same rule applied to L.  A copy, not a hook into rk4(): the hot kernels
+    // keep their code.
+    __device__ static __forceinline__ void rk4_cost(const ModelParams &P, double sw0, double sw1,
+                                                   double t, double (&X)[S], double step, double &q)
+    {
+        if constexpr (Mdl::kRefOrder) {
+            double F1[S], Fs[S], F[S], Y[S];
+            const double h2 = step / 2.0;
+            const double th = t + step / 2.0;
+            Mdl::rhs(P, sw0, sw1, t, X, F1);
+            const double L1 = lagrangian(P, sw0, sw1, t, X, F1);
+#pragma unroll
+            for (int i = 0; i < S; i++) Y[i] = X[i] + h2 * F1[i];
+            Mdl::rhs(P, sw0, sw1, th, Y, Fs);                 // F2
+            double Ls = lagrangian(P, sw0, sw1, th, Y, Fs);   // L2
+#pragma unroll
+            for (int i = 0; i < S; i++) Y[i] = X[i] + h2 * Fs[i];
+            Mdl::rhs(P, sw0, sw1, th, Y, F);                  // F3
+            Ls = Ls + lagrangian(P, sw0, sw1, th, Y, F);      // L2 + L3
+#pragma unroll
+            for (int i = 0; i < S; i++) { Y[i] = X[i] + step * F[i]; Fs[i] = Fs[i] + F[i]; }   // F2 + F3
+            Mdl::rhs(P, sw0, sw1, t + step, Y, F);            // F4
+            const double L4 = lagrangian(P, sw0, sw1, t + step, Y, F);
+            const double h6 = step / 6.0;
+#pragma unroll
+            for (int i = 0; i < S; i++) X[i] = X[i] + h6 * (F1[i] + (F[i] + 2.0 * Fs[i]));
+            q = q + h6 * (L1 + (L4 + 2.0 * Ls));
+        } else {
+            // throughput flavour: the running sums of rk4(), and one more for L
+            double A[S], F[S], Y[S];
+            const double h2 = 0.5 * step;
+            const double th = t + h2;
+            Mdl::rhs(P, sw0, sw1, t, X, A);
+            double LA = lagrangian(P, sw0, sw1, t, X, A);
+#pragma unroll
+            for (int i = 0; i < S; i++) Y[i] = X[i] + h2 * A[i];
+            Mdl::rhs(P, sw0, sw1, th, Y, F);
+            LA = LA + 2.0 * lagrangian(P, sw0, sw1, th, Y, F);
+#pragma unroll
+            for (int i = 0; i < S; i++) { Y[i] = X[i] + h2 * F[i]; A[i] = A[i] + 2.0 * F[i]; }
+            Mdl::rhs(P, sw0, sw1, th, Y, F);
+            LA = LA + 2.0 * lagrangian(P, sw0, sw1, th, Y, F);
+#pragma unroll
+            for (int i = 0; i < S; i++) { Y[i] = X[i] + step * F[i]; A[i] = A[i] + 2.0 * F[i]; }
+            Mdl::rhs(P, sw0, sw1, t + step, Y, F);
+            LA = LA + lagrangian(P, sw0, sw1, t + step, Y, F);
+            const double h6 = step * (1.0 / 6.0);
+#pragma unroll
+            for (int i = 0; i < S; i++) X[i] = X[i] + h6 * (A[i] + F[i]);
+            q = q + h6 * LA;
+        }
+    }
+
+    // the loop of integrate(), statement for statement, around rk4_cost(): the steps are the steps the residual takes
+    __device__ static __forceinline__ void integrate_cost(const ModelParams &P, double sw0, double sw1,
+                                                         double t0, double tf, double (&X)[S], double &q)
+    {
+        const double dt = (tf - t0) / P.step_nbr;
+        double t = t0;
+        int guard = P.step_nbr + 8;
+        while (t < (tf - dt / 2) && guard-- > 0) {
+            const double step = (t + dt > tf) ? (tf - t) : dt;
+            rk4_cost(P, sw0, sw1, t, X, step, q);
+            t += dt;
+        }
+    }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -781,5 +862,72 @@ __global__ __launch_bounds__(64) void trace_fill_kernel(ModelParams P, ProblemDe
     for (int j = 0; j < Mdl::NU; j++) row[1 + S + j] = u[j];
     row[1 + S + Mdl::NU] = H;
 }
+
+// ---------------------------------------------------------------------------------------------
+// K_cost: the integrated running cost of every segment of B unknown vectors (socp_cost_batch).  Z[B][n] -> cost[B][M],
+// optionally the segments' end states Xend[B][M][S].  One lane = (row, segment), T = b M + i, the lane mapping of K_trace.
+// Segment i starts from the shared prologue (Timeline / segment_start), so the segment costed IS the segment the residual
+// integrates, and Lane::integrate_cost takes the residual's fixed steps with q' = L = H - <p, f_x> beside the state, q = 0.0
+// at the segment's start.  A zero-length or backward segment takes no step: cost +0.0, end state = start state.
+// Fixed-step RK4 only, and no model with its own ComputeTraj (its chart changes rewrite the costate in mid-trajectory).
+// Consecutive lanes store consecutive doubles of cost; every store site is ONE block under ONE computed predicate (see the
+// note in segment_residual).
+// ---------------------------------------------------------------------------------------------
+template <class Mdl, class ZRead>
+__device__ __forceinline__ void segment_cost(const ModelParams &P, const ProblemDev &pb, const ZRead &z, int i,
+                                             double *__restrict__ cost, double *__restrict__ xend)
+{
+    static_assert(!has_custom_traj<Mdl>::value, "the running cost of a model with its own ComputeTraj needs a definition of its own");
+    constexpr int S = Mdl::S;
+    const Timeline<ZRead> tl{pb, z};
+    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
+    const double sw0 = tl.template switching_time<Mdl>(P.sw0, pb.sw_node0), sw1 = tl.template switching_time<Mdl>(P.sw1, pb.sw_node1);
+    double X[S];
+    segment_start(z, S * i, X);
+    double q = 0.0;
+    Lane<Mdl>::integrate_cost(P, sw0, sw1, t1, t2, X, q);
+    *cost = q;
+    const bool st = xend != nullptr;
+    if (st) {
+#pragma unroll
+        for (int k = 0; k < S; k++) xend[k] = X[k];
+    }
+}
+
+template <class Mdl, int WPE, int INTEG = 0, bool PERPROB = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) void cost_lane_kernel(ModelParams P, ProblemDev pb, int B,
+                                                          const double *__restrict__ Z, double *__restrict__ cost,
+                                                          double *__restrict__ Xend)
+{
+    static_assert(INTEG == 0, "the running cost is integrated with the fixed-step integrator only");
+    const long T = (long)blockIdx.x * 64 + threadIdx.x;              // = b * M + i: index into cost, row of Xend
+    if (T >= (long)B * pb.M) return;
+    const long b = T / pb.M;
+    const int i = (int)(T - b * pb.M);
+    const double *zr = Z + b * pb.n;
+    auto z = [=](int k) -> double { return zr[k]; };
+    double *xe = Xend ? Xend + T * Mdl::S : nullptr;
+    if constexpr (PERPROB) {
+        ModelParams Pq = P;
+        ProblemDev pq = pb;
+        load_problem_block(pb, b, Pq, pq);
+        segment_cost<Mdl>(Pq, pq, z, i, cost + T, xe);
+    } else {
+        segment_cost<Mdl>(P, pb, z, i, cost + T, xe);
+    }
+}
+
+#ifdef SOCP_DEFINE_COMMON
+// K_cost_total: total[b] = cost[b][0] + cost[b][1] + ... + cost[b][M-1], summed left to right; one lane per row
+__global__ __launch_bounds__(64) void cost_total_kernel(int B, int M, const double *__restrict__ cost, double *__restrict__ total)
+{
+    const long b = (long)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const double *c = cost + b * M;
+    double s = c[0];
+    for (int i = 1; i < M; i++) s = s + c[i];
+    total[b] = s;
+}
+#endif
 
 }  // namespace socp

@@ -58,12 +58,15 @@ inline int rows_per_block(int M, int n)
                                double *rows, int *count);                                            \
     hipError_t trace_fill_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,              \
                                     const ProblemDev &pb, int B, int cap, double *rows,              \
-                                    const int *count);
+                                    const int *count);                                               \
+    hipError_t cost_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                    \
+                              const ProblemDev &pb, int B, const double *Z, double *cost,            \
+                              double *Xend);
 
 // Launch table of an out-of-tree model (include/socp_plugin.h, plugin_impl.hpp): what the C-ABI layer calls
 // instead of the built-in flavour launchers when a context is created with a registered model id.
-constexpr int kPluginAbi = 6;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
-                                   // 6: batched trace launchers
+constexpr int kPluginAbi = 7;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+                                   // 6: batched trace launchers; 7: batched cost launcher
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -80,6 +83,9 @@ struct ModelLaunchers {
     // batched trace (socp_trace_batch): kept rows' t, X, aux and their number; then u and H of the stored rows in place
     hipError_t (*trace)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, int, double *, int *);
     hipError_t (*trace_fill)(hipStream_t, const ModelParams &, const ProblemDev &, int, int, double *, const int *);
+    // batched cost (socp_cost_batch): cost[B][M] and, unless null, Xend[B][M][S]; fixed-step integrator only.  Null: the model has
+    // no running-cost kernel (one with its own ComputeTraj)
+    hipError_t (*cost)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *);
 };
 
 SOCP_DECLARE_LAUNCHERS(exact)
@@ -92,6 +98,8 @@ hipError_t var_jacobian(int model_id, hipStream_t st, const ModelParams &P, cons
 hipError_t var_eval(int model_id, hipStream_t st, const ModelParams &P, int what, int B, const double *t, const double *X, int len,
                     double *out);
 hipError_t fd_diff(hipStream_t st, int n, int np, const double *z, double eps, const double *rows, double *fjac);
+// flavour- and model-independent: total[b] = sum of cost[b][0 .. M), left to right
+hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *total);
 
 SOCP_DECLARE_LAUNCHERS(fast)
 

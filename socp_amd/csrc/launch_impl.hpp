@@ -131,7 +131,42 @@ hipError_t SOCP_CAT(trace_fill_, SOCP_FLAVOUR)(int model_id, hipStream_t st, con
     return hipGetLastError();
 }
 
+// Batched cost: the residual's lane mapping and occupancy rule, the Goddard smooth-law rule of the kernels that read a shooting
+// problem.  A launch macro of its own: only the fixed-step integrator exists for this kernel (capi.cpp refuses the other).
+hipError_t SOCP_CAT(cost_, SOCP_FLAVOUR)(int model_id, hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B,
+                                         const double *Z, double *cost, double *Xend)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0) return hipErrorInvalidValue;
+    const unsigned grid = blocks_for((long)B * pb.M);
+#define SOCP_COST_LAUNCH(MDL, PP)                                                                                                   \
+    switch (wpe_for(grid)) {                                                                                                        \
+    case 1: hipLaunchKernelGGL((cost_lane_kernel<MDL, 1, 0, PP>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, cost, Xend); break;     \
+    case 2: hipLaunchKernelGGL((cost_lane_kernel<MDL, 2, 0, PP>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, cost, Xend); break;     \
+    default: hipLaunchKernelGGL((cost_lane_kernel<MDL, 3, 0, PP>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, cost, Xend); break;    \
+    }
+#define SOCP_COST_MODELS(PP, SMOOTH_OK)                                                  \
+    do {                                                                                 \
+        if (model_id == 1 && (SMOOTH_OK)) { SOCP_COST_LAUNCH(SOCP_GODDARD_SMOOTH, PP) }  \
+        else if (model_id == 1) { SOCP_COST_LAUNCH(SOCP_GODDARD, PP) }                   \
+        else if (model_id == 3) { SOCP_COST_LAUNCH(SOCP_COVID, PP) }                     \
+        else { SOCP_COST_LAUNCH(SOCP_DINT, PP) }                                         \
+    } while (0)
+    if (pb.pp_params || pb.pp_time || pb.pp_xnode) SOCP_COST_MODELS(true, pb.pp_params ? pb.pp_smooth != 0 : P.p[6] > 0);
+    else SOCP_COST_MODELS(false, P.p[6] > 0);
+#undef SOCP_COST_MODELS
+#undef SOCP_COST_LAUNCH
+    return hipGetLastError();
+}
+
 #ifdef SOCP_DEFINE_COMMON
+hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *total)
+{
+    if (B <= 0 || M <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cost_total_kernel, dim3(blocks_for(B)), dim3(64), 0, st, B, M, cost, total);
+    return hipGetLastError();
+}
+
 hipError_t fd_diff(hipStream_t st, int n, int np, const double *z, double eps, const double *rows, double *fjac)
 {
     if (np <= 0) return hipSuccess;

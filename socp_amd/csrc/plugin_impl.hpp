@@ -38,7 +38,7 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
 #include "launch.hpp"
@@ -144,6 +144,30 @@ hipError_t trace_fill(hipStream_t st, const ModelParams &P, const ProblemDev &pb
     return hipGetLastError();
 }
 
+// batched cost: fixed-step integrator only, so no adaptive instantiation (the C-ABI layer refuses the adaptive integrator)
+template <class Mdl>
+hipError_t cost(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *out, double *Xend)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0) return hipErrorInvalidValue;
+    const unsigned grid = blocks_for((long)B * pb.M);
+#define SOCP_PLUGIN_COST(PP, W) hipLaunchKernelGGL((cost_lane_kernel<Mdl, W, 0, PP>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, out, Xend)
+#define SOCP_PLUGIN_COST_T(PP)                                                        \
+    do {                                                                              \
+        if constexpr (one_wave_per_simd<Mdl>::value) SOCP_PLUGIN_COST(PP, 1);         \
+        else switch (wpe_for(grid)) {                                                 \
+        case 1: SOCP_PLUGIN_COST(PP, 1); break;                                       \
+        case 2: SOCP_PLUGIN_COST(PP, 2); break;                                       \
+        default: SOCP_PLUGIN_COST(PP, 3); break;                                      \
+        }                                                                             \
+    } while (0)
+    if (pb.pp_params || pb.pp_time || pb.pp_xnode) SOCP_PLUGIN_COST_T(true);
+    else SOCP_PLUGIN_COST_T(false);
+#undef SOCP_PLUGIN_COST_T
+#undef SOCP_PLUGIN_COST
+    return hipGetLastError();
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -162,6 +186,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     for (double v : defaults) if (i < kMaxParams) t.default_params[i++] = v;
     t.traj = &traj<Mdl>; t.residual = &residual<Mdl>; t.fdjac = &fdjac<Mdl>; t.fdrows = &fdrows<Mdl>;
     t.dense = &dense<Mdl>; t.eval = &eval<Mdl>; t.trace = &trace<Mdl>; t.trace_fill = &trace_fill<Mdl>;
+    if constexpr (!has_custom_traj<Mdl>::value) t.cost = &cost<Mdl>;     // a model with its own ComputeTraj has no cost kernel
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

@@ -292,6 +292,25 @@ def trace_local(ctx, args, local, lo, rank, params=None):
             "wall_s": wall, "file": path}
 
 
+def cost_local(ctx, args, local, lo, rank, params=None):
+    """--cost-out: the integrated running cost (socp_cost_batch) of this rank's CONVERGED chains, each with its own parameter block
+    when the chains have one, written to PATH.rank<r>.npz: cost [k][M] per segment, total [k], index [k] = position of the chain
+    in the sweep's start table, z [k][n] = the unknown vectors costed.  Runs after the timed solve.  Returns the record entry of
+    this rank: what ranks the extremals the sweep found."""
+    conv = np.where(np.asarray(local["info"]) == 1)[0]
+    z = np.asarray(local["z"])[conv]
+    t0 = time.perf_counter()
+    r = ctx.cost_batch(z, params=None if params is None else params[conv])
+    wall = time.perf_counter() - t0
+    path = "%s.rank%d.npz" % (args.cost_out, rank)
+    total = r["total"]
+    np.savez(path, cost=r["cost"], total=total, index=lo + conv, z=z)
+    some = len(conv) > 0
+    return {"chains": int(len(conv)), "min": float(total.min()) if some else None, "median": float(np.median(total)) if some else None,
+            "max": float(total.max()) if some else None, "best_index": int(lo + conv[int(np.argmin(total))]) if some else None,
+            "wall_s": wall, "file": path}
+
+
 def interceptor_sweep(args, torch, dist, capi, world, rank, local_rank, dev, record_fd):
     eps = args.eps if args.eps is not None else 1e-3
     ctx, Z0, _kw = interceptor_config5_sweep(args.starts, variant=args.variant, eps=eps, ode_tol=args.ode_tol, fixed_step=args.fixed_step,
@@ -374,9 +393,16 @@ def main():
                     help="after the timed solve, each rank traces the converged chains of its own block in one batch (socp_trace_batch), with the "
                          "chains' own parameter blocks, and writes PATH.rank<r>.npz (rows, count, index of the chains).  Trajectories are "
                          "NOT gathered across ranks.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--cost-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank integrates the running cost of the converged chains of its own block in one batch "
+                         "(socp_cost_batch), with the chains' own parameter blocks, writes PATH.rank<r>.npz (cost per segment, total, index "
+                         "of the chains, z) and adds cost_rank<r> {chains, min, median, max, best_index, wall_s, file} to the record.  Not "
+                         "with --model interceptor.  Absent: the timed wall and the printed record are unchanged")
     args = ap.parse_args()
     if args.trace_stride < 1:
         ap.error("--trace-stride must be >= 1")
+    if args.cost_out and args.model == "interceptor":
+        ap.error("--cost-out: the interceptor has no running-cost kernel (its chart changes rewrite the costate in mid-trajectory)")
 
     # stdout carries only the JSON record: RCCL prints a version banner to file descriptor 1 when a process group is created
     import sys
@@ -463,6 +489,12 @@ def main():
             blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
             blocks[:, 2] = local["param_final"]
         extra = {"trace_rank%d" % rank: trace_local(ctx, args, local, lo_w, rank, blocks)}
+    if args.cost_out:
+        blocks = None
+        if chain_kw is not None:                        # as for the trace: every chain at the KD it reached
+            blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
+            blocks[:, 2] = local["param_final"]
+        extra["cost_rank%d" % rank] = cost_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
