@@ -295,6 +295,48 @@ int socp_cost_batch(socp_ctx *ctx, int B, const double *Z, double *cost, double 
 int socp_cost_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
                            const double *time, const double *xnode, double *cost, double *total, double *Xend);
 
+/* replaces: shooting::Move(tf) (shooting.cpp:383-437) for a whole batch: the state ON a stored solution at a query time, and the
+ * re-grid the reference's multi-stage flows build from it (testGoddard.cpp:115-145: vX[i] = Move(vt[i]), then InitShooting(vt, vX)
+ * on a new structure).  Z[B][n], tq[B][K] -> Xq[B][K][s]; tout[B][K] (may be NULL) = the time actually reached.
+ * Per row b and query k, with z = Z[b], s = 2 d and tl(j) timeline entry j exactly as the residual forms it (socp_timeline; row
+ * b's own blocks when socp_problem_set_blocks_dev is in force):
+ *   t0 = tl(0), te = tl(M)                                   (:391-405  FIXED: the table's time, FREE: the unknown)
+ *   target = (q >= t0 && q <= te) ? q : te                   (:407-409  out of range and NaN go to te)
+ *   seg = 0; while (seg < M-1 && tl(seg+1) < target) seg++   (:416-424  the bound only makes a NaN / disordered timeline safe)
+ *   X = z[s seg .. s seg + s)                                (:426-431)
+ *   X <- model::ComputeTraj(tl(seg), X, target)              (:433      with the switching times the residual uses for the row)
+ * So a query equal to an interior node time integrates the WHOLE previous segment (it does not copy the node state), q == t0 is a
+ * zero-length integration that returns z[0 .. s) bit for bit, and every query costs one full step_nbr-step (or adaptive)
+ * integration from its segment's start, as in the reference: it is not a sample of a stored trajectory.  The variational state
+ * is not moved (the reference drops isJac here too, :440-444).  All models, both variants, both integrators.
+ * socp_regrid_*: B solutions onto a new structure of M2 segments with time modes mode_t2[M2+1] (HOST array, read before the call
+ * returns) and node times T2[B][M2+1]:
+ *   Z2[b][s j + c]     = Move(T2[b][j])[c]  for j < M2
+ *   Z2[b][s M2 + r]    = T2[b][j_r] AS GIVEN (not clamped), j_r the r-th FREE node in node order   (shooting.cpp:228-243)
+ *   xnode2[b][j][:]    = Move(T2[b][j])     for j = 0 .. M2 (may be NULL): InitShooting(vt, vX)'s data->X, the block
+ *                        socp_problem_set_blocks_dev and socp_chains_solve's x_goal take; the caller's own T2 is the time block
+ * socp_regrid_num_param = n2 = s M2 + #FREE(mode_t2), the row length of Z2.  1 <= M2 <= 255, so that the mode table travels as a
+ * kernel argument and the _dev form neither copies from pageable memory nor synchronises.
+ * SOCP_ERR_ARG: no problem set, B < 0, K < 0, a NULL required pointer with B K > 0, _blocks with params and param_stride !=
+ * nparams + 2, M2 outside 1 .. 255, a mode_t2 entry outside FIXED / FREE / CONTINUOUS; B == 0 or K == 0: SOCP_OK without a launch;
+ * a model whose launch table has no move entry: SOCP_ERR_UNSUPPORTED.  An error leaves the context unchanged.
+ * One launch (re-grid: two -- a move with K = M2 + 1 into d_xnode2, or into a workspace buffer of the context when that is NULL,
+ * then the pack); socp_ctx_counters advances by B K trajectories (re-grid: B (M2 + 1)).  The _dev forms take device pointers and
+ * only enqueue on the context's stream (one exception: socp_regrid_batch_dev with d_xnode2 NULL allocates its grow-only workspace
+ * buffer the first time, and again when B (M2 + 1) outgrows it -- a hipMalloc, which synchronises the device; pass d_xnode2 where
+ * that matters); the host forms stage through that stream and return when the results are in the caller's
+ * arrays.  _blocks: per-row blocks like socp_residual_batch_blocks (any of params / time / xnode may be NULL); the context's own
+ * blocks are restored afterwards. */
+int socp_move_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int K, const double *d_tq, double *d_Xq, double *d_tout);
+int socp_move_batch(socp_ctx *ctx, int B, const double *Z, int K, const double *tq, double *Xq, double *tout);
+int socp_move_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
+                           const double *time, const double *xnode, int K, const double *tq, double *Xq, double *tout);
+int socp_regrid_num_param(const socp_ctx *ctx, int M2, const int *mode_t2);
+int socp_regrid_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int M2, const int *mode_t2, const double *d_T2, double *d_Z2,
+                          double *d_xnode2);
+int socp_regrid_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                             const double *xnode, int M2, const int *mode_t2, const double *T2, double *Z2, double *xnode2);
+
 /* replaces: shooting::ShootingFunctionJacobian (shooting.cpp:996-1130), variational Jacobian
  * for models with modelOrder == 1 (socp_ctx_has_variational); fjac column-major as handed to hybrj (shooting.cpp:889-893).
  * The variational state follows the context's integrator (socp_ctx_set_integrator): fixed-step RK4, or -- as the reference does

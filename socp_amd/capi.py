@@ -135,6 +135,12 @@ def lib():
         L.socp_cost_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_cost_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
         L.socp_cost_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]
+        L.socp_move_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
+        L.socp_move_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]
+        L.socp_move_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp]
+        L.socp_regrid_num_param.argtypes = [_vp, C.c_int, _ip]
+        L.socp_regrid_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _vp, _vp, _vp]
+        L.socp_regrid_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp]
         L.socp_ctx_get_switching_times.argtypes = [_vp, _dp]
         L.socp_chains_solve.argtypes = [_vp, C.c_int, C.POINTER(ChainOptions), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip,
                                         _ip, _dp, _dp, _dp, C.POINTER(ChainStats)]
@@ -226,6 +232,22 @@ def trace_kept_rows(R, stride):
     if kept[-1] != R - 1:
         kept.append(R - 1)
     return kept
+
+
+def move_segment(tl, q):
+    """The selection rule of shooting::Move(tf) (shooting.cpp:407-424) as the batched move applies it: for a timeline tl[0 .. M] and a
+    query time q, returns (seg, target) -- the query clamped to [tl[0], tl[M]] the reference's way (out of range and NaN go to tl[M]) and
+    the segment whose start node the integration tl[seg] -> target starts from.  The definition callers and tests share."""
+    tl = [float(t) for t in tl]
+    M = len(tl) - 1
+    if M < 1:
+        raise ValueError("move_segment: a timeline has at least two entries")
+    q = float(q)
+    target = q if (q >= tl[0] and q <= tl[M]) else tl[M]
+    seg = 0
+    while seg < M - 1 and tl[seg + 1] < target:
+        seg += 1
+    return seg, target
 
 
 def _d(a):
@@ -556,6 +578,64 @@ class Context:
         self._chk(self.L.socp_cost_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
                                                 _d(cost), ptr(tot), ptr(xe)))
         return dict(cost=cost, total=tot, xend=xe)
+
+    # -- batched Move(tf) / re-grid
+    def move_batch_dev(self, B, d_Z, K, d_tq, d_Xq, d_tout=None):
+        """Device pointers (ints; d_tout may be None); enqueue only, no copy, no synchronise (socp_move_batch_dev)."""
+        self._chk(self.L.socp_move_batch_dev(self.h, int(B), _vp(d_Z), int(K), _vp(d_tq), _vp(d_Xq), _vp(d_tout)))
+
+    def move_batch(self, Z, tq, params=None, time=None, xnode=None, tout=False):
+        """shooting::Move(tf) for a whole batch: the state on the stored solution Z[b] at every query time tq[b][k] (move_segment says
+        from which node it is integrated).  Returns Xq[B][K][2d], or (Xq, tout[B][K]) with tout=True: the times actually reached.
+        params / time / xnode: per-row blocks as in residual_batch_blocks."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        tq = _f64(tq)
+        K = tq.size // B if B else (tq.shape[-1] if tq.ndim >= 2 else 0)
+        tq = tq.reshape(B, K)
+        pp = _f64(params).reshape(B, -1) if params is not None else None
+        tt = _f64(time).reshape(B, -1) if time is not None else None
+        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
+        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+        Xq = np.full((B, K, self.s), np.nan)
+        to = np.full((B, K), np.nan) if tout else None
+        self._chk(self.L.socp_move_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
+                                                K, _d(tq), _d(Xq), ptr(to)))
+        return (Xq, to) if tout else Xq
+
+    def regrid_num_param(self, mode_t2):
+        """Number of unknowns of a re-grid's target structure: 2d M2 + #FREE(mode_t2) (socp_regrid_num_param)."""
+        mt = np.ascontiguousarray(mode_t2, dtype=np.int32)
+        n2 = self.L.socp_regrid_num_param(self.h, len(mt) - 1, mt.ctypes.data_as(_ip))
+        if n2 < 0:
+            raise SocpError(n2, "regrid_num_param: 1 <= M2 <= 255 and time modes FIXED / FREE / CONTINUOUS are required")
+        return n2
+
+    def regrid_batch_dev(self, B, d_Z, mode_t2, d_T2, d_Z2, d_xnode2=None):
+        """Device pointers (ints; d_xnode2 may be None), mode_t2 a host sequence; enqueue only (socp_regrid_batch_dev)."""
+        mt = np.ascontiguousarray(mode_t2, dtype=np.int32)
+        self._chk(self.L.socp_regrid_batch_dev(self.h, int(B), _vp(d_Z), len(mt) - 1, mt.ctypes.data_as(_ip), _vp(d_T2), _vp(d_Z2),
+                                               _vp(d_xnode2)))
+
+    def regrid_batch(self, Z, mode_t2, T2, params=None, time=None, xnode=None, want_xnode=True):
+        """B solutions onto a new structure (time modes mode_t2[M2+1], node times T2[B][M2+1]): what testGoddard.cpp:119-145 does with
+        Move + InitShooting(vt, vX).  Returns dict(z[B][n2], time = T2, xnode[B][M2+1][2d] or None): the start vectors of the next
+        stage and the blocks chains_solve takes as time_goal / x_goal.  params / time / xnode: per-row blocks of THIS context's problem."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        mt = np.ascontiguousarray(mode_t2, dtype=np.int32)
+        M2 = len(mt) - 1
+        T2 = np.array(np.broadcast_to(np.asarray(T2, dtype=np.float64), (B, M2 + 1)), order="C")       # the caller's own times: returned as `time`
+        pp = _f64(params).reshape(B, -1) if params is not None else None
+        tt = _f64(time).reshape(B, -1) if time is not None else None
+        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
+        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+        n2 = self.L.socp_regrid_num_param(self.h, M2, mt.ctypes.data_as(_ip))
+        Z2 = np.full((B, max(n2, 0)), np.nan)
+        X2 = np.full((B, M2 + 1, self.s), np.nan) if want_xnode else None
+        self._chk(self.L.socp_regrid_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
+                                                  M2, mt.ctypes.data_as(_ip), _d(T2), _d(Z2), ptr(X2)))
+        return dict(z=Z2, time=T2, xnode=X2)
 
     def chains_solve(self, Z0, kind=CHAIN_PLAIN, param_index=0, step=1.0, step_min=1e-12, goal=None, params=None,
                      time_prev=None, x_prev=None, time_goal=None, x_goal=None, xtol=1e-8, maxfev=10000, epsfcn=1e-15,

@@ -1004,6 +1004,186 @@ int socp_cost_batch_blocks(socp_ctx *c, int B, const double *Z, const double *pa
     return rc;
 }
 
+/* ---- batched Move(tf) / re-grid ------------------------------------------------------------- */
+
+namespace {
+// every refusal comes before anything is counted, reserved or enqueued: an error leaves the context as it was
+int move_args(socp_ctx *c, const char *who, int B, int K)
+{
+    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, std::string(who) + ": no problem set");
+    if (B < 0 || K < 0) return fail(c, SOCP_ERR_ARG, std::string(who) + ": B >= 0 and K >= 0 are required");
+    if (c->vt && !table_of(c)->move)
+        return fail(c, SOCP_ERR_UNSUPPORTED, std::string(who) + ": this model's launch table has no move entry");
+    return SOCP_OK;
+}
+
+hipError_t run_move(socp_ctx *c, int B, const double *d_Z, int K, const double *d_tq, double *d_Xq, double *d_tout)
+{
+    c->n_traj += (long long)B * K; c->n_launch += 1;
+    if (c->vt) return table_of(c)->move(c->stream, c->P, c->pb, B, d_Z, K, d_tq, d_Xq, d_tout);
+    return use_fast(c) ? move_fast(c->model_id, c->stream, c->P, c->pb, B, d_Z, K, d_tq, d_Xq, d_tout)
+                       : move_exact(c->model_id, c->stream, c->P, c->pb, B, d_Z, K, d_tq, d_Xq, d_tout);
+}
+
+// per-row blocks of a _blocks entry point: staged through s_aux and put in force; the caller saves and restores c->pb
+int stage_blocks(socp_ctx *c, int B, const double *params, int pstride, const double *time, const double *xnode)
+{
+    const size_t nodes = (size_t)c->M + 1;
+    const size_t nbP = params ? sizeof(double) * (size_t)B * pstride : 0, nbT = time ? sizeof(double) * B * nodes : 0,
+                 nbX = xnode ? sizeof(double) * B * nodes * c->S : 0;
+    HIP_TRY(c, c->s_aux.reserve(nbP + nbT + nbX + 64));
+    char *base = c->s_aux.as<char>();
+    double *dP = reinterpret_cast<double *>(base), *dT = reinterpret_cast<double *>(base + nbP), *dX = reinterpret_cast<double *>(base + nbP + nbT);
+    if (nbP) HIP_TRY(c, hipMemcpyAsync(dP, params, nbP, hipMemcpyHostToDevice, c->stream));
+    if (nbT) HIP_TRY(c, hipMemcpyAsync(dT, time, nbT, hipMemcpyHostToDevice, c->stream));
+    if (nbX) HIP_TRY(c, hipMemcpyAsync(dX, xnode, nbX, hipMemcpyHostToDevice, c->stream));
+    return socp_problem_set_blocks_dev(c, params ? dP : nullptr, pstride, time ? dT : nullptr, xnode ? dX : nullptr);
+}
+
+// the target structure of a re-grid: n2 = S M2 + #FREE, the FREE-node bit words; SOCP_ERR_ARG for what the entry points refuse
+int regrid_layout(const socp_ctx *c, int M2, const int *mode_t2, unsigned long long (&bits)[4])
+{
+    if (!c || !mode_t2 || M2 < 1 || M2 > 255) return SOCP_ERR_ARG;
+    int n2 = c->S * M2;
+    for (int k = 0; k < 4; k++) bits[k] = 0;
+    for (int j = 0; j <= M2; j++) {
+        if (mode_t2[j] < SOCP_FIXED || mode_t2[j] > SOCP_CONTINUOUS) return SOCP_ERR_ARG;
+        if (mode_t2[j] == SOCP_FREE) { bits[j >> 6] |= 1ull << (j & 63); n2++; }
+    }
+    return n2;
+}
+
+int regrid_args(socp_ctx *c, int B, int M2, const int *mode_t2, unsigned long long (&bits)[4], int *n2)
+{
+    const int rc = move_args(c, "regrid_batch", B, 0);
+    if (rc != SOCP_OK) return rc;
+    if (M2 < 1 || M2 > 255) return fail(c, SOCP_ERR_ARG, "regrid_batch: 1 <= M2 <= 255 is required");
+    if (!mode_t2) return fail(c, SOCP_ERR_ARG, "regrid_batch: null time-mode table");
+    *n2 = regrid_layout(c, M2, mode_t2, bits);
+    if (*n2 < 0) return fail(c, SOCP_ERR_ARG, "regrid_batch: bad time mode in the target structure");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_move_batch_dev(socp_ctx *c, int B, const double *d_Z, int K, const double *d_tq, double *d_Xq, double *d_tout)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc = move_args(c, "move_batch", B, K);
+    if (rc != SOCP_OK) return rc;
+    if (B == 0 || K == 0) return SOCP_OK;
+    if (!d_Z || !d_tq || !d_Xq) return fail(c, SOCP_ERR_ARG, "move_batch: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, run_move(c, B, d_Z, K, d_tq, d_Xq, d_tout));
+    return SOCP_OK;
+}
+
+int socp_move_batch(socp_ctx *c, int B, const double *Z, int K, const double *tq, double *Xq, double *tout)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = move_args(c, "move_batch", B, K);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B == 0 || K == 0) return SOCP_OK;
+    if (!Z || !tq || !Xq) return fail(c, SOCP_ERR_ARG, "move_batch: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t lanes = (size_t)B * K;
+    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbQ = sizeof(double) * lanes, nbX = sizeof(double) * lanes * c->S;
+    HIP_TRY(c, c->s_in.reserve(nbZ));
+    HIP_TRY(c, c->s_t0.reserve(nbQ));
+    HIP_TRY(c, c->s_out.reserve(nbX + nbQ));
+    double *dX = c->s_out.as<double>(), *dT = dX + lanes * c->S;
+    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nbZ, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->s_t0.p, tq, nbQ, hipMemcpyHostToDevice, c->stream));
+    const int rc = socp_move_batch_dev(c, B, c->s_in.as<double>(), K, c->s_t0.as<double>(), dX, tout ? dT : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(Xq, dX, nbX, hipMemcpyDeviceToHost, c->stream));
+    if (tout) HIP_TRY(c, hipMemcpyAsync(tout, dT, nbQ, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_move_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                           const double *xnode, int K, const double *tq, double *Xq, double *tout)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = move_args(c, "move_batch_blocks", B, K);
+    if (rc0 != SOCP_OK) return rc0;
+    // before anything is sized or copied from it: a wrong stride would read past the caller's array
+    if (params && pstride != c->nparams + 2)
+        return fail(c, SOCP_ERR_ARG, "move_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    if (B == 0 || K == 0) return SOCP_OK;
+    if (!Z || !tq || !Xq) return fail(c, SOCP_ERR_ARG, "move_batch_blocks: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const ProblemDev saved = c->pb;
+    int rc = stage_blocks(c, B, params, pstride, time, xnode);
+    if (rc == SOCP_OK) rc = socp_move_batch(c, B, Z, K, tq, Xq, tout);
+    c->pb = saved;
+    return rc;
+}
+
+int socp_regrid_num_param(const socp_ctx *c, int M2, const int *mode_t2)
+{
+    unsigned long long bits[4];
+    return regrid_layout(c, M2, mode_t2, bits);
+}
+
+int socp_regrid_batch_dev(socp_ctx *c, int B, const double *d_Z, int M2, const int *mode_t2, const double *d_T2, double *d_Z2,
+                          double *d_xnode2)
+{
+    if (!c) return SOCP_ERR_ARG;
+    unsigned long long bits[4];
+    int n2 = 0;
+    const int rc = regrid_args(c, B, M2, mode_t2, bits, &n2);
+    if (rc != SOCP_OK) return rc;
+    if (B == 0) return SOCP_OK;
+    if (!d_Z || !d_T2 || !d_Z2) return fail(c, SOCP_ERR_ARG, "regrid_batch: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // launch 1: Move(T2[b][j]) for every node of the target, into the caller's xnode2 or a workspace buffer of the context
+    // (grow-only: the first use and every growth is a hipMalloc, which synchronises the device -- the header says so)
+    double *d_Xm = d_xnode2;
+    if (!d_Xm) {
+        HIP_TRY(c, c->s_var.reserve(sizeof(double) * (size_t)B * (M2 + 1) * c->S));
+        d_Xm = c->s_var.as<double>();
+    }
+    HIP_TRY(c, run_move(c, B, d_Z, M2 + 1, d_T2, d_Xm, nullptr));
+    // launch 2: the unknown vectors of the target structure
+    c->n_launch += 1;
+    HIP_TRY(c, regrid_pack(c->stream, B, c->S, M2, n2, bits, d_Xm, d_T2, d_Z2));
+    return SOCP_OK;
+}
+
+int socp_regrid_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                             const double *xnode, int M2, const int *mode_t2, const double *T2, double *Z2, double *xnode2)
+{
+    if (!c) return SOCP_ERR_ARG;
+    unsigned long long bits[4];
+    int n2 = 0;
+    const int rc0 = regrid_args(c, B, M2, mode_t2, bits, &n2);
+    if (rc0 != SOCP_OK) return rc0;
+    if (params && pstride != c->nparams + 2)
+        return fail(c, SOCP_ERR_ARG, "regrid_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    if (B == 0) return SOCP_OK;
+    if (!Z || !T2 || !Z2) return fail(c, SOCP_ERR_ARG, "regrid_batch_blocks: null argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nodes2 = (size_t)M2 + 1;
+    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbT = sizeof(double) * B * nodes2, nbZ2 = sizeof(double) * (size_t)B * n2,
+                 nbX = sizeof(double) * B * nodes2 * c->S;
+    HIP_TRY(c, c->s_in.reserve(nbZ));
+    HIP_TRY(c, c->s_t0.reserve(nbT));
+    HIP_TRY(c, c->s_out.reserve(nbZ2 + nbX));
+    double *dZ2 = c->s_out.as<double>(), *dX = dZ2 + (size_t)B * n2;
+    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nbZ, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->s_t0.p, T2, nbT, hipMemcpyHostToDevice, c->stream));
+    const ProblemDev saved = c->pb;
+    int rc = stage_blocks(c, B, params, pstride, time, xnode);
+    if (rc == SOCP_OK) rc = socp_regrid_batch_dev(c, B, c->s_in.as<double>(), M2, mode_t2, c->s_t0.as<double>(), dZ2, xnode2 ? dX : nullptr);
+    c->pb = saved;
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(Z2, dZ2, nbZ2, hipMemcpyDeviceToHost, c->stream));
+    if (xnode2) HIP_TRY(c, hipMemcpyAsync(xnode2, dX, nbX, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
 int socp_fd_jacobian_multi_dev(socp_ctx *c, int np, const double *d_Z, const double *d_Fvec, double epsfcn,
                                double *d_Fjac, int dedup)
 {

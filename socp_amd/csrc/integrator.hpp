@@ -930,4 +930,90 @@ __global__ __launch_bounds__(64) void cost_total_kernel(int B, int M, const doub
 }
 #endif
 
+// ---------------------------------------------------------------------------------------------
+// K_move: shooting::Move(tf) (shooting.cpp:383-437) for a whole batch -- the state ON the stored solution z at a query time.
+// Z[B][n], tq[B][K] -> Xq[B][K][S], optionally tout[B][K] (the time actually reached).  One lane = (row, query), T = b K + k.
+// The lane forms the timeline with the shared prologue (Timeline: row b's own blocks under PERPROB), clamps the query to
+// [tl(0), tl(M)] the way the reference does (:407-409: out of range -- and NaN, every comparison false -- goes to tl(M)),
+// walks to the segment whose end is the first at or past the target (:416-424; the bound seg < M-1 is never reached by a finite
+// ordered timeline, it keeps a NaN or disordered one inside row b), starts from THAT node's state z[S seg .. S seg + S) and
+// integrates tl(seg) -> target with integrate_with: the model's ComputeTraj, a full step_nbr-step (or adaptive) integration
+// whatever the distance.  So a query equal to an interior node time integrates the whole previous segment, and q == tl(0) is
+// a zero-length integration that returns z[0 .. S) bit for bit.  isJac is dropped as in the reference (:440-444).
+// Fixed-step lanes of a wave all take step_nbr steps whatever their segment: the search adds no divergence to the loop.
+// A lane's row is S consecutive doubles and consecutive lanes own adjacent rows (direct stores, like K_trace: a wave writes one
+// contiguous 64 S 8-byte span); every store site is ONE block under ONE computed predicate (see the note in segment_residual).
+// ---------------------------------------------------------------------------------------------
+template <class Mdl, int INTEG, class ZRead>
+__device__ __forceinline__ void segment_move(const ModelParams &P, const ProblemDev &pb, const ZRead &z, double q,
+                                             double *__restrict__ xq, double *__restrict__ tout)
+{
+    constexpr int S = Mdl::S;
+    const int M = pb.M;
+    const Timeline<ZRead> tl{pb, z};
+    const double t0 = tl.nt(0), te = tl.nt(M);
+    const double target = (q >= t0 && q <= te) ? q : te;
+    int seg = 0;
+    while (seg < M - 1 && tl.nt(seg + 1) < target) seg++;
+    const double t1 = tl.nt(seg);
+    double sw0 = tl.template switching_time<Mdl>(P.sw0, pb.sw_node0), sw1 = tl.template switching_time<Mdl>(P.sw1, pb.sw_node1);
+    double X[S];
+    segment_start(z, S * seg, X);
+    Lane<Mdl>::template integrate_with<INTEG>(P, sw0, sw1, t1, target, X);     // shooting.cpp:433 Move(t1, X1, t_f)
+#pragma unroll
+    for (int k = 0; k < S; k++) xq[k] = X[k];
+    const bool st = tout != nullptr;
+    if (st) *tout = target;
+}
+
+template <class Mdl, int WPE, int INTEG = 0, bool PERPROB = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) void move_lane_kernel(ModelParams P, ProblemDev pb, int B,
+                                                          const double *__restrict__ Z, int K, const double *__restrict__ tq,
+                                                          double *__restrict__ Xq, double *__restrict__ tout)
+{
+    const long T = (long)blockIdx.x * 64 + threadIdx.x;              // = b * K + k: index into tq and tout, row of Xq
+    if (T >= (long)B * K) return;
+    const long b = T / K;
+    const double *zr = Z + b * pb.n;
+    auto z = [=](int k) -> double { return zr[k]; };
+    double *to = tout ? tout + T : nullptr;
+    if constexpr (PERPROB) {
+        ModelParams Pq = P;
+        ProblemDev pq = pb;
+        load_problem_block(pb, b, Pq, pq);
+        segment_move<Mdl, INTEG>(Pq, pq, z, tq[T], Xq + T * Mdl::S, to);
+    } else {
+        segment_move<Mdl, INTEG>(P, pb, z, tq[T], Xq + T * Mdl::S, to);
+    }
+}
+
+#ifdef SOCP_DEFINE_COMMON
+// FREE nodes of a re-grid's target structure, bit j of word j / 64 = node j is FREE: a kernel argument, so the host's mode table is
+// read before socp_regrid_batch_dev returns and nothing is copied from pageable memory (M2 <= 255 -> 256 bits).
+struct RegridFree {
+    unsigned long long w[4];
+};
+
+// K_regrid_pack: the unknown vector of the target structure from the moved node states (shooting.cpp:228-243, the layout of
+// InitShooting(vt, vX)):  Z2[b][S j + c] = Xm[b][j][c] for j < M2, then the FREE node times T2[b][j_r] AS GIVEN (not clamped),
+// r-th FREE node in node order.  One lane per entry of Z2, consecutive lanes on consecutive doubles; one store under one predicate.
+__global__ __launch_bounds__(64) void regrid_pack_kernel(int B, int S, int M2, int n2, RegridFree fr, const double *__restrict__ Xm,
+                                                         const double *__restrict__ T2, double *__restrict__ Z2)
+{
+    const long T = (long)blockIdx.x * 64 + threadIdx.x;              // = b * n2 + e
+    if (T >= (long)B * n2) return;
+    const long b = T / n2;
+    const int e = (int)(T - b * n2);
+    const int r = e - S * M2;                                        // >= 0: the r-th FREE node's time
+    int node = 0;
+    for (int j = 0, seen = 0; j <= M2; j++) {
+        const bool is_free = (fr.w[j >> 6] >> (j & 63)) & 1ull;
+        node = (is_free && seen == r) ? j : node;
+        seen += is_free ? 1 : 0;
+    }
+    const double *src = r < 0 ? Xm + b * (long)(M2 + 1) * S + e : T2 + b * (long)(M2 + 1) + node;
+    Z2[T] = *src;
+}
+#endif
+
 }  // namespace socp

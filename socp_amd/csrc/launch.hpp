@@ -61,12 +61,15 @@ inline int rows_per_block(int M, int n)
                                     const int *count);                                               \
     hipError_t cost_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                    \
                               const ProblemDev &pb, int B, const double *Z, double *cost,            \
-                              double *Xend);
+                              double *Xend);                                                         \
+    hipError_t move_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                    \
+                              const ProblemDev &pb, int B, const double *Z, int K, const double *tq, \
+                              double *Xq, double *tout);
 
 // Launch table of an out-of-tree model (include/socp_plugin.h, plugin_impl.hpp): what the C-ABI layer calls
 // instead of the built-in flavour launchers when a context is created with a registered model id.
-constexpr int kPluginAbi = 7;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
-                                   // 6: batched trace launchers; 7: batched cost launcher
+constexpr int kPluginAbi = 8;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+                                   // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -86,6 +89,8 @@ struct ModelLaunchers {
     // batched cost (socp_cost_batch): cost[B][M] and, unless null, Xend[B][M][S]; fixed-step integrator only.  Null: the model has
     // no running-cost kernel (one with its own ComputeTraj)
     hipError_t (*cost)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *);
+    // batched Move(tf) (socp_move_batch): Z[B][n], tq[B][K] -> Xq[B][K][S] and, unless null, tout[B][K]; both integrators
+    hipError_t (*move)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, const double *, double *, double *);
 };
 
 SOCP_DECLARE_LAUNCHERS(exact)
@@ -100,6 +105,10 @@ hipError_t var_eval(int model_id, hipStream_t st, const ModelParams &P, int what
 hipError_t fd_diff(hipStream_t st, int n, int np, const double *z, double eps, const double *rows, double *fjac);
 // flavour- and model-independent: total[b] = sum of cost[b][0 .. M), left to right
 hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *total);
+// flavour- and model-independent: the unknown vectors Z2[B][n2] of a re-grid's target structure from the moved node states
+// Xm[B][M2+1][S] and the target times T2[B][M2+1]; free_bits: bit j of word j / 64 = node j of the target is FREE (M2 <= 255)
+hipError_t regrid_pack(hipStream_t st, int B, int S, int M2, int n2, const unsigned long long (&free_bits)[4], const double *Xm,
+                       const double *T2, double *Z2);
 
 SOCP_DECLARE_LAUNCHERS(fast)
 

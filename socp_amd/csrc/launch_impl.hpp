@@ -159,7 +159,27 @@ hipError_t SOCP_CAT(cost_, SOCP_FLAVOUR)(int model_id, hipStream_t st, const Mod
     return hipGetLastError();
 }
 
+// Batched Move(tf): one lane per (row, query); the trace's launch shape -- wpe_for(grid), one wave per SIMD under the adaptive
+// integrator, the Goddard smooth-law rule of the kernels that read a shooting problem.
+hipError_t SOCP_CAT(move_, SOCP_FLAVOUR)(int model_id, hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B,
+                                         const double *Z, int K, const double *tq, double *Xq, double *tout)
+{
+    if (B <= 0 || K <= 0) return hipSuccess;
+    SOCP_DISPATCH_PB(move_lane_kernel, blocks_for((long)B * K), st, P, pb, B, Z, K, tq, Xq, tout);
+    return hipGetLastError();
+}
+
 #ifdef SOCP_DEFINE_COMMON
+hipError_t regrid_pack(hipStream_t st, int B, int S, int M2, int n2, const unsigned long long (&free_bits)[4], const double *Xm,
+                       const double *T2, double *Z2)
+{
+    if (B <= 0 || n2 <= 0) return hipSuccess;
+    RegridFree fr;
+    for (int k = 0; k < 4; k++) fr.w[k] = free_bits[k];
+    hipLaunchKernelGGL(regrid_pack_kernel, dim3(blocks_for((long)B * n2)), dim3(64), 0, st, B, S, M2, n2, fr, Xm, T2, Z2);
+    return hipGetLastError();
+}
+
 hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *total)
 {
     if (B <= 0 || M <= 0) return hipSuccess;

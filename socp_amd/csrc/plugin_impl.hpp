@@ -38,7 +38,7 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, batched cost, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
 #include "launch.hpp"
@@ -168,6 +168,16 @@ hipError_t cost(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int 
     return hipGetLastError();
 }
 
+// batched Move(tf): one lane per (row, query), both integrators
+template <class Mdl>
+hipError_t move(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int K, const double *tq, double *Xq,
+                double *tout)
+{
+    if (B <= 0 || K <= 0) return hipSuccess;
+    SOCP_PLUGIN_LAUNCH_PB(move_lane_kernel, blocks_for((long)B * K), st, P, pb, B, Z, K, tq, Xq, tout);
+    return hipGetLastError();
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -186,6 +196,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     for (double v : defaults) if (i < kMaxParams) t.default_params[i++] = v;
     t.traj = &traj<Mdl>; t.residual = &residual<Mdl>; t.fdjac = &fdjac<Mdl>; t.fdrows = &fdrows<Mdl>;
     t.dense = &dense<Mdl>; t.eval = &eval<Mdl>; t.trace = &trace<Mdl>; t.trace_fill = &trace_fill<Mdl>;
+    t.move = &move<Mdl>;
     if constexpr (!has_custom_traj<Mdl>::value) t.cost = &cost<Mdl>;     // a model with its own ComputeTraj has no cost kernel
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;

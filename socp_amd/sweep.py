@@ -311,6 +311,35 @@ def cost_local(ctx, args, local, lo, rank, params=None):
             "wall_s": wall, "file": path}
 
 
+def regrid_structure(args):
+    """--regrid-segments: time modes of the target structure -- goddard_multiple_shooting_problem(M2)'s (free final time) for a
+    multiple-shooting sweep, FIXED end times for single shooting (whose final time is fixed)."""
+    from . import capi
+    M2 = args.regrid_segments
+    return [capi.FIXED] + [capi.CONTINUOUS] * (M2 - 1) + [capi.FIXED if args.segments == 1 else capi.FREE]
+
+
+def regrid_local(ctx, args, local, lo, rank, params=None):
+    """--regrid-out: this rank's CONVERGED chains moved onto --regrid-segments uniform segments between each chain's own first and
+    last timeline entry (socp_regrid_batch: Move(tf) of every new node time on the stored solution, each chain with its own parameter
+    block when the chains have one), written to PATH.rank<r>.npz: z [k][n2] = the unknown vectors of the new structure, time [k][M2+1]
+    and xnode [k][M2+1][14] = its boundary blocks, index [k] = position of the chain in the sweep's start table, source [k][n] = the
+    solutions moved.  Runs after the timed solve.  Returns the record entry of this rank."""
+    conv = np.where(np.asarray(local["info"]) == 1)[0]
+    z = np.asarray(local["z"])[conv]
+    M2 = args.regrid_segments
+    T2 = np.empty((len(conv), M2 + 1))
+    for k, zk in enumerate(z):
+        tl = ctx.timeline(zk)
+        T2[k] = np.linspace(tl[0], tl[-1], M2 + 1)
+    t0 = time.perf_counter()
+    r = ctx.regrid_batch(z, regrid_structure(args), T2, params=None if params is None else params[conv])
+    seconds = time.perf_counter() - t0
+    path = "%s.rank%d.npz" % (args.regrid_out, rank)
+    np.savez(path, index=lo + conv, z=r["z"], time=r["time"], xnode=r["xnode"], source=z)
+    return {"count": int(len(conv)), "n2": int(r["z"].shape[1]), "seconds": seconds}
+
+
 def interceptor_sweep(args, torch, dist, capi, world, rank, local_rank, dev, record_fd):
     eps = args.eps if args.eps is not None else 1e-3
     ctx, Z0, _kw = interceptor_config5_sweep(args.starts, variant=args.variant, eps=eps, ode_tol=args.ode_tol, fixed_step=args.fixed_step,
@@ -398,7 +427,19 @@ def main():
                          "(socp_cost_batch), with the chains' own parameter blocks, writes PATH.rank<r>.npz (cost per segment, total, index "
                          "of the chains, z) and adds cost_rank<r> {chains, min, median, max, best_index, wall_s, file} to the record.  Not "
                          "with --model interceptor.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--regrid-segments", type=int, default=0, metavar="M2",
+                    help="with --regrid-out: the number of uniform segments the converged chains are moved onto")
+    ap.add_argument("--regrid-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank moves the converged chains of its own block onto M2 uniform segments between each "
+                         "chain's own first and last node time in one batch (socp_regrid_batch: Move(tf) at every new node, the chains' own "
+                         "parameter blocks; the structure of the M2-segment testGoddard layout, FIXED end times for --segments 1), writes "
+                         "PATH.rank<r>.npz (index, z, time, xnode, source) and adds regrid_rank<r> {count, n2, seconds} to the record.  Not "
+                         "with --model interceptor.  Absent: the timed wall and the printed record are unchanged")
     args = ap.parse_args()
+    if bool(args.regrid_out) != (args.regrid_segments > 0) or not 0 <= args.regrid_segments <= 255:
+        ap.error("--regrid-segments M2 (1 .. 255) and --regrid-out PATH go together")
+    if args.regrid_out and args.model == "interceptor":
+        ap.error("--regrid-out is implemented for the Goddard sweeps")
     if args.trace_stride < 1:
         ap.error("--trace-stride must be >= 1")
     if args.cost_out and args.model == "interceptor":
@@ -495,6 +536,12 @@ def main():
             blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
             blocks[:, 2] = local["param_final"]
         extra["cost_rank%d" % rank] = cost_local(ctx, args, local, lo_w, rank, blocks)
+    if args.regrid_out:
+        blocks = None
+        if chain_kw is not None:                        # as for the trace: every chain at the KD it reached
+            blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
+            blocks[:, 2] = local["param_final"]
+        extra["regrid_rank%d" % rank] = regrid_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
