@@ -49,7 +49,7 @@ struct DevBuf {
 
 struct socp_ctx {
     int model_id = 0;
-    const ModelLaunchers *vt = nullptr;   // table-driven model (out-of-tree plugin, or in-tree interceptor): its launch table
+    const ModelLaunchers *vt = nullptr;   // the model's launch table (in-tree model or out-of-tree plugin), reference operation order
     const ModelLaunchers *vt_fast = nullptr;   // the same model's throughput flavour, when it has one
     int device = 0;
     int dim = 0, S = 0, nu = 3;
@@ -115,14 +115,8 @@ int hip_fail(socp_ctx *c, hipError_t e, const char *what)
         if (e__ != hipSuccess) return hip_fail((c), e__, #call);         \
     } while (0)
 
-bool use_fast(const socp_ctx *c)
-{
-    // AUTO keeps the reference operation order: it is the variant every parity claim is made on.
-    return c->variant == SOCP_VARIANT_LANE_FAST;
-}
-
-// launch table of a table-driven model for the current variant / integrator
-// (a table carries its own adaptive-integrator instantiations, so the throughput table serves both integrators)
+// launch table for the current variant.  AUTO keeps the reference operation order: it is the variant every parity claim is made
+// on.  (A table carries its own adaptive-integrator instantiations, so the throughput table serves both integrators.)
 const ModelLaunchers *table_of(const socp_ctx *c)
 {
     return (c->variant == SOCP_VARIANT_LANE_FAST && c->vt_fast) ? c->vt_fast : c->vt;
@@ -132,41 +126,30 @@ hipError_t run_traj(socp_ctx *c, int B, const double *t0, const double *tf, cons
                     const double *X0, double *Xf)
 {
     c->n_traj += B; c->n_launch += 1;
-    if (c->vt) return table_of(c)->traj(c->stream, c->P, B, t0, tf, sw, X0, Xf);
-    return use_fast(c) ? traj_fast(c->model_id, c->stream, c->P, B, t0, tf, sw, X0, Xf)
-                       : traj_exact(c->model_id, c->stream, c->P, B, t0, tf, sw, X0, Xf);
+    return table_of(c)->traj(c->stream, c->P, B, t0, tf, sw, X0, Xf);
 }
 
 hipError_t run_residual(socp_ctx *c, int B, const double *Z, double *F)
 {
     c->n_traj += (long long)B * c->M; c->n_launch += 1;
-    if (c->vt) return table_of(c)->residual(c->stream, c->P, c->pb, B, Z, F);
-    return use_fast(c) ? residual_fast(c->model_id, c->stream, c->P, c->pb, B, Z, F)
-                       : residual_exact(c->model_id, c->stream, c->P, c->pb, B, Z, F);
+    return table_of(c)->residual(c->stream, c->P, c->pb, B, Z, F);
 }
 
 hipError_t run_fdjac(socp_ctx *c, int np, int T, const int2 *pairs, const double *z, const double *fvec,
                      double eps, double *fjac)
 {
     c->n_traj += (long long)np * T; c->n_launch += 1;
-    if (c->vt) return table_of(c)->fdjac(c->stream, c->P, c->pb, np, T, pairs, z, fvec, eps, fjac);
-    return use_fast(c) ? fdjac_fast(c->model_id, c->stream, c->P, c->pb, np, T, pairs, z, fvec, eps, fjac)
-                       : fdjac_exact(c->model_id, c->stream, c->P, c->pb, np, T, pairs, z, fvec, eps, fjac);
+    return table_of(c)->fdjac(c->stream, c->P, c->pb, np, T, pairs, z, fvec, eps, fjac);
 }
 
 hipError_t run_fdrows(socp_ctx *c, int np, const double *z, double eps, double *rows)
 {
     c->n_traj += (long long)np * (c->n + 1) * c->M; c->n_launch += 1;
-    if (c->vt) return table_of(c)->fdrows(c->stream, c->P, c->pb, np, z, eps, rows);
-    return use_fast(c) ? fdrows_fast(c->model_id, c->stream, c->P, c->pb, np, z, eps, rows)
-                       : fdrows_exact(c->model_id, c->stream, c->P, c->pb, np, z, eps, rows);
+    return table_of(c)->fdrows(c->stream, c->P, c->pb, np, z, eps, rows);
 }
 
-// variational equations on the device: the in-tree double integrator, or a table-driven model whose table carries them
-bool has_var(const socp_ctx *c)
-{
-    return c->vt ? (c->vt->var_traj && c->vt->var_jacobian && c->vt->var_eval) : c->model_id == SOCP_MODEL_DOUBLE_INTEGRATOR;
-}
+// variational equations on the device: a model whose table carries them (in-tree: the double integrator); always reference order
+bool has_var(const socp_ctx *c) { return c->vt->var_traj && c->vt->var_jacobian && c->vt->var_eval; }
 
 double fd_eps(double epsfcn) { return std::sqrt(epsfcn > DBL_EPSILON ? epsfcn : DBL_EPSILON); }
 
@@ -186,9 +169,11 @@ int socp_ctx_create(socp_ctx **out, int model_id, int device)
         auto it = plugins().find(model_id);
         if (it != plugins().end()) vt = &it->second;
     }
-    if (model_id == SOCP_MODEL_INTERCEPTOR) vt = interceptor_launchers();   // in-tree, table-driven (kernels_interceptor.hip)
-    if (model_id == SOCP_MODEL_VTOLUAV) vt = vtol_launchers();              // in-tree, table-driven (kernels_vtol.hip)
-    if (!vt && model_id != SOCP_MODEL_GODDARD && model_id != SOCP_MODEL_DOUBLE_INTEGRATOR && model_id != SOCP_MODEL_COVID19)
+    // in-tree models: kernels_interceptor.hip, kernels_vtol.hip, kernels_exact.hip
+    if (model_id == SOCP_MODEL_INTERCEPTOR) vt = interceptor_launchers();
+    else if (model_id == SOCP_MODEL_VTOLUAV) vt = vtol_launchers();
+    else if (!vt) vt = builtin_launchers(model_id);                         // null for an id that is not theirs
+    if (!vt)
         return fail(nullptr, SOCP_ERR_UNSUPPORTED, "socp_ctx_create: unknown model id (no device dynamics; plugins: socp_plugin_load)");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -204,32 +189,16 @@ int socp_ctx_create(socp_ctx **out, int model_id, int device)
     c->model_id = model_id;
     c->vt = vt;
     if (model_id == SOCP_MODEL_INTERCEPTOR) c->vt_fast = interceptor_launchers_fast();
-    if (model_id == SOCP_MODEL_VTOLUAV) c->vt_fast = vtol_launchers_fast();
+    else if (model_id == SOCP_MODEL_VTOLUAV) c->vt_fast = vtol_launchers_fast();
+    else c->vt_fast = builtin_launchers_fast(model_id);
     c->device = device;
-    if (vt) {
-        c->dim = vt->dim; c->nparams = vt->nparams; c->nu = vt->control_dim;
-        std::memcpy(c->P.p, vt->default_params, sizeof(double) * kMaxParams);
-        c->P.sw0 = c->P.sw1 = 0.0; c->P.step_nbr = vt->default_step_nbr;
-        // interceptor: the auxiliary scalars are (stageMode, currentChart); a fresh object has (0, 1) (interceptor.cpp:62-64)
-        if (model_id == SOCP_MODEL_INTERCEPTOR) c->P.sw1 = 1.0;
-    } else if (model_id == SOCP_MODEL_GODDARD) {
-        // goddard.cpp:23-40 defaults
-        c->dim = 7; c->nparams = SOCP_GODDARD_NPARAMS;
-        const double d[8] = {3.5, 7.0, 310.0, 500.0, 1.0, 1.0, 0.0, -1.0};
-        std::memcpy(c->P.p, d, sizeof(d));
-        c->P.sw0 = 0.0227; c->P.sw1 = 0.08; c->P.step_nbr = 10;
-    } else if (model_id == SOCP_MODEL_COVID19) {
-        // covid19.cpp:25-38 defaults; its ModelInt integrates with its own stepNbr = 1000
-        c->dim = 4; c->nparams = SOCP_COVID_NPARAMS; c->nu = 1;
-        const double d[8] = {4, 10, 5, 1, 0.1, 1, -10, 20};
-        std::memcpy(c->P.p, d, sizeof(d));
-        c->P.sw0 = c->P.sw1 = 0.0; c->P.step_nbr = 1000;
-    } else {
-        // doubleIntegrator.cpp:26-34 defaults
-        c->dim = 6; c->nparams = SOCP_DINT_NPARAMS;
-        c->P.p[0] = 1.0; c->P.p[1] = 1.0; c->P.p[2] = 0.01;
-        c->P.sw0 = c->P.sw1 = 0.0; c->P.step_nbr = 30;
-    }
+    c->dim = vt->dim; c->nparams = vt->nparams; c->nu = vt->control_dim;
+    std::memcpy(c->P.p, vt->default_params, sizeof(double) * kMaxParams);
+    c->P.sw0 = c->P.sw1 = 0.0; c->P.step_nbr = vt->default_step_nbr;
+    // the table has no slot for the auxiliary scalars.  Interceptor: they are (stageMode, currentChart), and a fresh object has
+    // (0, 1) (interceptor.cpp:62-64); Goddard: the switching times of goddard.cpp:23-40
+    if (model_id == SOCP_MODEL_INTERCEPTOR) c->P.sw1 = 1.0;
+    if (model_id == SOCP_MODEL_GODDARD) { c->P.sw0 = 0.0227; c->P.sw1 = 0.08; }
     c->S = 2 * c->dim;
     // default arithmetic flavour can be chosen from the environment (host programs that do not call
     // socp_ctx_set_variant): SOCP_VARIANT=exact|fast
@@ -495,8 +464,7 @@ int socp_integrate_batch_dev(socp_ctx *c, int B, const double *d_t0, const doubl
             return fail(c, SOCP_ERR_UNSUPPORTED, "integrate_batch: this model has no variational equations (modelOrder 0)");
         if (d_Xf == d_X0) return fail(c, SOCP_ERR_ARG, "integrate_batch: is_jac=1 needs distinct input and output");
         c->n_traj += B; c->n_launch += 1;
-        HIP_TRY(c, c->vt ? c->vt->var_traj(c->stream, c->P, B, d_t0, d_tf, d_X0, d_Xf)
-                         : var_traj(c->model_id, c->stream, c->P, B, d_t0, d_tf, d_X0, d_Xf));
+        HIP_TRY(c, c->vt->var_traj(c->stream, c->P, B, d_t0, d_tf, d_X0, d_Xf));
         return SOCP_OK;
     }
     HIP_TRY(c, run_traj(c, B, d_t0, d_tf, d_sw, d_X0, d_Xf));
@@ -555,11 +523,7 @@ int socp_integrate_dense_aux(socp_ctx *c, double t0, double tf, const double *sw
     HIP_TRY(c, hipMemcpyAsync(c->s_in.p, X0, sizeof(double) * S, hipMemcpyHostToDevice, c->stream));
     const double s0 = sw ? sw[0] : c->P.sw0, s1 = sw ? sw[1] : c->P.sw1;
     c->n_traj += 1; c->n_launch += 1;
-    hipError_t e = c->vt
-        ? table_of(c)->dense(c->stream, c->P, t0, tf, s0, s1, c->s_in.as<double>(), c->s_out.as<double>(), c->s_t0.as<double>(), cap, c->s_aux.as<int>(), d_aux)
-        : use_fast(c)
-        ? dense_fast(c->model_id, c->stream, c->P, t0, tf, s0, s1, c->s_in.as<double>(), c->s_out.as<double>(), c->s_t0.as<double>(), cap, c->s_aux.as<int>(), d_aux)
-        : dense_exact(c->model_id, c->stream, c->P, t0, tf, s0, s1, c->s_in.as<double>(), c->s_out.as<double>(), c->s_t0.as<double>(), cap, c->s_aux.as<int>(), d_aux);
+    hipError_t e = table_of(c)->dense(c->stream, c->P, t0, tf, s0, s1, c->s_in.as<double>(), c->s_out.as<double>(), c->s_t0.as<double>(), cap, c->s_aux.as<int>(), d_aux);
     HIP_TRY(c, e);
     HIP_TRY(c, hipMemcpyAsync(rows, c->s_aux.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -603,13 +567,8 @@ int socp_eval_batch(socp_ctx *c, int what, int B, const double *t, const double 
     }
     c->n_launch += 1;
     hipError_t e = var
-        ? (c->vt ? c->vt->var_eval(c->stream, c->P, what == SOCP_EVAL_RHS ? 0 : 1, B, c->s_t0.as<double>(), c->s_in.as<double>(), len, c->s_out.as<double>())
-                 : var_eval(c->model_id, c->stream, c->P, what == SOCP_EVAL_RHS ? 0 : 1, B, c->s_t0.as<double>(), c->s_in.as<double>(), len, c->s_out.as<double>()))
-        : c->vt
-        ? table_of(c)->eval(c->stream, c->P, what, B, c->s_t0.as<double>(), dsw, c->s_in.as<double>(), c->s_out.as<double>())
-        : use_fast(c)
-        ? eval_fast(c->model_id, c->stream, c->P, what, B, c->s_t0.as<double>(), dsw, c->s_in.as<double>(), c->s_out.as<double>())
-        : eval_exact(c->model_id, c->stream, c->P, what, B, c->s_t0.as<double>(), dsw, c->s_in.as<double>(), c->s_out.as<double>());
+        ? c->vt->var_eval(c->stream, c->P, what == SOCP_EVAL_RHS ? 0 : 1, B, c->s_t0.as<double>(), c->s_in.as<double>(), len, c->s_out.as<double>())
+        : table_of(c)->eval(c->stream, c->P, what, B, c->s_t0.as<double>(), dsw, c->s_in.as<double>(), c->s_out.as<double>());
     HIP_TRY(c, e);
     HIP_TRY(c, hipMemcpyAsync(out, c->s_out.p, sizeof(double) * (size_t)B * out_len, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -840,7 +799,7 @@ int trace_args(socp_ctx *c, int B, int stride, int cap)
 {
     if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "trace_batch: no problem set");
     if (B < 0 || stride < 1 || cap < 1) return fail(c, SOCP_ERR_ARG, "trace_batch: B >= 0, stride >= 1 and cap >= 1 are required");
-    if (c->vt && !(table_of(c)->trace && table_of(c)->trace_fill))
+    if (!(table_of(c)->trace && table_of(c)->trace_fill))
         return fail(c, SOCP_ERR_UNSUPPORTED, "trace_batch: this model's launch table has no trace entry");
     return SOCP_OK;
 }
@@ -855,16 +814,8 @@ int socp_trace_batch_dev(socp_ctx *c, int B, const double *d_Z, int stride, int 
     if (B == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     c->n_traj += (long long)B * c->M; c->n_launch += 2;
-    if (c->vt) {
-        HIP_TRY(c, table_of(c)->trace(c->stream, c->P, c->pb, B, d_Z, stride, cap, d_rows, d_count));
-        HIP_TRY(c, table_of(c)->trace_fill(c->stream, c->P, c->pb, B, cap, d_rows, d_count));
-    } else if (use_fast(c)) {
-        HIP_TRY(c, trace_fast(c->model_id, c->stream, c->P, c->pb, B, d_Z, stride, cap, d_rows, d_count));
-        HIP_TRY(c, trace_fill_fast(c->model_id, c->stream, c->P, c->pb, B, cap, d_rows, d_count));
-    } else {
-        HIP_TRY(c, trace_exact(c->model_id, c->stream, c->P, c->pb, B, d_Z, stride, cap, d_rows, d_count));
-        HIP_TRY(c, trace_fill_exact(c->model_id, c->stream, c->P, c->pb, B, cap, d_rows, d_count));
-    }
+    HIP_TRY(c, table_of(c)->trace(c->stream, c->P, c->pb, B, d_Z, stride, cap, d_rows, d_count));
+    HIP_TRY(c, table_of(c)->trace_fill(c->stream, c->P, c->pb, B, cap, d_rows, d_count));
     return SOCP_OK;
 }
 
@@ -921,7 +872,7 @@ int socp_trace_batch_blocks(socp_ctx *c, int B, const double *Z, const double *p
 
 /* ---- batched cost -------------------------------------------------------------------------- */
 
-int socp_ctx_has_cost(const socp_ctx *c) { return c ? ((c->vt && !table_of(c)->cost) ? 0 : 1) : SOCP_ERR_ARG; }
+int socp_ctx_has_cost(const socp_ctx *c) { return c ? (table_of(c)->cost ? 1 : 0) : SOCP_ERR_ARG; }
 
 namespace {
 // every refusal comes before anything is counted, reserved or enqueued: an error leaves the context as it was
@@ -930,7 +881,7 @@ int cost_args(socp_ctx *c, int B, const void *Z, const void *cost)
     if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "cost_batch: no problem set");
     if (B < 0) return fail(c, SOCP_ERR_ARG, "cost_batch: B >= 0 is required");
     if (B > 0 && (!Z || !cost)) return fail(c, SOCP_ERR_ARG, "cost_batch: null argument");
-    if (c->vt && !table_of(c)->cost)
+    if (!table_of(c)->cost)
         return fail(c, SOCP_ERR_UNSUPPORTED, "cost_batch: this model's launch table has no cost entry");
     if (c->P.integrator == SOCP_INT_DOPRI5)
         return fail(c, SOCP_ERR_UNSUPPORTED, "cost_batch: the running cost is integrated with the fixed-step integrator only "
@@ -947,9 +898,7 @@ int socp_cost_batch_dev(socp_ctx *c, int B, const double *d_Z, double *d_cost, d
     if (B == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     c->n_traj += (long long)B * c->M; c->n_launch += d_total ? 2 : 1;
-    if (c->vt) HIP_TRY(c, table_of(c)->cost(c->stream, c->P, c->pb, B, d_Z, d_cost, d_Xend));
-    else if (use_fast(c)) HIP_TRY(c, cost_fast(c->model_id, c->stream, c->P, c->pb, B, d_Z, d_cost, d_Xend));
-    else HIP_TRY(c, cost_exact(c->model_id, c->stream, c->P, c->pb, B, d_Z, d_cost, d_Xend));
+    HIP_TRY(c, table_of(c)->cost(c->stream, c->P, c->pb, B, d_Z, d_cost, d_Xend));
     if (d_total) HIP_TRY(c, cost_total(c->stream, B, c->M, d_cost, d_total));
     return SOCP_OK;
 }
@@ -1012,7 +961,7 @@ int move_args(socp_ctx *c, const char *who, int B, int K)
 {
     if (!c->has_problem) return fail(c, SOCP_ERR_ARG, std::string(who) + ": no problem set");
     if (B < 0 || K < 0) return fail(c, SOCP_ERR_ARG, std::string(who) + ": B >= 0 and K >= 0 are required");
-    if (c->vt && !table_of(c)->move)
+    if (!table_of(c)->move)
         return fail(c, SOCP_ERR_UNSUPPORTED, std::string(who) + ": this model's launch table has no move entry");
     return SOCP_OK;
 }
@@ -1020,9 +969,7 @@ int move_args(socp_ctx *c, const char *who, int B, int K)
 hipError_t run_move(socp_ctx *c, int B, const double *d_Z, int K, const double *d_tq, double *d_Xq, double *d_tout)
 {
     c->n_traj += (long long)B * K; c->n_launch += 1;
-    if (c->vt) return table_of(c)->move(c->stream, c->P, c->pb, B, d_Z, K, d_tq, d_Xq, d_tout);
-    return use_fast(c) ? move_fast(c->model_id, c->stream, c->P, c->pb, B, d_Z, K, d_tq, d_Xq, d_tout)
-                       : move_exact(c->model_id, c->stream, c->P, c->pb, B, d_Z, K, d_tq, d_Xq, d_tout);
+    return table_of(c)->move(c->stream, c->P, c->pb, B, d_Z, K, d_tq, d_Xq, d_tout);
 }
 
 // per-row blocks of a _blocks entry point: staged through s_aux and put in force; the caller saves and restores c->pb
@@ -1304,8 +1251,7 @@ int socp_var_jacobian_multi_dev(socp_ctx *c, int np, const double *d_Z, double *
     HIP_TRY(c, c->s_var.reserve(sizeof(double) * (2 * B * L + 2 * B)));
     double *Xaug = c->s_var.as<double>(), *Xtf = Xaug + B * L, *t0 = Xtf + B * L, *tf = t0 + B;
     c->n_traj += (long long)B; c->n_launch += 3;
-    HIP_TRY(c, c->vt ? c->vt->var_jacobian(c->stream, c->P, c->pb, np, d_Z, Xaug, Xtf, t0, tf, d_Fjac)
-                     : var_jacobian(c->model_id, c->stream, c->P, c->pb, np, d_Z, Xaug, Xtf, t0, tf, d_Fjac));
+    HIP_TRY(c, c->vt->var_jacobian(c->stream, c->P, c->pb, np, d_Z, Xaug, Xtf, t0, tf, d_Fjac));
     return SOCP_OK;
 }
 

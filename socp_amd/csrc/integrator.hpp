@@ -319,7 +319,7 @@ struct Lane {
 // ---------------------------------------------------------------------------------------------
 // WPE = cap on waves per SIMD (amdgpu_waves_per_eu max): the launcher picks ceil(waves / 1024) so that a
 // grid smaller than the chip is spread one (or two) waves per SIMD instead of being packed three deep on
-// a fraction of the SIMDs (launch_impl.hpp).
+// a fraction of the SIMDs (launch.hpp).
 template <class Mdl, int WPE, int INTEG = 0, bool PERPROB = false>      // PERPROB unused here (one launch-macro shape for all hot kernels)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) void traj_lane_kernel(ModelParams P, int B,
                                                        const double *__restrict__ t0,

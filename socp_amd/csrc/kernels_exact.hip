@@ -1,40 +1,49 @@
 // kernels_exact.hip -- reference-operation-order kernels.  MUST be compiled with
 // -ffp-contract=off (see socp_amd/csrc/Makefile): the parity tests compare these against the
-// CPU oracle at the few-ulp level.
+// CPU oracle at the few-ulp level.  Holds the launch tables of the in-tree Goddard, double-integrator and covid19
+// models (builtin_tables.hpp; adaptive Dormand-Prince instantiations included) and the model-independent launchers.
+#define SOCP_DEFINE_COMMON 1   // fd_diff, cost_total and regrid_pack live in the no-contraction TU
 #include "models_exact.hpp"
-#define SOCP_FLAVOUR exact
-#define SOCP_HAVE_DOPRI5 1      // adaptive Dormand-Prince instantiations live here (reference-order RHS)
-#define SOCP_DEFINE_COMMON 1   // fd_diff lives in the no-contraction TU
-#define SOCP_GODDARD GoddardExact
-#define SOCP_GODDARD_SMOOTH GoddardExactSmooth
-#define SOCP_COVID CovidExact
-#define SOCP_DINT DIntExact
-#include "launch_impl.hpp"
-
-// ---- variational path (compiled here: no contraction) -------------------------------------------
+#include "builtin_tables.hpp"
 #include "models_variational.hpp"
 
 namespace socp {
 
-hipError_t var_traj(int model_id, hipStream_t st, const ModelParams &P, int B, const double *t0, const double *tf,
-                    const double *X0, double *Xf)
+const ModelLaunchers *builtin_launchers(int model_id)
 {
-    if (model_id != 2) return hipErrorInvalidValue;      // in-tree: the double integrator; table-driven models bring their own (launch.hpp)
-    return varimpl::traj<DIntVar>(st, P, B, t0, tf, X0, Xf);
+    constexpr auto tables = &builtin_tables<GoddardExact, GoddardExactSmooth, CovidExact, DIntExact>;
+    // variational (hybrj) path: the double integrator only; DIntVar is a struct of its own, so the entries are set by hand
+    static const ModelLaunchers dint = [] {
+        ModelLaunchers t = *tables(SOCP_MODEL_DOUBLE_INTEGRATOR);
+        t.var_traj = &varimpl::traj<DIntVar>; t.var_jacobian = &varimpl::jacobian<DIntVar>; t.var_eval = &varimpl::eval<DIntVar>;
+        return t;
+    }();
+    return model_id == SOCP_MODEL_DOUBLE_INTEGRATOR ? &dint : tables(model_id);
 }
 
-hipError_t var_jacobian(int model_id, hipStream_t st, const ModelParams &P, const ProblemDev &pb, int np, const double *z,
-                        double *Xaug, double *Xtf, double *t0, double *tf, double *fjac)
+hipError_t regrid_pack(hipStream_t st, int B, int S, int M2, int n2, const unsigned long long (&free_bits)[4], const double *Xm,
+                       const double *T2, double *Z2)
 {
-    if (model_id != 2) return hipErrorInvalidValue;
-    return varimpl::jacobian<DIntVar>(st, P, pb, np, z, Xaug, Xtf, t0, tf, fjac);
+    if (B <= 0 || n2 <= 0) return hipSuccess;
+    RegridFree fr;
+    for (int k = 0; k < 4; k++) fr.w[k] = free_bits[k];
+    hipLaunchKernelGGL(regrid_pack_kernel, dim3(blocks_for((long)B * n2)), dim3(64), 0, st, B, S, M2, n2, fr, Xm, T2, Z2);
+    return hipGetLastError();
 }
 
-hipError_t var_eval(int model_id, hipStream_t st, const ModelParams &P, int what, int B, const double *t, const double *X, int len,
-                    double *out)
+hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *total)
 {
-    if (model_id != 2) return hipErrorInvalidValue;
-    return varimpl::eval<DIntVar>(st, P, what, B, t, X, len, out);
+    if (B <= 0 || M <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cost_total_kernel, dim3(blocks_for(B)), dim3(64), 0, st, B, M, cost, total);
+    return hipGetLastError();
+}
+
+hipError_t fd_diff(hipStream_t st, int n, int np, const double *z, double eps, const double *rows, double *fjac)
+{
+    if (np <= 0) return hipSuccess;
+    const long total = (long)np * n * n;
+    hipLaunchKernelGGL(fd_diff_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n, np, z, eps, rows, fjac);
+    return hipGetLastError();
 }
 
 }  // namespace socp

@@ -1,4 +1,5 @@
-// launch.hpp -- host-callable launchers, one set per arithmetic flavour (translation unit).
+// launch.hpp -- what the C-ABI layer launches through: every model, in-tree or plugin, is a ModelLaunchers table, one per
+// arithmetic flavour (translation unit); plus the launch geometry the tables share and the model-independent launchers.
 #pragma once
 #include <cstdlib>
 
@@ -6,7 +7,7 @@
 
 namespace socp {
 
-// ---- launch geometry shared by the in-tree flavours (launch_impl.hpp) and table-driven models (plugin_impl.hpp) ----
+// ---- launch geometry of the tables' launchers (plugin_impl.hpp) ----
 constexpr int kNumSIMD = 1024;                       // MI355X: 256 CUs x 4 SIMDs
 
 inline unsigned blocks_for(long n) { return (unsigned)((n + 63) / 64); }
@@ -36,38 +37,8 @@ inline int rows_per_block(int M, int n)
     return R < 1 ? 0 : R;
 }
 
-#define SOCP_DECLARE_LAUNCHERS(FLAVOUR)                                                              \
-    hipError_t traj_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P, int B,             \
-                              const double *t0, const double *tf, const double *sw,                  \
-                              const double *X0, double *Xf);                                         \
-    hipError_t residual_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                \
-                                  const ProblemDev &pb, int B, const double *Z, double *F);          \
-    hipError_t fdjac_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                   \
-                               const ProblemDev &pb, int np, int T, const int2 *pairs,               \
-                               const double *z, const double *fvec, double eps, double *fjac);       \
-    hipError_t fdrows_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                  \
-                                const ProblemDev &pb, int np, const double *z, double eps,           \
-                                double *rows);                                                       \
-    hipError_t dense_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P, double t0,         \
-                               double tf, double sw0, double sw1, const double *X0, double *dense,   \
-                               double *times, int cap, int *rows, double *aux);                      \
-    hipError_t eval_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P, int what, int B,   \
-                              const double *t, const double *sw, const double *X, double *out);      \
-    hipError_t trace_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                   \
-                               const ProblemDev &pb, int B, const double *Z, int stride, int cap,    \
-                               double *rows, int *count);                                            \
-    hipError_t trace_fill_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,              \
-                                    const ProblemDev &pb, int B, int cap, double *rows,              \
-                                    const int *count);                                               \
-    hipError_t cost_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                    \
-                              const ProblemDev &pb, int B, const double *Z, double *cost,            \
-                              double *Xend);                                                         \
-    hipError_t move_##FLAVOUR(int model_id, hipStream_t st, const ModelParams &P,                    \
-                              const ProblemDev &pb, int B, const double *Z, int K, const double *tq, \
-                              double *Xq, double *tout);
-
-// Launch table of an out-of-tree model (include/socp_plugin.h, plugin_impl.hpp): what the C-ABI layer calls
-// instead of the built-in flavour launchers when a context is created with a registered model id.
+// Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
+// picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
 constexpr int kPluginAbi = 8;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher
 struct ModelLaunchers {
@@ -93,15 +64,7 @@ struct ModelLaunchers {
     hipError_t (*move)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, const double *, double *, double *);
 };
 
-SOCP_DECLARE_LAUNCHERS(exact)
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
-// variational (hybrj) path: double integrator only; reference operation order
-hipError_t var_traj(int model_id, hipStream_t st, const ModelParams &P, int B, const double *t0, const double *tf,
-                    const double *X0, double *Xf);
-hipError_t var_jacobian(int model_id, hipStream_t st, const ModelParams &P, const ProblemDev &pb, int np, const double *z,
-                        double *Xaug, double *Xtf, double *t0, double *tf, double *fjac);
-hipError_t var_eval(int model_id, hipStream_t st, const ModelParams &P, int what, int B, const double *t, const double *X, int len,
-                    double *out);
 hipError_t fd_diff(hipStream_t st, int n, int np, const double *z, double eps, const double *rows, double *fjac);
 // flavour- and model-independent: total[b] = sum of cost[b][0 .. M), left to right
 hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *total);
@@ -110,9 +73,10 @@ hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *
 hipError_t regrid_pack(hipStream_t st, int B, int S, int M2, int n2, const unsigned long long (&free_bits)[4], const double *Xm,
                        const double *T2, double *Z2);
 
-SOCP_DECLARE_LAUNCHERS(fast)
-
-// in-tree models that live in their own translation unit behind a launch table, like an out-of-tree plugin
+// the in-tree models' tables, one translation unit each
+// Goddard, double integrator, covid19 by SOCP_MODEL_* id (builtin_tables.hpp); null for any other id
+const ModelLaunchers *builtin_launchers(int model_id);      // kernels_exact.hip            (reference operation order)
+const ModelLaunchers *builtin_launchers_fast(int model_id); // kernels_fast.hip             (restructured, contraction on)
 const ModelLaunchers *interceptor_launchers();      // kernels_interceptor.hip      (reference operation order)
 const ModelLaunchers *interceptor_launchers_fast(); // kernels_interceptor_fast.hip (restructured, contraction on)
 const ModelLaunchers *vtol_launchers();             // kernels_vtol.hip             (reference operation order)

@@ -1,4 +1,5 @@
-// plugin_impl.hpp -- build an OUT-OF-TREE device model into a loadable plugin.
+// plugin_impl.hpp -- the launch table of a device model (every in-tree model's is built here too: kernels_*.hip,
+// builtin_tables.hpp), and how to build an OUT-OF-TREE device model into a loadable plugin.
 //
 // A model is one struct with the static interface the in-tree models have (models_exact.hpp):
 //
@@ -54,11 +55,14 @@ template <class M, class = void> struct one_wave_per_simd : std::false_type {};
 template <class M> struct one_wave_per_simd<M, std::void_t<decltype(M::kOneWavePerSimd)>> : std::bool_constant<M::kOneWavePerSimd> {};
 
 // one launch of a hot kernel: adaptive integrator -> one wave per SIMD; otherwise occupancy cap from the grid.
+// ADAPTIVE: false for a kernel that has no adaptive instantiation (that arm is then not compiled)
 // PP: the PERPROB template argument (always false for the trajectory kernel)
-#define SOCP_PLUGIN_LAUNCH_T(KERNEL, PP, GRID, LDS, ST, ...)                                                        \
+#define SOCP_PLUGIN_LAUNCH_T(KERNEL, ADAPTIVE, PP, GRID, LDS, ST, ...)                                                \
     do {                                                                                                               \
-        if (P.integrator == 1) hipLaunchKernelGGL((KERNEL<Mdl, 1, 1, PP>), dim3(GRID), dim3(64), LDS, ST, __VA_ARGS__); \
-        else if constexpr (one_wave_per_simd<Mdl>::value)                                                              \
+        if constexpr (ADAPTIVE) {                                                                                      \
+            if (P.integrator == 1) { hipLaunchKernelGGL((KERNEL<Mdl, 1, 1, PP>), dim3(GRID), dim3(64), LDS, ST, __VA_ARGS__); break; } \
+        }                                                                                                              \
+        if constexpr (one_wave_per_simd<Mdl>::value)                                                                   \
             hipLaunchKernelGGL((KERNEL<Mdl, 1, 0, PP>), dim3(GRID), dim3(64), LDS, ST, __VA_ARGS__);                 \
         else switch (wpe_for(GRID)) {                                                                                  \
         case 1: hipLaunchKernelGGL((KERNEL<Mdl, 1, 0, PP>), dim3(GRID), dim3(64), LDS, ST, __VA_ARGS__); break;       \
@@ -66,14 +70,14 @@ template <class M> struct one_wave_per_simd<M, std::void_t<decltype(M::kOneWaveP
         default: hipLaunchKernelGGL((KERNEL<Mdl, 3, 0, PP>), dim3(GRID), dim3(64), LDS, ST, __VA_ARGS__); break;      \
         }                                                                                                              \
     } while (0)
-#define SOCP_PLUGIN_LAUNCH(KERNEL, GRID, ST, ...) SOCP_PLUGIN_LAUNCH_T(KERNEL, false, GRID, 0, ST, __VA_ARGS__)
+#define SOCP_PLUGIN_LAUNCH(KERNEL, GRID, ST, ...) SOCP_PLUGIN_LAUNCH_T(KERNEL, true, false, GRID, 0, ST, __VA_ARGS__)
 // kernels that read a shooting problem `pb`: per-problem blocks (dev_common.hpp) select the PERPROB instantiation
-#define SOCP_PLUGIN_LAUNCH_PB_LDS(KERNEL, GRID, LDS, ST, ...)                                                           \
+#define SOCP_PLUGIN_LAUNCH_PB_LDS(KERNEL, ADAPTIVE, GRID, LDS, ST, ...)                                                 \
     do {                                                                                                               \
-        if (pb.pp_params || pb.pp_time || pb.pp_xnode) SOCP_PLUGIN_LAUNCH_T(KERNEL, true, GRID, LDS, ST, __VA_ARGS__); \
-        else SOCP_PLUGIN_LAUNCH_T(KERNEL, false, GRID, LDS, ST, __VA_ARGS__);                             \
+        if (pb.pp_params || pb.pp_time || pb.pp_xnode) SOCP_PLUGIN_LAUNCH_T(KERNEL, ADAPTIVE, true, GRID, LDS, ST, __VA_ARGS__); \
+        else SOCP_PLUGIN_LAUNCH_T(KERNEL, ADAPTIVE, false, GRID, LDS, ST, __VA_ARGS__);                               \
     } while (0)
-#define SOCP_PLUGIN_LAUNCH_PB(KERNEL, GRID, ST, ...) SOCP_PLUGIN_LAUNCH_PB_LDS(KERNEL, GRID, 0, ST, __VA_ARGS__)
+#define SOCP_PLUGIN_LAUNCH_PB(KERNEL, GRID, ST, ...) SOCP_PLUGIN_LAUNCH_PB_LDS(KERNEL, true, GRID, 0, ST, __VA_ARGS__)
 
 template <class Mdl>
 hipError_t traj(hipStream_t st, const ModelParams &P, int B, const double *t0, const double *tf, const double *sw,
@@ -89,7 +93,7 @@ hipError_t residual(hipStream_t st, const ModelParams &P, const ProblemDev &pb, 
     if (B <= 0) return hipSuccess;
     const int R = rows_per_block(pb.M, pb.n);
     const unsigned grid = R ? (unsigned)((B + R - 1) / R) : blocks_for((long)B * pb.M);
-    SOCP_PLUGIN_LAUNCH_PB_LDS(residual_lane_kernel, grid, (unsigned)((long)R * pb.n * 8), st, P, pb, B, Z, F, R);
+    SOCP_PLUGIN_LAUNCH_PB_LDS(residual_lane_kernel, true, grid, (unsigned)((long)R * pb.n * 8), st, P, pb, B, Z, F, R);
     return hipGetLastError();
 }
 template <class Mdl>
@@ -107,7 +111,7 @@ hipError_t fdrows(hipStream_t st, const ModelParams &P, const ProblemDev &pb, in
     const long vrows = (long)np * (pb.n + 1);
     const int R = rows_per_block(pb.M, pb.n);
     const unsigned grid = R ? (unsigned)((vrows + R - 1) / R) : blocks_for(vrows * pb.M);
-    SOCP_PLUGIN_LAUNCH_PB_LDS(fdrows_lane_kernel, grid, (unsigned)((long)R * pb.n * 8), st, P, pb, np, z, eps, rows, R);
+    SOCP_PLUGIN_LAUNCH_PB_LDS(fdrows_lane_kernel, true, grid, (unsigned)((long)R * pb.n * 8), st, P, pb, np, z, eps, rows, R);
     return hipGetLastError();
 }
 template <class Mdl>
@@ -134,14 +138,18 @@ hipError_t trace(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int
     SOCP_PLUGIN_LAUNCH_PB(trace_lane_kernel, blocks_for((long)B * pb.M), st, P, pb, B, Z, stride, cap, rows, count);
     return hipGetLastError();
 }
+// PP: the kernel's PERPROB argument -- every problem brings its own parameter block
+template <class Mdl, bool PP>
+hipError_t trace_fill_pp(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, int cap, double *rows, const int *count)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL((trace_fill_kernel<Mdl, PP>), dim3(blocks_for((long)B * pb.M * cap)), dim3(64), 0, st, P, pb, B, cap, rows, count);
+    return hipGetLastError();
+}
 template <class Mdl>
 hipError_t trace_fill(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, int cap, double *rows, const int *count)
 {
-    if (B <= 0) return hipSuccess;
-    const unsigned grid = blocks_for((long)B * pb.M * cap);
-    if (pb.pp_params) hipLaunchKernelGGL((trace_fill_kernel<Mdl, true>), dim3(grid), dim3(64), 0, st, P, pb, B, cap, rows, count);
-    else hipLaunchKernelGGL((trace_fill_kernel<Mdl, false>), dim3(grid), dim3(64), 0, st, P, pb, B, cap, rows, count);
-    return hipGetLastError();
+    return pb.pp_params ? trace_fill_pp<Mdl, true>(st, P, pb, B, cap, rows, count) : trace_fill_pp<Mdl, false>(st, P, pb, B, cap, rows, count);
 }
 
 // batched cost: fixed-step integrator only, so no adaptive instantiation (the C-ABI layer refuses the adaptive integrator)
@@ -150,21 +158,7 @@ hipError_t cost(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int 
 {
     if (B <= 0) return hipSuccess;
     if (P.integrator != 0) return hipErrorInvalidValue;
-    const unsigned grid = blocks_for((long)B * pb.M);
-#define SOCP_PLUGIN_COST(PP, W) hipLaunchKernelGGL((cost_lane_kernel<Mdl, W, 0, PP>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, out, Xend)
-#define SOCP_PLUGIN_COST_T(PP)                                                        \
-    do {                                                                              \
-        if constexpr (one_wave_per_simd<Mdl>::value) SOCP_PLUGIN_COST(PP, 1);         \
-        else switch (wpe_for(grid)) {                                                 \
-        case 1: SOCP_PLUGIN_COST(PP, 1); break;                                       \
-        case 2: SOCP_PLUGIN_COST(PP, 2); break;                                       \
-        default: SOCP_PLUGIN_COST(PP, 3); break;                                      \
-        }                                                                             \
-    } while (0)
-    if (pb.pp_params || pb.pp_time || pb.pp_xnode) SOCP_PLUGIN_COST_T(true);
-    else SOCP_PLUGIN_COST_T(false);
-#undef SOCP_PLUGIN_COST_T
-#undef SOCP_PLUGIN_COST
+    SOCP_PLUGIN_LAUNCH_PB_LDS(cost_lane_kernel, false, blocks_for((long)B * pb.M), 0, st, P, pb, B, Z, out, Xend);
     return hipGetLastError();
 }
 

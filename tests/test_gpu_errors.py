@@ -213,3 +213,34 @@ def test_context_second_stream_is_created_once_and_left_alone():
     assert L.socp_ctx_aux_stream(twin, C.byref(st)) == 0 and st.value not in (None, a)
     assert L.socp_ctx_destroy(twin) == 0
     ctx.close()
+
+
+def test_in_tree_defaults_come_from_the_tables():
+    """A fresh context of each in-tree model that lives in the flavour translation units: parameter count and values, variational
+    and cost availability as the reference's constructors give them (goddard.cpp:23-40, doubleIntegrator.cpp:26-34,
+    covid19.cpp:25-38), and one trajectory at the default step number (and, for Goddard, the default switching times) bit-equal
+    to the reference's own first row (tests/golden/make_golden.py)."""
+    import os
+    from socp_amd import capi
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_vectors.npz"))
+    L = capi.lib()
+    cases = [
+        # model, parameters, variational, (golden input, tf, golden output)
+        (capi.MODEL_GODDARD, [3.5, 7.0, 310.0, 500.0, 1.0, 1.0, 0.0, -1.0], 0, ("g_traj_X0", 0.1, "g_traj_mu0_N10")),
+        (capi.MODEL_DOUBLE_INTEGRATOR, [1.0, 1.0, 0.01], 1, ("d_traj_X0", 7.5, "d_traj")),
+        (capi.MODEL_COVID19, [4.0, 10.0, 5.0, 1.0, 0.1, 1.0, -10.0, 20.0], 0, ("c_traj_X0", 1.5, "c_traj")),
+    ]
+    for model, params, var, (x0, tf, xf) in cases:
+        ctx = capi.Context(model)
+        assert L.socp_ctx_num_params(ctx.h) == len(params)
+        got = np.empty(len(params))
+        assert L.socp_ctx_get_params(ctx.h, got.ctypes.data_as(C.POINTER(C.c_double)), len(params)) == capi.OK
+        assert np.array_equal(got, params)
+        assert L.socp_ctx_has_variational(ctx.h) == var
+        assert L.socp_ctx_has_cost(ctx.h) == 1
+        if model == capi.MODEL_COVID19:
+            ctx.set_params([3.4, 14, 5, 1, 0.1, 1, -10, 20])       # the golden's parameters; the step number stays the default 1000
+        Xf = ctx.integrate_batch(0.0, tf, gold[x0][:1])
+        print("model %d: max |Xf - golden| = %.3g" % (model, np.max(np.abs(Xf[0] - gold[xf][0]))))
+        assert np.array_equal(Xf[0], gold[xf][0])
+        ctx.close()
