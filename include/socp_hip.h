@@ -295,6 +295,53 @@ int socp_cost_batch(socp_ctx *ctx, int B, const double *Z, double *cost, double 
 int socp_cost_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
                            const double *time, const double *xnode, double *cost, double *total, double *Xend);
 
+/* Control-structure events of a whole batch of unknown vectors: on which arcs the control of an extremal is saturated, interior or
+ * off, and when it changes branch.  [ext] The reference reads this off a plot (testGoddard.cpp:117-118: "estimated from observation
+ * of the previous solution").  A model offers event CHANNELS, scalars of (t, X) -- typically the switching function of its control
+ * law; the caller gives E watches (chan[e], level[b][e]) and gets every crossing of channel chan[e] through that level:
+ *   goddard            1 channel:  Switch = mu1 - b p_mass - C / mass |p_v|  (goddard.cpp:135), for every mu2; with mu2 > 0 the thrust
+ *                                  is on below 0 and saturated below -2 mu2 u_max
+ *   doubleIntegrator   1 channel:  the norm of the unsaturated control -p_v / a_max (doubleIntegrator.cpp:218-259); saturated above u_max
+ *   covid19            2 channels: 0 the unclamped control (covid19.cpp:97-126; levels umin, umax), 1 the state I = X[2] (level Imax:
+ *                                  the contact times of the penalised state constraint)
+ *   interceptor, vtolUAV, a plugin without the trait (include/socp_plugin.h): none
+ * Z[B][n], chan[E] (HOST array, read before the call returns: the channels travel as a kernel argument), levels[B][E] ->
+ * tev[B][M][cap], id[B][M][cap], count[B][M], Xev[B][M][cap][s] (may be NULL).  Segment i of row b is integrated exactly as the
+ * residual integrates it (same timeline, switching times, start state z[s i .. s i + s), fixed RK4 steps, per-problem blocks of
+ * socp_problem_set_blocks_dev: row b reads block b).  With g the channel values at the two ends of a step that starts at the
+ * accumulated time tk from the state Xk and has the length `step` (the clamped last step included), neg(v) = (v < 0.0):
+ *   a0 = g(tk, Xk) - level, a1 = g(tk + step, X) - level;   an event iff neither is NaN and neg(a0) != neg(a1)
+ *   a = 0.0, c = step, ga = a0, gc = a1
+ *   `refine` times:  th = a + (c - a) * (ga / (ga - gc));  Y = one RK4 step of length th from (tk, Xk);  gt = g(tk + th, Y) - level
+ *                    neg(gt) == neg(ga) ? (a = th, ga = gt) : (c = th, gc = gt)
+ *   th = a + (c - a) * (ga / (ga - gc));  tev = tk + th;  id = neg(a0) ? +(e + 1) : -(e + 1)     (rising / falling through the level)
+ *   Xev = one RK4 step of length th from (tk, Xk)
+ * in this operation order (refine = 0: linear interpolation over the step).  The events of a segment are stored in (step, e) order;
+ * count[b][i] = their number (events beyond cap are counted, not stored, nothing is written past slab [b][i]; rows at or beyond
+ * min(count, cap) keep what the buffer held).  A zero-length or backward segment takes no step: count 0.
+ * NOT SEEN: a crossing that falls in the gap between a segment's end state and the next node's unknowns (an unconverged row), and
+ * a level touched without a sign change at the ends of a step.
+ * The times are a measuring instrument for structure and a source of candidate node times for socp_regrid_batch; a stage started
+ * from them need not converge to the root a hand-picked structure converges to.
+ * socp_ctx_event_channels: the number of channels of the context's model, 0 when it has none.
+ * SOCP_ERR_ARG: no problem set, B < 0, E outside 1 .. 8, refine outside 0 .. 8, cap < 1, a channel outside 0 .. channels-1, a NULL
+ * required pointer (chan; with B > 0: Z, levels, tev, id, count), _blocks with params and param_stride != nparams + 2; B == 0: SOCP_OK
+ * without a launch; SOCP_ERR_UNSUPPORTED (the message says which): the context's integrator is SOCP_INT_DOPRI5, or the model's launch
+ * table has no events entry.  An error leaves the context unchanged.
+ * One launch; socp_ctx_counters advances by B M trajectories.  The _dev form takes device pointers (chan stays a host array),
+ * enqueues on the context's stream and neither copies nor synchronises; the host forms stage through that stream (tev, id and Xev
+ * travel both ways) and return when the results are in the caller's arrays.  _blocks: per-row blocks like
+ * socp_residual_batch_blocks (any of params / time / xnode may be NULL); the context's own blocks are restored afterwards.  When a
+ * count exceeds cap, call again with cap >= the largest count. */
+int socp_ctx_event_channels(const socp_ctx *ctx);      /* number of channels; 0: the model has none */
+int socp_events_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int E, const int *chan, const double *d_levels,
+                          int refine, int cap, double *d_tev, int *d_id, int *d_count, double *d_Xev);
+int socp_events_batch(socp_ctx *ctx, int B, const double *Z, int E, const int *chan, const double *levels,
+                      int refine, int cap, double *tev, int *id, int *count, double *Xev);
+int socp_events_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                             const double *xnode, int E, const int *chan, const double *levels, int refine, int cap, double *tev,
+                             int *id, int *count, double *Xev);
+
 /* replaces: shooting::Move(tf) (shooting.cpp:383-437) for a whole batch: the state ON a stored solution at a query time, and the
  * re-grid the reference's multi-stage flows build from it (testGoddard.cpp:115-145: vX[i] = Move(vt[i]), then InitShooting(vt, vX)
  * on a new structure).  Z[B][n], tq[B][K] -> Xq[B][K][s]; tout[B][K] (may be NULL) = the time actually reached.

@@ -135,6 +135,11 @@ def lib():
         L.socp_cost_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_cost_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
         L.socp_cost_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]
+        L.socp_ctx_event_channels.argtypes = [_vp]
+        L.socp_events_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]
+        L.socp_events_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _ip, _ip, _dp]
+        L.socp_events_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _ip,
+                                               _ip, _dp]
         L.socp_move_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
         L.socp_move_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]
         L.socp_move_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp]
@@ -232,6 +237,21 @@ def trace_kept_rows(R, stride):
     if kept[-1] != R - 1:
         kept.append(R - 1)
     return kept
+
+
+def merge_events(t, id, count):
+    """The events of all segments of every row, sorted by time: from what events_batch returns (t[B][M][cap], id[B][M][cap],
+    count[B][M]) a list of B pairs (times, ids).  Only the stored events take part (min(count, cap) per segment); events at equal
+    times keep their (segment, step, watch) order."""
+    t, id, count = np.asarray(t), np.asarray(id), np.asarray(count)
+    B, M, cap = t.shape
+    out = []
+    for b in range(B):
+        tt = np.concatenate([t[b, i, :min(int(count[b, i]), cap)] for i in range(M)]) if M else np.empty(0)
+        ii = np.concatenate([id[b, i, :min(int(count[b, i]), cap)] for i in range(M)]) if M else np.empty(0, dtype=np.int32)
+        order = np.argsort(tt, kind="stable")
+        out.append((tt[order], ii[order]))
+    return out
 
 
 def move_segment(tl, q):
@@ -578,6 +598,49 @@ class Context:
         self._chk(self.L.socp_cost_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
                                                 _d(cost), ptr(tot), ptr(xe)))
         return dict(cost=cost, total=tot, xend=xe)
+
+    # -- batched events
+    def event_channels(self):
+        """Number of event channels of this model (socp_ctx_event_channels); 0: it has none (interceptor, vtolUAV)."""
+        return self.L.socp_ctx_event_channels(self.h)
+
+    def events_batch_dev(self, B, d_Z, chan, d_levels, refine, cap, d_tev, d_id, d_count, d_Xev=None):
+        """Device pointers (ints; d_Xev may be None), chan a host sequence; enqueue only, no copy, no synchronise
+        (socp_events_batch_dev)."""
+        ch = np.ascontiguousarray(chan, dtype=np.int32).ravel()
+        self._chk(self.L.socp_events_batch_dev(self.h, int(B), _vp(d_Z), len(ch), ch.ctypes.data_as(_ip), _vp(d_levels), int(refine), int(cap),
+                                               _vp(d_tev), _vp(d_id), _vp(d_count), _vp(d_Xev)))
+
+    def events_batch(self, Z, chan, levels, refine=2, cap=4, params=None, time=None, xnode=None, xev=False):
+        """Every crossing of channel chan[e] through levels[b][e] (a 1-D levels: the same for all rows) along the residual's fixed
+        RK4 steps of every segment of every row of Z, each refined inside its step by `refine` false-position steps (include/socp_hip.h).
+        Returns (t[B][M][cap], id[B][M][cap], count[B][M]) and Xev[B][M][cap][2d] with xev=True; id = +(e+1) rising, -(e+1) falling;
+        the slots at or beyond count hold NaN / 0.  When a segment has more than `cap` events the call is repeated with the largest
+        count.  params / time / xnode: per-row blocks as in residual_batch_blocks.  merge_events sorts a row's events by time."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        ch = np.ascontiguousarray(chan, dtype=np.int32).ravel()
+        E = len(ch)
+        lv = np.asarray(levels, dtype=np.float64)
+        lv = np.array(np.broadcast_to(lv, (B, E)) if lv.ndim == 1 else lv.reshape(B, E), dtype=np.float64, order="C")
+        pp = _f64(params).reshape(B, -1) if params is not None else None
+        tt = _f64(time).reshape(B, -1) if time is not None else None
+        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
+        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+
+        def call(c):
+            t = np.full((B, self.M, c), np.nan)
+            ident = np.zeros((B, self.M, c), dtype=np.int32)
+            count = np.zeros((B, self.M), dtype=np.int32)
+            X = np.full((B, self.M, c, self.s), np.nan) if xev else None
+            self._chk(self.L.socp_events_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
+                                                      E, ch.ctypes.data_as(_ip), _d(lv), int(refine), int(c), _d(t),
+                                                      ident.ctypes.data_as(_ip), count.ctypes.data_as(_ip), ptr(X)))
+            return t, ident, count, X
+        t, ident, count, X = call(int(cap))
+        if B and count.max() > t.shape[2]:
+            t, ident, count, X = call(int(count.max()))
+        return (t, ident, count, X) if xev else (t, ident, count)
 
     # -- batched Move(tf) / re-grid
     def move_batch_dev(self, B, d_Z, K, d_tq, d_Xq, d_tout=None):

@@ -1067,6 +1067,108 @@ int socp_move_batch_blocks(socp_ctx *c, int B, const double *Z, const double *pa
     return rc;
 }
 
+/* ---- batched events ------------------------------------------------------------------------ */
+
+int socp_ctx_event_channels(const socp_ctx *c) { return c ? (table_of(c)->events ? table_of(c)->event_channels : 0) : SOCP_ERR_ARG; }
+
+namespace {
+// every refusal comes before anything is counted, reserved or enqueued: an error leaves the context as it was.
+// *chans: the watches' channels, four bits each (a kernel argument: the host array is read here)
+int events_args(socp_ctx *c, const char *who, int B, int E, const int *chan, int refine, int cap, unsigned *chans)
+{
+    const std::string w(who);
+    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, w + ": no problem set");
+    if (B < 0) return fail(c, SOCP_ERR_ARG, w + ": B >= 0 is required");
+    if (E < 1 || E > kMaxEventWatches) return fail(c, SOCP_ERR_ARG, w + ": 1 <= E <= 8 watches are required");
+    if (refine < 0 || refine > kMaxEventRefine) return fail(c, SOCP_ERR_ARG, w + ": 0 <= refine <= 8 is required");
+    if (cap < 1) return fail(c, SOCP_ERR_ARG, w + ": cap >= 1 is required");
+    if (!chan) return fail(c, SOCP_ERR_ARG, w + ": null channel table");
+    if (!table_of(c)->events)
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": this model's launch table has no events entry (the model has no event channels)");
+    if (c->P.integrator == SOCP_INT_DOPRI5)
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": events are located along the fixed-step integrator only "
+                                                 "(this context is set to SOCP_INT_DOPRI5)");
+    *chans = 0;
+    for (int e = 0; e < E; e++) {
+        if (chan[e] < 0 || chan[e] >= table_of(c)->event_channels)
+            return fail(c, SOCP_ERR_ARG, w + ": watch " + std::to_string(e) + " names channel " + std::to_string(chan[e]) +
+                                             ", the model has " + std::to_string(table_of(c)->event_channels));
+        *chans |= (unsigned)chan[e] << (4 * e);
+    }
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_events_batch_dev(socp_ctx *c, int B, const double *d_Z, int E, const int *chan, const double *d_levels, int refine, int cap,
+                          double *d_tev, int *d_id, int *d_count, double *d_Xev)
+{
+    if (!c) return SOCP_ERR_ARG;
+    unsigned chans = 0;
+    const int rc = events_args(c, "events_batch", B, E, chan, refine, cap, &chans);
+    if (rc != SOCP_OK) return rc;
+    if (B > 0 && (!d_Z || !d_levels || !d_tev || !d_id || !d_count)) return fail(c, SOCP_ERR_ARG, "events_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_traj += (long long)B * c->M; c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->events(c->stream, c->P, c->pb, B, d_Z, E, chans, d_levels, refine, cap, d_tev, d_id, d_count, d_Xev));
+    return SOCP_OK;
+}
+
+int socp_events_batch(socp_ctx *c, int B, const double *Z, int E, const int *chan, const double *levels, int refine, int cap,
+                      double *tev, int *id, int *count, double *Xev)
+{
+    if (!c) return SOCP_ERR_ARG;
+    unsigned chans = 0;
+    const int rc0 = events_args(c, "events_batch", B, E, chan, refine, cap, &chans);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B > 0 && (!Z || !levels || !tev || !id || !count)) return fail(c, SOCP_ERR_ARG, "events_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t segs = (size_t)B * c->M, slots = segs * cap;
+    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbL = sizeof(double) * (size_t)B * E, nbT = sizeof(double) * slots,
+                 nbX = Xev ? sizeof(double) * slots * c->S : 0, nbI = sizeof(int) * slots, nbC = sizeof(int) * segs;
+    HIP_TRY(c, c->s_in.reserve(nbZ + nbL));
+    HIP_TRY(c, c->s_out.reserve(nbT + nbX));
+    HIP_TRY(c, c->s_var.reserve(nbI + nbC));
+    double *dZ = c->s_in.as<double>(), *dL = dZ + (size_t)B * c->n, *dT = c->s_out.as<double>(), *dX = dT + slots;
+    int *dI = c->s_var.as<int>(), *dC = dI + slots;
+    HIP_TRY(c, hipMemcpyAsync(dZ, Z, nbZ, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dL, levels, nbL, hipMemcpyHostToDevice, c->stream));
+    // the caller's buffers travel both ways: what the kernel leaves untouched (rows at or beyond min(count, cap)) comes back as it went
+    HIP_TRY(c, hipMemcpyAsync(dT, tev, nbT, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dI, id, nbI, hipMemcpyHostToDevice, c->stream));
+    if (Xev) HIP_TRY(c, hipMemcpyAsync(dX, Xev, nbX, hipMemcpyHostToDevice, c->stream));
+    const int rc = socp_events_batch_dev(c, B, dZ, E, chan, dL, refine, cap, dT, dI, dC, Xev ? dX : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(tev, dT, nbT, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(id, dI, nbI, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(count, dC, nbC, hipMemcpyDeviceToHost, c->stream));
+    if (Xev) HIP_TRY(c, hipMemcpyAsync(Xev, dX, nbX, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_events_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                             const double *xnode, int E, const int *chan, const double *levels, int refine, int cap, double *tev,
+                             int *id, int *count, double *Xev)
+{
+    if (!c) return SOCP_ERR_ARG;
+    unsigned chans = 0;
+    const int rc0 = events_args(c, "events_batch_blocks", B, E, chan, refine, cap, &chans);
+    if (rc0 != SOCP_OK) return rc0;
+    // before anything is sized or copied from it: a wrong stride would read past the caller's array
+    if (params && pstride != c->nparams + 2)
+        return fail(c, SOCP_ERR_ARG, "events_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    if (B > 0 && (!Z || !levels || !tev || !id || !count)) return fail(c, SOCP_ERR_ARG, "events_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const ProblemDev saved = c->pb;
+    int rc = stage_blocks(c, B, params, pstride, time, xnode);
+    if (rc == SOCP_OK) rc = socp_events_batch(c, B, Z, E, chan, levels, refine, cap, tev, id, count, Xev);
+    c->pb = saved;
+    return rc;
+}
+
 int socp_regrid_num_param(const socp_ctx *c, int M2, const int *mode_t2)
 {
     unsigned long long bits[4];

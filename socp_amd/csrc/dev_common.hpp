@@ -22,6 +22,8 @@ struct ModelParams {
 };
 constexpr int kMapStride = 7;          // type, centre xyz, radii xyz (SOCP_MAP_STRIDE)
 constexpr int kMaxObstacles = 256;     // upper bound of socp_ctx_set_map (SOCP_MAX_OBSTACLES)
+constexpr int kMaxEventWatches = 8;    // socp_events_batch: watches per call (their channels travel as 4 bits each of one kernel argument)
+constexpr int kMaxEventRefine = 8;     // socp_events_batch: false-position steps per event
 
 // Shooting problem tables (device pointers), built by socp_problem_set.
 // node_kind[k]:  >=0 -> FREE junction, value = index into z of its time unknown

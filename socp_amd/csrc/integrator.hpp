@@ -31,6 +31,11 @@ template <class M> struct has_switching_state<M, std::void_t<decltype(&M::switch
 // are zero: the reference's default hook is a no-op on a block its caller has just zeroed.
 template <class M, class = void> struct has_switching_state_jac : std::false_type {};
 template <class M> struct has_switching_state_jac<M, std::void_t<decltype(&M::switching_state_jac)>> : std::true_type {};
+// optional trait event channels (socp_events_batch): kEventChannels scalars the model lets a caller watch along a trajectory,
+//   event_fn(P, sw0, sw1, t, X, chan)   -- typically the switching function of its control law (models_exact.hpp).
+// Absent = 0 channels: the model's launch table has no events entry.
+template <class M, class = void> struct event_channels : std::integral_constant<int, 0> {};
+template <class M> struct event_channels<M, std::void_t<decltype(M::kEventChannels)>> : std::integral_constant<int, M::kEventChannels> {};
 template <class M, class = void> struct has_custom_final : std::false_type {};
 template <class M> struct has_custom_final<M, std::void_t<decltype(M::kCustomFinal)>> : std::bool_constant<M::kCustomFinal> {};
 
@@ -306,6 +311,74 @@ struct Lane {
         while (t < (tf - dt / 2) && guard-- > 0) {
             const double step = (t + dt > tf) ? (tf - t) : dt;
             rk4_cost(P, sw0, sw1, t, X, step, q);
+            t += dt;
+        }
+    }
+
+    // ---- event location (socp_events_batch): the loop of integrate(), statement for statement, around rk4(), with the state
+    // before the step (Xk, at the accumulated time tk) and the channel values at both ends of the step kept.  Watch e looks at
+    // channel chan[e] (four bits of `chans` each) minus level[e]; a sign change over a step, neg(v) = (v < 0.0) and neither end
+    // NaN, is an event.  It is refined inside the step by `refine` bracketed false-position steps, each ONE RK4 step of length
+    // th from Xk (not an interpolant: the located state is a state the integrator itself produces), then one more interpolation:
+    //     a = 0.0, c = step, ga = a0, gc = a1
+    //     repeat:  th = a + (c - a) * (ga / (ga - gc));  Y = rk4(tk, Xk, th);  gt = event_fn(tk + th, Y) - level
+    //              neg(gt) == neg(ga) ? (a = th, ga = gt) : (c = th, gc = gt)
+    //     te = tk + (a + (c - a) * (ga / (ga - gc)))
+    // in exactly this operation order (the parity contract of tests/events_reference.py).  id = +(e+1) rising through the level,
+    // -(e+1) falling.  Events leave through sink(te, id, tk, Xk, th) in (step, e) order.  All channels are evaluated at every
+    // step end (their number is a compile-time constant, so g0 / g1 stay in registers); the refinement runs under the exec
+    // mask of the few lanes that have an event in the step.
+    template <class Sink>
+    __device__ static __forceinline__ void integrate_events(const ModelParams &P, double sw0, double sw1, double t0, double tf,
+                                                           double (&X)[S], int E, unsigned chans, const double *__restrict__ level,
+                                                           int refine, Sink &&sink)
+    {
+        constexpr int NC = event_channels<Mdl>::value;
+        static_assert(NC >= 1, "the model has no event channels");
+        auto pick = [](const double (&g)[NC], int ch) {
+            double v = g[0];
+#pragma unroll
+            for (int c = 1; c < NC; c++) v = (ch == c) ? g[c] : v;
+            return v;
+        };
+        const double dt = (tf - t0) / P.step_nbr;
+        double t = t0;
+        double g0[NC], g1[NC], Xk[S];
+#pragma unroll
+        for (int c = 0; c < NC; c++) g0[c] = Mdl::event_fn(P, sw0, sw1, t0, X, c);
+        int guard = P.step_nbr + 8;
+        while (t < (tf - dt / 2) && guard-- > 0) {
+            const double step = (t + dt > tf) ? (tf - t) : dt;
+#pragma unroll
+            for (int k = 0; k < S; k++) Xk[k] = X[k];
+            rk4(P, sw0, sw1, t, X, step);
+#pragma unroll
+            for (int c = 0; c < NC; c++) g1[c] = Mdl::event_fn(P, sw0, sw1, t + step, X, c);
+            for (int e = 0; e < E; e++) {
+                const int ch = (int)((chans >> (4 * e)) & 15u);
+                const double lv = level[e];
+                const double a0 = pick(g0, ch) - lv, a1 = pick(g1, ch) - lv;
+                if (a0 == a0 && a1 == a1 && (a0 < 0.0) != (a1 < 0.0)) {
+                    double a = 0.0, c = step, ga = a0, gc = a1;
+                    for (int r = 0; r < refine; r++) {
+                        const double th = a + (c - a) * (ga / (ga - gc));
+                        double Y[S];
+#pragma unroll
+                        for (int k = 0; k < S; k++) Y[k] = Xk[k];
+                        rk4(P, sw0, sw1, t, Y, th);
+                        const double gt = Mdl::event_fn(P, sw0, sw1, t + th, Y, ch) - lv;
+                        const bool same = (gt < 0.0) == (ga < 0.0);
+                        a = same ? th : a;
+                        ga = same ? gt : ga;
+                        c = same ? c : th;
+                        gc = same ? gc : gt;
+                    }
+                    const double th = a + (c - a) * (ga / (ga - gc));
+                    sink(t + th, (a0 < 0.0) ? e + 1 : -(e + 1), t, Xk, th);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NC; c++) g0[c] = g1[c];
             t += dt;
         }
     }
@@ -929,6 +1002,79 @@ __global__ __launch_bounds__(64) void cost_total_kernel(int B, int M, const doub
     total[b] = s;
 }
 #endif
+
+// ---------------------------------------------------------------------------------------------
+// K_events: the control-structure events of every segment of B unknown vectors (socp_events_batch).  Z[B][n], levels[B][E] ->
+// tev[B][M][cap], id[B][M][cap], count[B][M] and, unless null, Xev[B][M][cap][S].  One lane = (row, segment), T = b M + i, the
+// lane mapping of K_cost.  Segment i starts from the shared prologue (Timeline / segment_start), so the segment watched IS the
+// segment the residual integrates, and Lane::integrate_events takes the residual's fixed steps.  The events of a segment are
+// stored in (step, watch) order: the first `cap` are stored, all are counted, and the rows at or beyond min(count, cap) keep
+// what the buffer held (the conventions of K_trace); nothing is written past slab [b][i].  Xev of an event is one more RK4 step
+// of the located length from the state before the step.  A zero-length or backward segment takes no step: count 0.
+// NOT SEEN: a crossing in the gap between a segment's end state and the next node's unknowns (an unconverged row, whose
+// trajectory jumps there) -- the watch compares the two ends of STEPS, and no step spans a node.
+// Fixed-step RK4 only, and no model with its own ComputeTraj.  Consecutive lanes store consecutive words of count; every store
+// site is ONE block under ONE computed predicate (see the note in segment_residual).
+// ---------------------------------------------------------------------------------------------
+template <class Mdl, class ZRead>
+__device__ __forceinline__ void segment_events(const ModelParams &P, const ProblemDev &pb, const ZRead &z, int i, int E, unsigned chans,
+                                               const double *__restrict__ level, int refine, int cap, double *__restrict__ tev,
+                                               int *__restrict__ id, int *__restrict__ count, double *__restrict__ xev)
+{
+    static_assert(!has_custom_traj<Mdl>::value, "the events of a model with its own ComputeTraj need a definition of their own");
+    constexpr int S = Mdl::S;
+    const Timeline<ZRead> tl{pb, z};
+    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
+    const double sw0 = tl.template switching_time<Mdl>(P.sw0, pb.sw_node0), sw1 = tl.template switching_time<Mdl>(P.sw1, pb.sw_node1);
+    double X[S];
+    segment_start(z, S * i, X);
+    int found = 0;      // events so far (those beyond cap are counted, not stored)
+    Lane<Mdl>::integrate_events(P, sw0, sw1, t1, t2, X, E, chans, level, refine,
+                                [&](double te, int ev, double tk, const double (&Xk)[S], double th) {
+        const bool st = found < cap;
+        if (st) {
+            tev[found] = te;
+            id[found] = ev;
+        }
+        const bool sx = st && xev != nullptr;
+        if (sx) {
+            double Y[S];
+#pragma unroll
+            for (int k = 0; k < S; k++) Y[k] = Xk[k];
+            Lane<Mdl>::rk4(P, sw0, sw1, tk, Y, th);
+            double *row = xev + (long)found * S;
+#pragma unroll
+            for (int k = 0; k < S; k++) row[k] = Y[k];
+        }
+        found++;
+    });
+    *count = found;
+}
+
+template <class Mdl, int WPE, int INTEG = 0, bool PERPROB = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) void events_lane_kernel(ModelParams P, ProblemDev pb, int B,
+                                                            const double *__restrict__ Z, int E, unsigned chans,
+                                                            const double *__restrict__ levels, int refine, int cap,
+                                                            double *__restrict__ tev, int *__restrict__ id,
+                                                            int *__restrict__ count, double *__restrict__ Xev)
+{
+    static_assert(INTEG == 0, "events are located along the fixed-step integrator only");
+    const long T = (long)blockIdx.x * 64 + threadIdx.x;              // = b * M + i: index into count, slab of tev / id / Xev
+    if (T >= (long)B * pb.M) return;
+    const long b = T / pb.M;
+    const int i = (int)(T - b * pb.M);
+    const double *zr = Z + b * pb.n;
+    auto z = [=](int k) -> double { return zr[k]; };
+    double *xe = Xev ? Xev + T * cap * Mdl::S : nullptr;
+    if constexpr (PERPROB) {
+        ModelParams Pq = P;
+        ProblemDev pq = pb;
+        load_problem_block(pb, b, Pq, pq);
+        segment_events<Mdl>(Pq, pq, z, i, E, chans, levels + b * E, refine, cap, tev + T * cap, id + T * cap, count + T, xe);
+    } else {
+        segment_events<Mdl>(P, pb, z, i, E, chans, levels + b * E, refine, cap, tev + T * cap, id + T * cap, count + T, xe);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // K_move: shooting::Move(tf) (shooting.cpp:383-437) for a whole batch -- the state ON the stored solution z at a query time.

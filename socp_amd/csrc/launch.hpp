@@ -39,8 +39,9 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 8;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
-                                   // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher
+constexpr int kPluginAbi = 9;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+                                   // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
+                                   // 9: batched events launcher
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -62,6 +63,12 @@ struct ModelLaunchers {
     hipError_t (*cost)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *);
     // batched Move(tf) (socp_move_batch): Z[B][n], tq[B][K] -> Xq[B][K][S] and, unless null, tout[B][K]; both integrators
     hipError_t (*move)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, const double *, double *, double *);
+    // batched events (socp_events_batch): Z[B][n], E watches (channel of watch e: bits 4e .. 4e+3 of `chans`), levels[B][E],
+    // refine, cap -> tev[B][M][cap], id[B][M][cap], count[B][M] and, unless null, Xev[B][M][cap][S]; fixed-step integrator only.
+    // event_channels = 0 and a null entry: the model has no event channels (no kEventChannels / event_fn trait)
+    int event_channels;
+    hipError_t (*events)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, unsigned, const double *, int, int,
+                         double *, int *, int *, double *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)

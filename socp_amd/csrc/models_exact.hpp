@@ -272,6 +272,17 @@ struct GoddardExactT {
     {
         return hamiltonian(P, sw0, sw1, t, X);
     }
+
+    // event channel 0 (socp_events_batch): the switching function of the control law, goddard.cpp:135 in its order, on plain IEEE
+    // operations (no shared-denominator quotient: tests/events_reference.py restates it in numpy bit for bit).  Defined for every
+    // mu2; with mu2 > 0 the thrust is on below 0 and saturated below -2 mu2 u_max.
+    static constexpr int kEventChannels = 1;
+    __device__ static __forceinline__ double event_fn(const ModelParams &P, double, double, double, const double (&X)[S], int)
+    {
+        const double mass = X[6], p_vx = X[10], p_vy = X[11], p_vz = X[12], p_mass = X[13];
+        const double norm_pv = sqrt(p_vx*p_vx + p_vy*p_vy + p_vz*p_vz);
+        return P.p[GP_MU1] - P.p[GP_B]*p_mass - P.p[GP_C] / mass*norm_pv;
+    }
 };
 
 using GoddardExact = GoddardExactT<false>;        // general law (any mu2)
@@ -312,6 +323,16 @@ struct DIntExact {
         dX[9] = -X[6];  dX[10] = -X[7];  dX[11] = -X[8];
     }
 
+    // event channel 0 (socp_events_batch): the norm of the unsaturated control (doubleIntegrator.cpp:218-259 before the
+    // rescaling); the control is saturated above u_max
+    static constexpr int kEventChannels = 1;
+    __device__ static __forceinline__ double event_fn(const ModelParams &P, double, double, double, const double (&X)[S], int)
+    {
+        const double a_max = P.p[DP_AMAX];
+        const double u0 = -X[9] / a_max, u1 = -X[10] / a_max, u2 = -X[11] / a_max;
+        return sqrt(u0*u0 + u1*u1 + u2*u2);
+    }
+
     // doubleIntegrator.cpp:264-300, isJac == 0
     __device__ static double hamiltonian(const ModelParams &P, double sw0, double sw1, double t, const double (&X)[S])
     {
@@ -350,6 +371,16 @@ struct CovidExact {
     __device__ static void control_only(const ModelParams &P, double, double, double, const double (&X)[S], double (&u)[3])
     {
         u[0] = control_scalar(P, X); u[1] = 0; u[2] = 0;
+    }
+
+    // event channels (socp_events_batch).  0: the unclamped control, the first line of control_scalar (covid19.cpp:97-126) --
+    // the control sits on its bounds below umin and above umax; 1: I = X[2], whose crossings of Imax are the contact times of
+    // the penalised state constraint
+    static constexpr int kEventChannels = 2;
+    __device__ static __forceinline__ double event_fn(const ModelParams &P, double, double, double, const double (&X)[S], int chan)
+    {
+        const double u = (X[5] - X[4])*X[0]*X[2] / P.p[CP_TINF] / P.p[CP_N] * P.p[CP_R0];
+        return chan == 0 ? u : X[2];
     }
 
     // covid19.cpp:53-95.  All ten divisions are by the model constants Tinf, Tinc, N: shared denominators (see Den).

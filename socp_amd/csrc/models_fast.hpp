@@ -161,6 +161,12 @@ struct GoddardFastT {
     {
         return GoddardExactT<SMOOTH>::switching_fn(P, sw0, sw1, t, X, Xp);
     }
+    // the event channel of the reference-order flavour (one evaluation per step: nothing to restructure), contraction on
+    static constexpr int kEventChannels = 1;
+    __device__ static __forceinline__ double event_fn(const ModelParams &P, double sw0, double sw1, double t, const double (&X)[S], int chan)
+    {
+        return GoddardExactT<SMOOTH>::event_fn(P, sw0, sw1, t, X, chan);
+    }
 };
 
 using GoddardFast = GoddardFastT<false>;

@@ -27,6 +27,11 @@
 //       __device__ static void switching_state_jac(const socp::ModelParams &P, double t, int j, const double (&X)[S], const double (&Xp)[S],
 //                                                  const double *Xd, double (&dfs_dX)[S], double (&dfs_dXp)[S],
 //                                                  double (&dfc_dX)[S], double (&dfc_dXp)[S]);
+//       // OPTIONAL -- event channels (socp_events_batch): scalars a caller may watch along the trajectories, typically the
+//       // switching function of the control law.  Plain IEEE operations if a CPU restatement is to match bit for bit.
+//       static constexpr int kEventChannels = ...;                                        // 1 .. 16
+//       __device__ static double event_fn(const socp::ModelParams &P, double sw0, double sw1, double t,
+//                                         const double (&X)[S], int chan);
 //       // OPTIONAL -- variational equations, for classes with modelOrder = 1 (hybrj; model.hpp:104-120,149-183):
 //       __device__ static double aug_rhs(const socp::ModelParams &P, double t, int e, const double *Y);
 //                 // element e of Model(t, Y, isJac = 1), Y = [X(S) ; R(S x S)], R[k][i] at Y[S (k+1) + i]  
@@ -39,7 +44,7 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
 #include "launch.hpp"
@@ -172,6 +177,20 @@ hipError_t move(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int 
     return hipGetLastError();
 }
 
+// batched events: fixed-step integrator only, like the cost.  The state before the step stays alive beside rk4()'s working set,
+// so the Goddard instantiations take more registers than the residual's and run one or two waves per SIMD whatever WPE allows;
+// no instantiation has a private segment ("Batched events")
+template <class Mdl>
+hipError_t events(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int E, unsigned chans,
+                  const double *levels, int refine, int cap, double *tev, int *id, int *count, double *Xev)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0 || E < 1 || E > kMaxEventWatches || refine < 0 || refine > kMaxEventRefine || cap < 1) return hipErrorInvalidValue;
+    SOCP_PLUGIN_LAUNCH_PB_LDS(events_lane_kernel, false, blocks_for((long)B * pb.M), 0, st, P, pb, B, Z, E, chans, levels, refine, cap, tev, id,
+                              count, Xev);
+    return hipGetLastError();
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -192,6 +211,10 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     t.dense = &dense<Mdl>; t.eval = &eval<Mdl>; t.trace = &trace<Mdl>; t.trace_fill = &trace_fill<Mdl>;
     t.move = &move<Mdl>;
     if constexpr (!has_custom_traj<Mdl>::value) t.cost = &cost<Mdl>;     // a model with its own ComputeTraj has no cost kernel
+    if constexpr (event_channels<Mdl>::value > 0 && !has_custom_traj<Mdl>::value) {
+        static_assert(event_channels<Mdl>::value <= 16, "a watch's channel travels in four bits");
+        t.event_channels = event_channels<Mdl>::value; t.events = &events<Mdl>;
+    }
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

@@ -311,6 +311,32 @@ def cost_local(ctx, args, local, lo, rank, params=None):
             "wall_s": wall, "file": path}
 
 
+def events_local(ctx, args, local, lo, rank, params=None):
+    """--events-out: the control-structure events (socp_events_batch) of this rank's CONVERGED chains, each with its own parameter
+    block when the chains have one: the crossings of Goddard's switching function Switch = mu1 - b p_mass - C / m |p_v| through
+    -2 mu2 u_max (watch 1: saturation) and through 0 (watch 2: thrust on / off), the levels from each chain's own parameters, every
+    crossing refined by --events-refine false-position steps.  Written to PATH.rank<r>.npz: t [k][M][cap] and id [k][M][cap]
+    (+e rising / -e falling through the level of watch e), count [k][M], index [k] = position of the chain in the sweep's start
+    table.  Runs after the timed solve.  Returns the record entry of this rank, with the number of chains per event signature
+    (the ids of a chain in time order): a measuring instrument for structure, not a structure guess for a next stage."""
+    from . import capi
+    conv = np.where(np.asarray(local["info"]) == 1)[0]
+    z = np.asarray(local["z"])[conv]
+    own = np.tile(np.asarray(ctx.get_params()), (len(conv), 1)) if params is None else np.asarray(params)[conv]
+    levels = np.stack([-2.0 * own[:, 6] * own[:, 4], np.zeros(len(conv))], axis=1)
+    t0 = time.perf_counter()
+    t, ident, count = ctx.events_batch(z, [0, 0], levels, refine=args.events_refine, params=None if params is None else params[conv])
+    wall = time.perf_counter() - t0
+    path = "%s.rank%d.npz" % (args.events_out, rank)
+    np.savez(path, index=lo + conv, t=t, id=ident, count=count)
+    signatures = {}
+    for _times, ids in capi.merge_events(t, ident, count):
+        key = ",".join("%+d" % i for i in ids)
+        signatures[key] = signatures.get(key, 0) + 1
+    return {"chains": int(len(conv)), "refine": args.events_refine, "events_per_segment_max": int(count.max()) if len(conv) else 0,
+            "signatures": signatures, "wall_s": wall, "file": path}
+
+
 def regrid_structure(args):
     """--regrid-segments: time modes of the target structure -- goddard_multiple_shooting_problem(M2)'s (free final time) for a
     multiple-shooting sweep, FIXED end times for single shooting (whose final time is fixed)."""
@@ -435,7 +461,20 @@ def main():
                          "parameter blocks; the structure of the M2-segment testGoddard layout, FIXED end times for --segments 1), writes "
                          "PATH.rank<r>.npz (index, z, time, xnode, source) and adds regrid_rank<r> {count, n2, seconds} to the record.  Not "
                          "with --model interceptor.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--events-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank locates the control-structure events of the converged chains of its own block in "
+                         "one batch (socp_events_batch): the crossings of Goddard's switching function through -2 mu2 u_max (saturation) "
+                         "and 0 (thrust on / off), the levels from the chains' own parameter blocks; writes PATH.rank<r>.npz (index, t, "
+                         "id, count) and adds events_rank<r> {chains, refine, events_per_segment_max, signatures, wall_s, file} to the "
+                         "record, signatures = chains per tuple of event ids in time order.  Not with --model interceptor.  Absent: "
+                         "the timed wall and the printed record are unchanged")
+    ap.add_argument("--events-refine", type=int, default=2, metavar="R",
+                    help="with --events-out: false-position steps per event, 0 .. 8 (0: linear interpolation over the step)")
     args = ap.parse_args()
+    if not 0 <= args.events_refine <= 8:
+        ap.error("--events-refine must be 0 .. 8")
+    if args.events_out and args.model == "interceptor":
+        ap.error("--events-out: the interceptor has no event channels (its own ComputeTraj rewrites the costate in mid-trajectory)")
     if bool(args.regrid_out) != (args.regrid_segments > 0) or not 0 <= args.regrid_segments <= 255:
         ap.error("--regrid-segments M2 (1 .. 255) and --regrid-out PATH go together")
     if args.regrid_out and args.model == "interceptor":
@@ -542,6 +581,12 @@ def main():
             blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
             blocks[:, 2] = local["param_final"]
         extra["regrid_rank%d" % rank] = regrid_local(ctx, args, local, lo_w, rank, blocks)
+    if args.events_out:
+        blocks = None
+        if chain_kw is not None:                        # as for the trace: every chain at the KD it reached
+            blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
+            blocks[:, 2] = local["param_final"]
+        extra["events_rank%d" % rank] = events_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
