@@ -271,11 +271,28 @@ def move_segment(tl, q):
 
 
 def _d(a):
-    return a.ctypes.data_as(_dp)
+    """double* of a float64 array (the pointer keeps the array alive); None stays None: an optional argument that is absent."""
+    return a.ctypes.data_as(_dp) if a is not None else None
 
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _block_args(B, params, time, xnode):
+    """The (params, param_stride, time, xnode) arguments of a _blocks entry point from per-row blocks of B rows each (None: absent)."""
+    pp, tt, xx = (_f64(a).reshape(B, -1) if a is not None else None for a in (params, time, xnode))
+    return _d(pp), pp.shape[1] if pp is not None else 0, _d(tt), _d(xx)
+
+
+def _call_with_enough_cap(call, cap):
+    """call(cap) -> (count[B][M], result) of an entry point that stores at most `cap` items per segment and counts them all: called
+    with `cap` and, when a segment had more, once more with cap = count.max().  Returns the last result."""
+    cap = int(cap)
+    count, result = call(cap)
+    if count.size and count.max() > cap:
+        count, result = call(int(count.max()))
+    return result
 
 
 class Context:
@@ -528,12 +545,7 @@ class Context:
         Z = _f64(Z).reshape(-1, self.n)
         B = Z.shape[0]
         F = np.empty_like(Z)
-        pp = _f64(params).reshape(B, -1) if params is not None else None
-        tt = _f64(time).reshape(B, -1) if time is not None else None
-        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
-        self._chk(self.L.socp_residual_batch_blocks(self.h, B, _d(Z), _d(pp) if pp is not None else None,
-                                                    pp.shape[1] if pp is not None else 0, _d(tt) if tt is not None else None,
-                                                    _d(xx) if xx is not None else None, _d(F)))
+        self._chk(self.L.socp_residual_batch_blocks(self.h, B, _d(Z), *_block_args(B, params, time, xnode), _d(F)))
         return F
 
     # -- batched trace
@@ -553,25 +565,18 @@ class Context:
         one more with cap = count.max() when a segment had more."""
         Z = _f64(Z).reshape(-1, self.n)
         B, W = Z.shape[0], self.trace_width()
-        pp = _f64(params).reshape(B, -1) if params is not None else None
-        tt = _f64(time).reshape(B, -1) if time is not None else None
-        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
-        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+        blocks = _block_args(B, params, time, xnode)
 
         def call(c):
             rows = np.full((B, self.M, c, W), np.nan if fill is None else fill)
             count = np.zeros((B, self.M), dtype=np.int32)
-            self._chk(self.L.socp_trace_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
-                                                     int(stride), int(c), _d(rows), count.ctypes.data_as(_ip)))
-            return rows, count
+            self._chk(self.L.socp_trace_batch_blocks(self.h, B, _d(Z), *blocks, int(stride), c, _d(rows), count.ctypes.data_as(_ip)))
+            return count, (rows, count)
         if cap is not None:
-            return call(int(cap))
+            return call(int(cap))[1]
         step_nbr, integrator = C.c_int(), C.c_int()
         self._chk(self.L.socp_ctx_get_integrator(self.h, C.byref(step_nbr), C.byref(integrator), None))
-        rows, count = call(64 if integrator.value == INT_DOPRI5 else step_nbr.value // int(stride) + 3)
-        if B and count.max() > rows.shape[2]:
-            rows, count = call(int(count.max()))
-        return rows, count
+        return _call_with_enough_cap(call, 64 if integrator.value == INT_DOPRI5 else step_nbr.value // int(stride) + 3)
 
     # -- batched cost
     def has_cost(self):
@@ -588,15 +593,11 @@ class Context:
         residual_batch_blocks.  Fixed-step integrator only; not for the interceptor (has_cost)."""
         Z = _f64(Z).reshape(-1, self.n)
         B = Z.shape[0]
-        pp = _f64(params).reshape(B, -1) if params is not None else None
-        tt = _f64(time).reshape(B, -1) if time is not None else None
-        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
-        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+        blocks = _block_args(B, params, time, xnode)
         cost = np.empty((B, self.M))
         tot = np.empty(B) if total else None
         xe = np.empty((B, self.M, self.s)) if xend else None
-        self._chk(self.L.socp_cost_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
-                                                _d(cost), ptr(tot), ptr(xe)))
+        self._chk(self.L.socp_cost_batch_blocks(self.h, B, _d(Z), *blocks, _d(cost), _d(tot), _d(xe)))
         return dict(cost=cost, total=tot, xend=xe)
 
     # -- batched events
@@ -623,24 +624,17 @@ class Context:
         E = len(ch)
         lv = np.asarray(levels, dtype=np.float64)
         lv = np.array(np.broadcast_to(lv, (B, E)) if lv.ndim == 1 else lv.reshape(B, E), dtype=np.float64, order="C")
-        pp = _f64(params).reshape(B, -1) if params is not None else None
-        tt = _f64(time).reshape(B, -1) if time is not None else None
-        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
-        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+        blocks = _block_args(B, params, time, xnode)
 
         def call(c):
             t = np.full((B, self.M, c), np.nan)
             ident = np.zeros((B, self.M, c), dtype=np.int32)
             count = np.zeros((B, self.M), dtype=np.int32)
             X = np.full((B, self.M, c, self.s), np.nan) if xev else None
-            self._chk(self.L.socp_events_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
-                                                      E, ch.ctypes.data_as(_ip), _d(lv), int(refine), int(c), _d(t),
-                                                      ident.ctypes.data_as(_ip), count.ctypes.data_as(_ip), ptr(X)))
-            return t, ident, count, X
-        t, ident, count, X = call(int(cap))
-        if B and count.max() > t.shape[2]:
-            t, ident, count, X = call(int(count.max()))
-        return (t, ident, count, X) if xev else (t, ident, count)
+            self._chk(self.L.socp_events_batch_blocks(self.h, B, _d(Z), *blocks, E, ch.ctypes.data_as(_ip), _d(lv), int(refine), c, _d(t),
+                                                      ident.ctypes.data_as(_ip), count.ctypes.data_as(_ip), _d(X)))
+            return count, ((t, ident, count, X) if xev else (t, ident, count))
+        return _call_with_enough_cap(call, cap)
 
     # -- batched Move(tf) / re-grid
     def move_batch_dev(self, B, d_Z, K, d_tq, d_Xq, d_tout=None):
@@ -656,14 +650,10 @@ class Context:
         tq = _f64(tq)
         K = tq.size // B if B else (tq.shape[-1] if tq.ndim >= 2 else 0)
         tq = tq.reshape(B, K)
-        pp = _f64(params).reshape(B, -1) if params is not None else None
-        tt = _f64(time).reshape(B, -1) if time is not None else None
-        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
-        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+        blocks = _block_args(B, params, time, xnode)
         Xq = np.full((B, K, self.s), np.nan)
         to = np.full((B, K), np.nan) if tout else None
-        self._chk(self.L.socp_move_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
-                                                K, _d(tq), _d(Xq), ptr(to)))
+        self._chk(self.L.socp_move_batch_blocks(self.h, B, _d(Z), *blocks, K, _d(tq), _d(Xq), _d(to)))
         return (Xq, to) if tout else Xq
 
     def regrid_num_param(self, mode_t2):
@@ -689,15 +679,11 @@ class Context:
         mt = np.ascontiguousarray(mode_t2, dtype=np.int32)
         M2 = len(mt) - 1
         T2 = np.array(np.broadcast_to(np.asarray(T2, dtype=np.float64), (B, M2 + 1)), order="C")       # the caller's own times: returned as `time`
-        pp = _f64(params).reshape(B, -1) if params is not None else None
-        tt = _f64(time).reshape(B, -1) if time is not None else None
-        xx = _f64(xnode).reshape(B, -1) if xnode is not None else None
-        ptr = lambda a: _d(a) if a is not None else None  # noqa: E731
+        blocks = _block_args(B, params, time, xnode)
         n2 = self.L.socp_regrid_num_param(self.h, M2, mt.ctypes.data_as(_ip))
         Z2 = np.full((B, max(n2, 0)), np.nan)
         X2 = np.full((B, M2 + 1, self.s), np.nan) if want_xnode else None
-        self._chk(self.L.socp_regrid_batch_blocks(self.h, B, _d(Z), ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx),
-                                                  M2, mt.ctypes.data_as(_ip), _d(T2), _d(Z2), ptr(X2)))
+        self._chk(self.L.socp_regrid_batch_blocks(self.h, B, _d(Z), *blocks, M2, mt.ctypes.data_as(_ip), _d(T2), _d(Z2), _d(X2)))
         return dict(z=Z2, time=T2, xnode=X2)
 
     def chains_solve(self, Z0, kind=CHAIN_PLAIN, param_index=0, step=1.0, step_min=1e-12, goal=None, params=None,

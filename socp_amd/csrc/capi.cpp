@@ -153,6 +153,86 @@ bool has_var(const socp_ctx *c) { return c->vt->var_traj && c->vt->var_jacobian 
 
 double fd_eps(double epsfcn) { return std::sqrt(epsfcn > DBL_EPSILON ? epsfcn : DBL_EPSILON); }
 
+// ---- staging of the host-pointer entry points: copies travel on the context's stream, the entry point synchronises once at its end
+template <class T> hipError_t copy_up(socp_ctx *c, T *dev, const T *host, size_t count)
+{
+    return hipMemcpyAsync(dev, host, sizeof(T) * count, hipMemcpyHostToDevice, c->stream);
+}
+
+template <class T> hipError_t copy_down(socp_ctx *c, T *host, const T *dev, size_t count)
+{
+    return hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, c->stream);
+}
+
+// reserve `buf` for `room` elements of T and copy the first `count` of them up; dev: the buffer
+template <class T> hipError_t stage_up(socp_ctx *c, DevBuf &buf, const T *host, size_t count, T *&dev, size_t room = 0)
+{
+    const hipError_t e = buf.reserve(sizeof(T) * (room > count ? room : count));
+    if (e != hipSuccess) return e;
+    dev = buf.as<T>();
+    return copy_up(c, dev, host, count);
+}
+
+// ---- refusals the batched entry points over the shooting problem share; every refusal comes before anything is counted, reserved
+// or enqueued: an error leaves the context as it was.  args_head first, args_tail behind the entry point's own checks.
+int args_head(socp_ctx *c, const std::string &who, bool sizes_ok, const char *sizes)
+{
+    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, who + ": no problem set");
+    if (!sizes_ok) return fail(c, SOCP_ERR_ARG, who + ": " + sizes);
+    return SOCP_OK;
+}
+
+// entry: what the launch table must hold; fixed_only: null, or what the entry does along the fixed-step integrator only
+int args_tail(socp_ctx *c, const std::string &who, bool has_entry, const char *entry, const char *fixed_only)
+{
+    if (!has_entry) return fail(c, SOCP_ERR_UNSUPPORTED, who + ": this model's launch table has no " + entry);
+    if (fixed_only && c->P.integrator == SOCP_INT_DOPRI5)
+        return fail(c, SOCP_ERR_UNSUPPORTED, who + ": " + fixed_only + " the fixed-step integrator only (this context is set to SOCP_INT_DOPRI5)");
+    return SOCP_OK;
+}
+
+// ---- the blocks path: what the six _blocks entry points do with the caller's per-row blocks ("Per-row blocks")
+// before anything is sized or copied from the blocks: a wrong stride would read past the caller's array
+int blocks_stride(socp_ctx *c, const char *what, const double *params, int stride)
+{
+    if (params && stride != c->nparams + 2)
+        return fail(c, SOCP_ERR_ARG, std::string(what) + " must be nparams + 2 (parameters, then two switching times)");
+    return SOCP_OK;
+}
+
+// the blocks staged through s_aux and put in force
+int stage_blocks(socp_ctx *c, int B, const double *params, int pstride, const double *time, const double *xnode)
+{
+    const size_t nodes = (size_t)c->M + 1;
+    const size_t nP = params ? (size_t)B * pstride : 0, nT = time ? B * nodes : 0, nX = xnode ? B * nodes * c->S : 0;
+    HIP_TRY(c, c->s_aux.reserve(sizeof(double) * (nP + nT + nX) + 64));
+    double *dP = c->s_aux.as<double>(), *dT = dP + nP, *dX = dT + nT;
+    if (nP) HIP_TRY(c, copy_up(c, dP, params, nP));
+    if (nT) HIP_TRY(c, copy_up(c, dT, time, nT));
+    if (nX) HIP_TRY(c, copy_up(c, dX, xnode, nX));
+    return socp_problem_set_blocks_dev(c, params ? dP : nullptr, pstride, time ? dT : nullptr, xnode ? dX : nullptr);
+}
+
+// the context's own blocks, saved here and back in force when the scope is left, by whatever return
+struct BlocksGuard {
+    socp_ctx *c;
+    const ProblemDev saved;
+    explicit BlocksGuard(socp_ctx *ctx) : c(ctx), saved(ctx->pb) {}
+    ~BlocksGuard() { c->pb = saved; }
+    BlocksGuard(const BlocksGuard &) = delete;
+    BlocksGuard &operator=(const BlocksGuard &) = delete;
+};
+
+// `call` (the entry point's other form) with the caller's blocks in force; for a batch that is not empty and already checked
+template <class Call>
+int with_blocks(socp_ctx *c, int B, const double *params, int pstride, const double *time, const double *xnode, Call call)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    BlocksGuard guard(c);
+    const int rc = stage_blocks(c, B, params, pstride, time, xnode);
+    return rc == SOCP_OK ? call() : rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -478,25 +558,16 @@ int socp_integrate_batch(socp_ctx *c, int B, const double *t0, const double *tf,
     if (B < 0 || (B > 0 && (!t0 || !tf || !X0 || !Xf))) return fail(c, SOCP_ERR_ARG, "integrate_batch: null argument");
     if (B == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t len = is_jac ? (size_t)(c->S + 1) * c->S : (size_t)c->S;
-    const size_t nb = sizeof(double) * len * B;
-    HIP_TRY(c, c->s_t0.reserve(sizeof(double) * B));
-    HIP_TRY(c, c->s_tf.reserve(sizeof(double) * B));
-    HIP_TRY(c, c->s_in.reserve(nb));
-    HIP_TRY(c, c->s_out.reserve(nb));
-    HIP_TRY(c, hipMemcpyAsync(c->s_t0.p, t0, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->s_tf.p, tf, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, X0, nb, hipMemcpyHostToDevice, c->stream));
-    const double *dsw = nullptr;
-    if (sw) {
-        HIP_TRY(c, c->s_sw.reserve(sizeof(double) * 2 * B));
-        HIP_TRY(c, hipMemcpyAsync(c->s_sw.p, sw, sizeof(double) * 2 * B, hipMemcpyHostToDevice, c->stream));
-        dsw = c->s_sw.as<double>();
-    }
-    int rc = socp_integrate_batch_dev(c, B, c->s_t0.as<double>(), c->s_tf.as<double>(), dsw,
-                                      c->s_in.as<double>(), c->s_out.as<double>(), is_jac);
+    const size_t nX = (is_jac ? (size_t)(c->S + 1) * c->S : (size_t)c->S) * B;
+    double *d_t0, *d_tf, *d_X0, *d_sw = nullptr;
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * nX));
+    HIP_TRY(c, stage_up(c, c->s_t0, t0, B, d_t0));
+    HIP_TRY(c, stage_up(c, c->s_tf, tf, B, d_tf));
+    HIP_TRY(c, stage_up(c, c->s_in, X0, nX, d_X0));
+    if (sw) HIP_TRY(c, stage_up(c, c->s_sw, sw, (size_t)2 * B, d_sw));
+    int rc = socp_integrate_batch_dev(c, B, d_t0, d_tf, d_sw, d_X0, c->s_out.as<double>(), is_jac);
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(Xf, c->s_out.p, nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, Xf, c->s_out.as<double>(), nX));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -554,23 +625,17 @@ int socp_eval_batch(socp_ctx *c, int what, int B, const double *t, const double 
         // a longer (augmented) vector may be passed for Control / Hamiltonian: only the state part is read
         return fail(c, SOCP_ERR_ARG, "eval_batch: pass the 2*dim state part for is_jac=0 evaluations");
     }
-    HIP_TRY(c, c->s_t0.reserve(sizeof(double) * B));
-    HIP_TRY(c, c->s_in.reserve(sizeof(double) * (size_t)B * len));
+    double *d_t, *d_X, *d_sw = nullptr, *d_out;
     HIP_TRY(c, c->s_out.reserve(sizeof(double) * (size_t)B * out_len));
-    HIP_TRY(c, hipMemcpyAsync(c->s_t0.p, t, sizeof(double) * B, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, X, sizeof(double) * (size_t)B * len, hipMemcpyHostToDevice, c->stream));
-    const double *dsw = nullptr;
-    if (sw) {
-        HIP_TRY(c, c->s_sw.reserve(sizeof(double) * 2 * B));
-        HIP_TRY(c, hipMemcpyAsync(c->s_sw.p, sw, sizeof(double) * 2 * B, hipMemcpyHostToDevice, c->stream));
-        dsw = c->s_sw.as<double>();
-    }
+    d_out = c->s_out.as<double>();
+    HIP_TRY(c, stage_up(c, c->s_t0, t, B, d_t));
+    HIP_TRY(c, stage_up(c, c->s_in, X, (size_t)B * len, d_X));
+    if (sw) HIP_TRY(c, stage_up(c, c->s_sw, sw, (size_t)2 * B, d_sw));
     c->n_launch += 1;
-    hipError_t e = var
-        ? c->vt->var_eval(c->stream, c->P, what == SOCP_EVAL_RHS ? 0 : 1, B, c->s_t0.as<double>(), c->s_in.as<double>(), len, c->s_out.as<double>())
-        : table_of(c)->eval(c->stream, c->P, what, B, c->s_t0.as<double>(), dsw, c->s_in.as<double>(), c->s_out.as<double>());
+    hipError_t e = var ? c->vt->var_eval(c->stream, c->P, what == SOCP_EVAL_RHS ? 0 : 1, B, d_t, d_X, len, d_out)
+                       : table_of(c)->eval(c->stream, c->P, what, B, d_t, d_sw, d_X, d_out);
     HIP_TRY(c, e);
-    HIP_TRY(c, hipMemcpyAsync(out, c->s_out.p, sizeof(double) * (size_t)B * out_len, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, out, d_out, (size_t)B * out_len));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -695,9 +760,8 @@ int socp_problem_set_blocks_dev(socp_ctx *c, const double *d_params, int stride,
 {
     if (!c) return SOCP_ERR_ARG;
     if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "problem_set_blocks: no problem set");
-    if (d_params && stride != c->nparams + 2)
-        return fail(c, SOCP_ERR_ARG, "problem_set_blocks: stride must be nparams + 2 (parameters, then two switching times)");
-    if (d_params && c->nparams + 2 > kMaxParams + 2) return fail(c, SOCP_ERR_ARG, "problem_set_blocks: too many parameters");
+    if (const int rc = blocks_stride(c, "problem_set_blocks: stride", d_params, stride)) return rc;
+    if (d_params && c->nparams > kMaxParams) return fail(c, SOCP_ERR_ARG, "problem_set_blocks: too many parameters");
     c->pb.pp_params = d_params;
     c->pb.pp_stride = d_params ? stride : 0;
     c->pb.pp_time = d_time;
@@ -721,25 +785,9 @@ int socp_residual_batch_blocks(socp_ctx *c, int B, const double *Z, const double
     if (!c) return SOCP_ERR_ARG;
     if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "residual_batch_blocks: no problem set");
     if (B < 0 || (B > 0 && (!Z || !F))) return fail(c, SOCP_ERR_ARG, "residual_batch_blocks: null argument");
-    // before anything is sized or copied from it: a wrong stride would read past the caller's array
-    if (params && stride != c->nparams + 2)
-        return fail(c, SOCP_ERR_ARG, "residual_batch_blocks: stride must be nparams + 2 (parameters, then two switching times)");
+    if (const int rc = blocks_stride(c, "residual_batch_blocks: stride", params, stride)) return rc;
     if (B == 0) return SOCP_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t nodes = (size_t)c->M + 1;
-    const size_t nbP = params ? sizeof(double) * (size_t)B * stride : 0, nbT = time ? sizeof(double) * B * nodes : 0,
-                 nbX = xnode ? sizeof(double) * B * nodes * c->S : 0;
-    HIP_TRY(c, c->s_aux.reserve(nbP + nbT + nbX + 64));
-    char *base = c->s_aux.as<char>();
-    double *dP = reinterpret_cast<double *>(base), *dT = reinterpret_cast<double *>(base + nbP), *dX = reinterpret_cast<double *>(base + nbP + nbT);
-    if (params) HIP_TRY(c, hipMemcpyAsync(dP, params, nbP, hipMemcpyHostToDevice, c->stream));
-    if (time) HIP_TRY(c, hipMemcpyAsync(dT, time, nbT, hipMemcpyHostToDevice, c->stream));
-    if (xnode) HIP_TRY(c, hipMemcpyAsync(dX, xnode, nbX, hipMemcpyHostToDevice, c->stream));
-    const ProblemDev saved = c->pb;
-    int rc = socp_problem_set_blocks_dev(c, params ? dP : nullptr, stride, time ? dT : nullptr, xnode ? dX : nullptr);
-    if (rc == SOCP_OK) rc = socp_residual_batch(c, B, Z, F);
-    c->pb = saved;
-    return rc;
+    return with_blocks(c, B, params, stride, time, xnode, [&] { return socp_residual_batch(c, B, Z, F); });
 }
 
 int socp_problem_num_nodes(const socp_ctx *c) { return (c && c->has_problem) ? c->M + 1 : SOCP_ERR_ARG; }
@@ -779,13 +827,13 @@ int socp_residual_batch(socp_ctx *c, int B, const double *Z, double *F)
     if (B < 0 || (B > 0 && (!Z || !F))) return fail(c, SOCP_ERR_ARG, "residual_batch: null argument");
     if (B == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t nb = sizeof(double) * (size_t)B * c->n;
-    HIP_TRY(c, c->s_in.reserve(nb));
-    HIP_TRY(c, c->s_out.reserve(nb));
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nb, hipMemcpyHostToDevice, c->stream));
-    int rc = socp_residual_batch_dev(c, B, c->s_in.as<double>(), c->s_out.as<double>());
+    const size_t nZ = (size_t)B * c->n;
+    double *d_Z;
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * nZ));
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, d_Z));
+    int rc = socp_residual_batch_dev(c, B, d_Z, c->s_out.as<double>());
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(F, c->s_out.p, nb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, F, c->s_out.as<double>(), nZ));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -795,20 +843,17 @@ int socp_residual_batch(socp_ctx *c, int B, const double *Z, double *F)
 int socp_trace_width(const socp_ctx *c) { return c ? 1 + c->S + c->nu + 1 + 2 : SOCP_ERR_ARG; }
 
 namespace {
-int trace_args(socp_ctx *c, int B, int stride, int cap)
+int trace_args(socp_ctx *c, const char *who, int B, int stride, int cap)
 {
-    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "trace_batch: no problem set");
-    if (B < 0 || stride < 1 || cap < 1) return fail(c, SOCP_ERR_ARG, "trace_batch: B >= 0, stride >= 1 and cap >= 1 are required");
-    if (!(table_of(c)->trace && table_of(c)->trace_fill))
-        return fail(c, SOCP_ERR_UNSUPPORTED, "trace_batch: this model's launch table has no trace entry");
-    return SOCP_OK;
+    if (const int rc = args_head(c, who, B >= 0 && stride >= 1 && cap >= 1, "B >= 0, stride >= 1 and cap >= 1 are required")) return rc;
+    return args_tail(c, who, table_of(c)->trace && table_of(c)->trace_fill, "trace entry", nullptr);
 }
 }  // namespace
 
 int socp_trace_batch_dev(socp_ctx *c, int B, const double *d_Z, int stride, int cap, double *d_rows, int *d_count)
 {
     if (!c) return SOCP_ERR_ARG;
-    const int rc = trace_args(c, B, stride, cap);
+    const int rc = trace_args(c, "trace_batch", B, stride, cap);
     if (rc != SOCP_OK) return rc;
     if (B > 0 && (!d_Z || !d_rows || !d_count)) return fail(c, SOCP_ERR_ARG, "trace_batch: null argument");
     if (B == 0) return SOCP_OK;
@@ -822,24 +867,21 @@ int socp_trace_batch_dev(socp_ctx *c, int B, const double *d_Z, int stride, int 
 int socp_trace_batch(socp_ctx *c, int B, const double *Z, int stride, int cap, double *rows, int *count)
 {
     if (!c) return SOCP_ERR_ARG;
-    const int rc0 = trace_args(c, B, stride, cap);
+    const int rc0 = trace_args(c, "trace_batch", B, stride, cap);
     if (rc0 != SOCP_OK) return rc0;
     if (B > 0 && (!Z || !rows || !count)) return fail(c, SOCP_ERR_ARG, "trace_batch: null argument");
     if (B == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t segs = (size_t)B * c->M;
-    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbC = sizeof(int) * segs,
-                 nbR = sizeof(double) * segs * cap * socp_trace_width(c);
-    HIP_TRY(c, c->s_in.reserve(nbZ));
-    HIP_TRY(c, c->s_out.reserve(nbR));
-    HIP_TRY(c, c->s_var.reserve(nbC));
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nbZ, hipMemcpyHostToDevice, c->stream));
+    const size_t segs = (size_t)B * c->M, nR = segs * cap * socp_trace_width(c);
+    double *d_Z, *d_rows;
+    HIP_TRY(c, c->s_var.reserve(sizeof(int) * segs));
+    HIP_TRY(c, stage_up(c, c->s_in, Z, (size_t)B * c->n, d_Z));
     // the caller's buffers travel both ways: what the kernels leave untouched (rows at or beyond min(count, cap)) comes back as it went
-    HIP_TRY(c, hipMemcpyAsync(c->s_out.p, rows, nbR, hipMemcpyHostToDevice, c->stream));
-    const int rc = socp_trace_batch_dev(c, B, c->s_in.as<double>(), stride, cap, c->s_out.as<double>(), c->s_var.as<int>());
+    HIP_TRY(c, stage_up(c, c->s_out, rows, nR, d_rows));
+    const int rc = socp_trace_batch_dev(c, B, d_Z, stride, cap, d_rows, c->s_var.as<int>());
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(rows, c->s_out.p, nbR, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(count, c->s_var.p, nbC, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, rows, d_rows, nR));
+    HIP_TRY(c, copy_down(c, count, c->s_var.as<int>(), segs));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -848,26 +890,13 @@ int socp_trace_batch_blocks(socp_ctx *c, int B, const double *Z, const double *p
                             const double *xnode, int stride, int cap, double *rows, int *count)
 {
     if (!c) return SOCP_ERR_ARG;
-    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "trace_batch_blocks: no problem set");
-    if (B < 0) return fail(c, SOCP_ERR_ARG, "trace_batch_blocks: B >= 0 is required");
-    // before anything is sized or copied from it: a wrong stride would read past the caller's array
-    if (params && pstride != c->nparams + 2)
-        return fail(c, SOCP_ERR_ARG, "trace_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t nodes = (size_t)c->M + 1;
-    const size_t nbP = params ? sizeof(double) * (size_t)B * pstride : 0, nbT = time ? sizeof(double) * B * nodes : 0,
-                 nbX = xnode ? sizeof(double) * B * nodes * c->S : 0;
-    HIP_TRY(c, c->s_aux.reserve(nbP + nbT + nbX + 64));
-    char *base = c->s_aux.as<char>();
-    double *dP = reinterpret_cast<double *>(base), *dT = reinterpret_cast<double *>(base + nbP), *dX = reinterpret_cast<double *>(base + nbP + nbT);
-    if (nbP) HIP_TRY(c, hipMemcpyAsync(dP, params, nbP, hipMemcpyHostToDevice, c->stream));
-    if (nbT) HIP_TRY(c, hipMemcpyAsync(dT, time, nbT, hipMemcpyHostToDevice, c->stream));
-    if (nbX) HIP_TRY(c, hipMemcpyAsync(dX, xnode, nbX, hipMemcpyHostToDevice, c->stream));
-    const ProblemDev saved = c->pb;
-    int rc = socp_problem_set_blocks_dev(c, params ? dP : nullptr, pstride, time ? dT : nullptr, xnode ? dX : nullptr);
-    if (rc == SOCP_OK) rc = socp_trace_batch(c, B, Z, stride, cap, rows, count);
-    c->pb = saved;
-    return rc;
+    if (const int rc = args_head(c, "trace_batch_blocks", B >= 0, "B >= 0 is required")) return rc;
+    if (const int rc = blocks_stride(c, "trace_batch_blocks: the parameter stride", params, pstride)) return rc;
+    // what the host form refuses, under its name as before: nothing is staged for a call that is refused, or for an empty batch
+    if (const int rc = trace_args(c, "trace_batch", B, stride, cap)) return rc;
+    if (B > 0 && (!Z || !rows || !count)) return fail(c, SOCP_ERR_ARG, "trace_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode, [&] { return socp_trace_batch(c, B, Z, stride, cap, rows, count); });
 }
 
 /* ---- batched cost -------------------------------------------------------------------------- */
@@ -875,25 +904,18 @@ int socp_trace_batch_blocks(socp_ctx *c, int B, const double *Z, const double *p
 int socp_ctx_has_cost(const socp_ctx *c) { return c ? (table_of(c)->cost ? 1 : 0) : SOCP_ERR_ARG; }
 
 namespace {
-// every refusal comes before anything is counted, reserved or enqueued: an error leaves the context as it was
-int cost_args(socp_ctx *c, int B, const void *Z, const void *cost)
+int cost_args(socp_ctx *c, const char *who, int B, const void *Z, const void *cost)
 {
-    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, "cost_batch: no problem set");
-    if (B < 0) return fail(c, SOCP_ERR_ARG, "cost_batch: B >= 0 is required");
-    if (B > 0 && (!Z || !cost)) return fail(c, SOCP_ERR_ARG, "cost_batch: null argument");
-    if (!table_of(c)->cost)
-        return fail(c, SOCP_ERR_UNSUPPORTED, "cost_batch: this model's launch table has no cost entry");
-    if (c->P.integrator == SOCP_INT_DOPRI5)
-        return fail(c, SOCP_ERR_UNSUPPORTED, "cost_batch: the running cost is integrated with the fixed-step integrator only "
-                                             "(this context is set to SOCP_INT_DOPRI5)");
-    return SOCP_OK;
+    if (const int rc = args_head(c, who, B >= 0, "B >= 0 is required")) return rc;
+    if (B > 0 && (!Z || !cost)) return fail(c, SOCP_ERR_ARG, std::string(who) + ": null argument");
+    return args_tail(c, who, table_of(c)->cost != nullptr, "cost entry", "the running cost is integrated with");
 }
 }  // namespace
 
 int socp_cost_batch_dev(socp_ctx *c, int B, const double *d_Z, double *d_cost, double *d_total, double *d_Xend)
 {
     if (!c) return SOCP_ERR_ARG;
-    const int rc = cost_args(c, B, d_Z, d_cost);
+    const int rc = cost_args(c, "cost_batch", B, d_Z, d_cost);
     if (rc != SOCP_OK) return rc;
     if (B == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -906,22 +928,20 @@ int socp_cost_batch_dev(socp_ctx *c, int B, const double *d_Z, double *d_cost, d
 int socp_cost_batch(socp_ctx *c, int B, const double *Z, double *cost, double *total, double *Xend)
 {
     if (!c) return SOCP_ERR_ARG;
-    const int rc0 = cost_args(c, B, Z, cost);
+    const int rc0 = cost_args(c, "cost_batch", B, Z, cost);
     if (rc0 != SOCP_OK) return rc0;
     if (B == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t segs = (size_t)B * c->M;
-    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbC = sizeof(double) * segs, nbT = total ? sizeof(double) * (size_t)B : 0,
-                 nbX = Xend ? sizeof(double) * segs * c->S : 0;
-    HIP_TRY(c, c->s_in.reserve(nbZ));
-    HIP_TRY(c, c->s_out.reserve(nbC + nbT + nbX));
-    double *dC = c->s_out.as<double>(), *dT = dC + segs, *dX = dT + (total ? B : 0);
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nbZ, hipMemcpyHostToDevice, c->stream));
-    const int rc = socp_cost_batch_dev(c, B, c->s_in.as<double>(), dC, total ? dT : nullptr, Xend ? dX : nullptr);
+    const size_t segs = (size_t)B * c->M, nT = total ? (size_t)B : 0, nX = Xend ? segs * c->S : 0;
+    double *d_Z;
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (segs + nT + nX)));
+    double *dC = c->s_out.as<double>(), *dT = dC + segs, *dX = dT + nT;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, (size_t)B * c->n, d_Z));
+    const int rc = socp_cost_batch_dev(c, B, d_Z, dC, total ? dT : nullptr, Xend ? dX : nullptr);
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(cost, dC, nbC, hipMemcpyDeviceToHost, c->stream));
-    if (total) HIP_TRY(c, hipMemcpyAsync(total, dT, nbT, hipMemcpyDeviceToHost, c->stream));
-    if (Xend) HIP_TRY(c, hipMemcpyAsync(Xend, dX, nbX, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, cost, dC, segs));
+    if (total) HIP_TRY(c, copy_down(c, total, dT, nT));
+    if (Xend) HIP_TRY(c, copy_down(c, Xend, dX, nX));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -930,61 +950,25 @@ int socp_cost_batch_blocks(socp_ctx *c, int B, const double *Z, const double *pa
                            const double *xnode, double *cost, double *total, double *Xend)
 {
     if (!c) return SOCP_ERR_ARG;
-    const int rc0 = cost_args(c, B, Z, cost);
-    if (rc0 != SOCP_OK) return rc0;
-    // before anything is sized or copied from it: a wrong stride would read past the caller's array
-    if (params && pstride != c->nparams + 2)
-        return fail(c, SOCP_ERR_ARG, "cost_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    if (const int rc = cost_args(c, "cost_batch", B, Z, cost)) return rc;          // under the host form's name, as before
+    if (const int rc = blocks_stride(c, "cost_batch_blocks: the parameter stride", params, pstride)) return rc;
     if (B == 0) return SOCP_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t nodes = (size_t)c->M + 1;
-    const size_t nbP = params ? sizeof(double) * (size_t)B * pstride : 0, nbT = time ? sizeof(double) * B * nodes : 0,
-                 nbX = xnode ? sizeof(double) * B * nodes * c->S : 0;
-    HIP_TRY(c, c->s_aux.reserve(nbP + nbT + nbX + 64));
-    char *base = c->s_aux.as<char>();
-    double *dP = reinterpret_cast<double *>(base), *dT = reinterpret_cast<double *>(base + nbP), *dX = reinterpret_cast<double *>(base + nbP + nbT);
-    if (nbP) HIP_TRY(c, hipMemcpyAsync(dP, params, nbP, hipMemcpyHostToDevice, c->stream));
-    if (nbT) HIP_TRY(c, hipMemcpyAsync(dT, time, nbT, hipMemcpyHostToDevice, c->stream));
-    if (nbX) HIP_TRY(c, hipMemcpyAsync(dX, xnode, nbX, hipMemcpyHostToDevice, c->stream));
-    const ProblemDev saved = c->pb;
-    int rc = socp_problem_set_blocks_dev(c, params ? dP : nullptr, pstride, time ? dT : nullptr, xnode ? dX : nullptr);
-    if (rc == SOCP_OK) rc = socp_cost_batch(c, B, Z, cost, total, Xend);
-    c->pb = saved;
-    return rc;
+    return with_blocks(c, B, params, pstride, time, xnode, [&] { return socp_cost_batch(c, B, Z, cost, total, Xend); });
 }
 
 /* ---- batched Move(tf) / re-grid ------------------------------------------------------------- */
 
 namespace {
-// every refusal comes before anything is counted, reserved or enqueued: an error leaves the context as it was
 int move_args(socp_ctx *c, const char *who, int B, int K)
 {
-    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, std::string(who) + ": no problem set");
-    if (B < 0 || K < 0) return fail(c, SOCP_ERR_ARG, std::string(who) + ": B >= 0 and K >= 0 are required");
-    if (!table_of(c)->move)
-        return fail(c, SOCP_ERR_UNSUPPORTED, std::string(who) + ": this model's launch table has no move entry");
-    return SOCP_OK;
+    if (const int rc = args_head(c, who, B >= 0 && K >= 0, "B >= 0 and K >= 0 are required")) return rc;
+    return args_tail(c, who, table_of(c)->move != nullptr, "move entry", nullptr);
 }
 
 hipError_t run_move(socp_ctx *c, int B, const double *d_Z, int K, const double *d_tq, double *d_Xq, double *d_tout)
 {
     c->n_traj += (long long)B * K; c->n_launch += 1;
     return table_of(c)->move(c->stream, c->P, c->pb, B, d_Z, K, d_tq, d_Xq, d_tout);
-}
-
-// per-row blocks of a _blocks entry point: staged through s_aux and put in force; the caller saves and restores c->pb
-int stage_blocks(socp_ctx *c, int B, const double *params, int pstride, const double *time, const double *xnode)
-{
-    const size_t nodes = (size_t)c->M + 1;
-    const size_t nbP = params ? sizeof(double) * (size_t)B * pstride : 0, nbT = time ? sizeof(double) * B * nodes : 0,
-                 nbX = xnode ? sizeof(double) * B * nodes * c->S : 0;
-    HIP_TRY(c, c->s_aux.reserve(nbP + nbT + nbX + 64));
-    char *base = c->s_aux.as<char>();
-    double *dP = reinterpret_cast<double *>(base), *dT = reinterpret_cast<double *>(base + nbP), *dX = reinterpret_cast<double *>(base + nbP + nbT);
-    if (nbP) HIP_TRY(c, hipMemcpyAsync(dP, params, nbP, hipMemcpyHostToDevice, c->stream));
-    if (nbT) HIP_TRY(c, hipMemcpyAsync(dT, time, nbT, hipMemcpyHostToDevice, c->stream));
-    if (nbX) HIP_TRY(c, hipMemcpyAsync(dX, xnode, nbX, hipMemcpyHostToDevice, c->stream));
-    return socp_problem_set_blocks_dev(c, params ? dP : nullptr, pstride, time ? dT : nullptr, xnode ? dX : nullptr);
 }
 
 // the target structure of a re-grid: n2 = S M2 + #FREE, the FREE-node bit words; SOCP_ERR_ARG for what the entry points refuse
@@ -1032,18 +1016,16 @@ int socp_move_batch(socp_ctx *c, int B, const double *Z, int K, const double *tq
     if (B == 0 || K == 0) return SOCP_OK;
     if (!Z || !tq || !Xq) return fail(c, SOCP_ERR_ARG, "move_batch: null argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t lanes = (size_t)B * K;
-    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbQ = sizeof(double) * lanes, nbX = sizeof(double) * lanes * c->S;
-    HIP_TRY(c, c->s_in.reserve(nbZ));
-    HIP_TRY(c, c->s_t0.reserve(nbQ));
-    HIP_TRY(c, c->s_out.reserve(nbX + nbQ));
-    double *dX = c->s_out.as<double>(), *dT = dX + lanes * c->S;
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nbZ, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->s_t0.p, tq, nbQ, hipMemcpyHostToDevice, c->stream));
-    const int rc = socp_move_batch_dev(c, B, c->s_in.as<double>(), K, c->s_t0.as<double>(), dX, tout ? dT : nullptr);
+    const size_t lanes = (size_t)B * K, nX = lanes * c->S;
+    double *d_Z, *d_tq;
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (nX + lanes)));
+    double *dX = c->s_out.as<double>(), *dT = dX + nX;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, (size_t)B * c->n, d_Z));
+    HIP_TRY(c, stage_up(c, c->s_t0, tq, lanes, d_tq));
+    const int rc = socp_move_batch_dev(c, B, d_Z, K, d_tq, dX, tout ? dT : nullptr);
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(Xq, dX, nbX, hipMemcpyDeviceToHost, c->stream));
-    if (tout) HIP_TRY(c, hipMemcpyAsync(tout, dT, nbQ, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, Xq, dX, nX));
+    if (tout) HIP_TRY(c, copy_down(c, tout, dT, lanes));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -1054,17 +1036,10 @@ int socp_move_batch_blocks(socp_ctx *c, int B, const double *Z, const double *pa
     if (!c) return SOCP_ERR_ARG;
     const int rc0 = move_args(c, "move_batch_blocks", B, K);
     if (rc0 != SOCP_OK) return rc0;
-    // before anything is sized or copied from it: a wrong stride would read past the caller's array
-    if (params && pstride != c->nparams + 2)
-        return fail(c, SOCP_ERR_ARG, "move_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    if (const int rc = blocks_stride(c, "move_batch_blocks: the parameter stride", params, pstride)) return rc;
     if (B == 0 || K == 0) return SOCP_OK;
     if (!Z || !tq || !Xq) return fail(c, SOCP_ERR_ARG, "move_batch_blocks: null argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const ProblemDev saved = c->pb;
-    int rc = stage_blocks(c, B, params, pstride, time, xnode);
-    if (rc == SOCP_OK) rc = socp_move_batch(c, B, Z, K, tq, Xq, tout);
-    c->pb = saved;
-    return rc;
+    return with_blocks(c, B, params, pstride, time, xnode, [&] { return socp_move_batch(c, B, Z, K, tq, Xq, tout); });
 }
 
 /* ---- batched events ------------------------------------------------------------------------ */
@@ -1072,22 +1047,17 @@ int socp_move_batch_blocks(socp_ctx *c, int B, const double *Z, const double *pa
 int socp_ctx_event_channels(const socp_ctx *c) { return c ? (table_of(c)->events ? table_of(c)->event_channels : 0) : SOCP_ERR_ARG; }
 
 namespace {
-// every refusal comes before anything is counted, reserved or enqueued: an error leaves the context as it was.
 // *chans: the watches' channels, four bits each (a kernel argument: the host array is read here)
 int events_args(socp_ctx *c, const char *who, int B, int E, const int *chan, int refine, int cap, unsigned *chans)
 {
     const std::string w(who);
-    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, w + ": no problem set");
-    if (B < 0) return fail(c, SOCP_ERR_ARG, w + ": B >= 0 is required");
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
     if (E < 1 || E > kMaxEventWatches) return fail(c, SOCP_ERR_ARG, w + ": 1 <= E <= 8 watches are required");
     if (refine < 0 || refine > kMaxEventRefine) return fail(c, SOCP_ERR_ARG, w + ": 0 <= refine <= 8 is required");
     if (cap < 1) return fail(c, SOCP_ERR_ARG, w + ": cap >= 1 is required");
     if (!chan) return fail(c, SOCP_ERR_ARG, w + ": null channel table");
-    if (!table_of(c)->events)
-        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": this model's launch table has no events entry (the model has no event channels)");
-    if (c->P.integrator == SOCP_INT_DOPRI5)
-        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": events are located along the fixed-step integrator only "
-                                                 "(this context is set to SOCP_INT_DOPRI5)");
+    if (const int rc = args_tail(c, w, table_of(c)->events != nullptr, "events entry (the model has no event channels)", "events are located along"))
+        return rc;
     *chans = 0;
     for (int e = 0; e < E; e++) {
         if (chan[e] < 0 || chan[e] >= table_of(c)->event_channels)
@@ -1124,26 +1094,24 @@ int socp_events_batch(socp_ctx *c, int B, const double *Z, int E, const int *cha
     if (B > 0 && (!Z || !levels || !tev || !id || !count)) return fail(c, SOCP_ERR_ARG, "events_batch: null argument");
     if (B == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t segs = (size_t)B * c->M, slots = segs * cap;
-    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbL = sizeof(double) * (size_t)B * E, nbT = sizeof(double) * slots,
-                 nbX = Xev ? sizeof(double) * slots * c->S : 0, nbI = sizeof(int) * slots, nbC = sizeof(int) * segs;
-    HIP_TRY(c, c->s_in.reserve(nbZ + nbL));
-    HIP_TRY(c, c->s_out.reserve(nbT + nbX));
-    HIP_TRY(c, c->s_var.reserve(nbI + nbC));
-    double *dZ = c->s_in.as<double>(), *dL = dZ + (size_t)B * c->n, *dT = c->s_out.as<double>(), *dX = dT + slots;
-    int *dI = c->s_var.as<int>(), *dC = dI + slots;
-    HIP_TRY(c, hipMemcpyAsync(dZ, Z, nbZ, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dL, levels, nbL, hipMemcpyHostToDevice, c->stream));
+    const size_t segs = (size_t)B * c->M, slots = segs * cap, nZ = (size_t)B * c->n, nL = (size_t)B * E, nX = Xev ? slots * c->S : 0;
+    double *dZ, *dT;
+    int *dI;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, dZ, nZ + nL));
+    double *dL = dZ + nZ;
+    HIP_TRY(c, copy_up(c, dL, levels, nL));
     // the caller's buffers travel both ways: what the kernel leaves untouched (rows at or beyond min(count, cap)) comes back as it went
-    HIP_TRY(c, hipMemcpyAsync(dT, tev, nbT, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(dI, id, nbI, hipMemcpyHostToDevice, c->stream));
-    if (Xev) HIP_TRY(c, hipMemcpyAsync(dX, Xev, nbX, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, stage_up(c, c->s_out, tev, slots, dT, slots + nX));
+    HIP_TRY(c, stage_up(c, c->s_var, id, slots, dI, slots + segs));
+    double *dX = dT + slots;
+    int *dC = dI + slots;
+    if (Xev) HIP_TRY(c, copy_up(c, dX, Xev, nX));
     const int rc = socp_events_batch_dev(c, B, dZ, E, chan, dL, refine, cap, dT, dI, dC, Xev ? dX : nullptr);
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(tev, dT, nbT, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(id, dI, nbI, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(count, dC, nbC, hipMemcpyDeviceToHost, c->stream));
-    if (Xev) HIP_TRY(c, hipMemcpyAsync(Xev, dX, nbX, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, tev, dT, slots));
+    HIP_TRY(c, copy_down(c, id, dI, slots));
+    HIP_TRY(c, copy_down(c, count, dC, segs));
+    if (Xev) HIP_TRY(c, copy_down(c, Xev, dX, nX));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -1156,17 +1124,11 @@ int socp_events_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
     unsigned chans = 0;
     const int rc0 = events_args(c, "events_batch_blocks", B, E, chan, refine, cap, &chans);
     if (rc0 != SOCP_OK) return rc0;
-    // before anything is sized or copied from it: a wrong stride would read past the caller's array
-    if (params && pstride != c->nparams + 2)
-        return fail(c, SOCP_ERR_ARG, "events_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    if (const int rc = blocks_stride(c, "events_batch_blocks: the parameter stride", params, pstride)) return rc;
     if (B > 0 && (!Z || !levels || !tev || !id || !count)) return fail(c, SOCP_ERR_ARG, "events_batch_blocks: null argument");
     if (B == 0) return SOCP_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const ProblemDev saved = c->pb;
-    int rc = stage_blocks(c, B, params, pstride, time, xnode);
-    if (rc == SOCP_OK) rc = socp_events_batch(c, B, Z, E, chan, levels, refine, cap, tev, id, count, Xev);
-    c->pb = saved;
-    return rc;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_events_batch(c, B, Z, E, chan, levels, refine, cap, tev, id, count, Xev); });
 }
 
 int socp_regrid_num_param(const socp_ctx *c, int M2, const int *mode_t2)
@@ -1208,27 +1170,22 @@ int socp_regrid_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
     int n2 = 0;
     const int rc0 = regrid_args(c, B, M2, mode_t2, bits, &n2);
     if (rc0 != SOCP_OK) return rc0;
-    if (params && pstride != c->nparams + 2)
-        return fail(c, SOCP_ERR_ARG, "regrid_batch_blocks: the parameter stride must be nparams + 2 (parameters, then two switching times)");
+    if (const int rc = blocks_stride(c, "regrid_batch_blocks: the parameter stride", params, pstride)) return rc;
     if (B == 0) return SOCP_OK;
     if (!Z || !T2 || !Z2) return fail(c, SOCP_ERR_ARG, "regrid_batch_blocks: null argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t nodes2 = (size_t)M2 + 1;
-    const size_t nbZ = sizeof(double) * (size_t)B * c->n, nbT = sizeof(double) * B * nodes2, nbZ2 = sizeof(double) * (size_t)B * n2,
-                 nbX = sizeof(double) * B * nodes2 * c->S;
-    HIP_TRY(c, c->s_in.reserve(nbZ));
-    HIP_TRY(c, c->s_t0.reserve(nbT));
-    HIP_TRY(c, c->s_out.reserve(nbZ2 + nbX));
-    double *dZ2 = c->s_out.as<double>(), *dX = dZ2 + (size_t)B * n2;
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, nbZ, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->s_t0.p, T2, nbT, hipMemcpyHostToDevice, c->stream));
-    const ProblemDev saved = c->pb;
-    int rc = stage_blocks(c, B, params, pstride, time, xnode);
-    if (rc == SOCP_OK) rc = socp_regrid_batch_dev(c, B, c->s_in.as<double>(), M2, mode_t2, c->s_t0.as<double>(), dZ2, xnode2 ? dX : nullptr);
-    c->pb = saved;
+    const size_t nT = (size_t)B * (M2 + 1), nZ2 = (size_t)B * n2, nX = nT * c->S;
+    double *d_Z, *d_T2;
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (nZ2 + nX)));
+    double *dZ2 = c->s_out.as<double>(), *dX = dZ2 + nZ2;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, (size_t)B * c->n, d_Z));
+    HIP_TRY(c, stage_up(c, c->s_t0, T2, nT, d_T2));
+    // (the device form's workspace is s_var: the blocks in s_aux stay clear of it)
+    const int rc = with_blocks(c, B, params, pstride, time, xnode,
+                               [&] { return socp_regrid_batch_dev(c, B, d_Z, M2, mode_t2, d_T2, dZ2, xnode2 ? dX : nullptr); });
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(Z2, dZ2, nbZ2, hipMemcpyDeviceToHost, c->stream));
-    if (xnode2) HIP_TRY(c, hipMemcpyAsync(xnode2, dX, nbX, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, Z2, dZ2, nZ2));
+    if (xnode2) HIP_TRY(c, copy_down(c, xnode2, dX, nX));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -1286,13 +1243,13 @@ int socp_fd_rows(socp_ctx *c, int np, const double *Z, double epsfcn, double *Ro
     if (np < 0 || (np > 0 && (!Z || !Rows))) return fail(c, SOCP_ERR_ARG, "fd_rows: null argument");
     if (np == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = c->n;
-    HIP_TRY(c, c->s_in.reserve(sizeof(double) * n * np));
-    HIP_TRY(c, c->s_out.reserve(sizeof(double) * n * (n + 1) * np));
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, Z, sizeof(double) * n * np, hipMemcpyHostToDevice, c->stream));
-    int rc = socp_fd_rows_dev(c, np, c->s_in.as<double>(), epsfcn, c->s_out.as<double>());
+    const size_t n = c->n, nR = n * (n + 1) * np;
+    double *d_Z;
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * nR));
+    HIP_TRY(c, stage_up(c, c->s_in, Z, n * np, d_Z));
+    int rc = socp_fd_rows_dev(c, np, d_Z, epsfcn, c->s_out.as<double>());
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(Rows, c->s_out.p, sizeof(double) * n * (n + 1) * np, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, Rows, c->s_out.as<double>(), nR));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -1304,14 +1261,13 @@ int socp_fd_jacobian(socp_ctx *c, const double *z, const double *fvec, double ep
     if (!z || !fvec || !fjac) return fail(c, SOCP_ERR_ARG, "fd_jacobian: null argument");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = c->n;
-    HIP_TRY(c, c->s_in.reserve(sizeof(double) * n));
-    HIP_TRY(c, c->s_aux.reserve(sizeof(double) * n));
+    double *d_z, *d_fvec;
     HIP_TRY(c, c->s_out.reserve(sizeof(double) * n * n));
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, z, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->s_aux.p, fvec, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    int rc = socp_fd_jacobian_dev(c, c->s_in.as<double>(), c->s_aux.as<double>(), epsfcn, c->s_out.as<double>(), dedup);
+    HIP_TRY(c, stage_up(c, c->s_in, z, n, d_z));
+    HIP_TRY(c, stage_up(c, c->s_aux, fvec, n, d_fvec));
+    int rc = socp_fd_jacobian_dev(c, d_z, d_fvec, epsfcn, c->s_out.as<double>(), dedup);
     if (rc != SOCP_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(fjac, c->s_out.p, sizeof(double) * n * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, copy_down(c, fjac, c->s_out.as<double>(), n * n));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }
@@ -1364,11 +1320,11 @@ int socp_var_jacobian(socp_ctx *c, const double *z, double *fjac)
     if (!z || !fjac) return fail(c, SOCP_ERR_ARG, "var_jacobian: null argument");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = c->n;
-    HIP_TRY(c, c->s_in.reserve(sizeof(double) * n));
+    double *d_z;
     HIP_TRY(c, c->s_out.reserve(sizeof(double) * n * n));
-    HIP_TRY(c, hipMemcpyAsync(c->s_in.p, z, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    if (int rc = socp_var_jacobian_multi_dev(c, 1, c->s_in.as<double>(), c->s_out.as<double>())) return rc;
-    HIP_TRY(c, hipMemcpyAsync(fjac, c->s_out.p, sizeof(double) * n * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, stage_up(c, c->s_in, z, n, d_z));
+    if (int rc = socp_var_jacobian_multi_dev(c, 1, d_z, c->s_out.as<double>())) return rc;
+    HIP_TRY(c, copy_down(c, fjac, c->s_out.as<double>(), n * n));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
 }

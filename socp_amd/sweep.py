@@ -277,17 +277,23 @@ def warm_up(ctx, args, solve_first):
     return ctx.counters()[0]
 
 
+def converged_rows(local, lo, rank, params, out):
+    """What the *_local functions below start from: the positions of this rank's CONVERGED chains in its block, their unknown vectors,
+    their parameter blocks (None when the chains have none), their index in the sweep's start table, and the file OUT.rank<r>.npz."""
+    conv = np.where(np.asarray(local["info"]) == 1)[0]
+    return conv, np.asarray(local["z"])[conv], None if params is None else np.asarray(params)[conv], lo + conv, "%s.rank%d.npz" % (out, rank)
+
+
 def trace_local(ctx, args, local, lo, rank, params=None):
     """--trace-stride / --trace-out: the sampled trajectories (socp_trace_batch) of this rank's CONVERGED chains, each with its own
     parameter block when the chains have one, written to PATH.rank<r>.npz: rows [k][M][cap][W] (t, X, u, H, aux0, aux1),
     count [k][M], index [k] = position of the chain in the sweep's start table.  Runs after the timed solve; trajectories stay on
     the rank that solved them (a 4096-start sweep at stride 100 is 70 MB).  Returns the record entry of this rank."""
-    conv = np.where(np.asarray(local["info"]) == 1)[0]
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.trace_out)
     t0 = time.perf_counter()
-    rows, count = ctx.trace_batch(np.asarray(local["z"])[conv], stride=args.trace_stride, params=None if params is None else params[conv])
+    rows, count = ctx.trace_batch(z, stride=args.trace_stride, params=own)
     wall = time.perf_counter() - t0
-    path = "%s.rank%d.npz" % (args.trace_out, rank)
-    np.savez(path, rows=rows, count=count, index=lo + conv)
+    np.savez(path, rows=rows, count=count, index=index)
     return {"stride": args.trace_stride, "chains": int(len(conv)), "rows_per_segment_max": int(count.max()) if len(conv) else 0,
             "wall_s": wall, "file": path}
 
@@ -297,17 +303,15 @@ def cost_local(ctx, args, local, lo, rank, params=None):
     when the chains have one, written to PATH.rank<r>.npz: cost [k][M] per segment, total [k], index [k] = position of the chain
     in the sweep's start table, z [k][n] = the unknown vectors costed.  Runs after the timed solve.  Returns the record entry of
     this rank: what ranks the extremals the sweep found."""
-    conv = np.where(np.asarray(local["info"]) == 1)[0]
-    z = np.asarray(local["z"])[conv]
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.cost_out)
     t0 = time.perf_counter()
-    r = ctx.cost_batch(z, params=None if params is None else params[conv])
+    r = ctx.cost_batch(z, params=own)
     wall = time.perf_counter() - t0
-    path = "%s.rank%d.npz" % (args.cost_out, rank)
     total = r["total"]
-    np.savez(path, cost=r["cost"], total=total, index=lo + conv, z=z)
+    np.savez(path, cost=r["cost"], total=total, index=index, z=z)
     some = len(conv) > 0
     return {"chains": int(len(conv)), "min": float(total.min()) if some else None, "median": float(np.median(total)) if some else None,
-            "max": float(total.max()) if some else None, "best_index": int(lo + conv[int(np.argmin(total))]) if some else None,
+            "max": float(total.max()) if some else None, "best_index": int(index[int(np.argmin(total))]) if some else None,
             "wall_s": wall, "file": path}
 
 
@@ -320,15 +324,13 @@ def events_local(ctx, args, local, lo, rank, params=None):
     table.  Runs after the timed solve.  Returns the record entry of this rank, with the number of chains per event signature
     (the ids of a chain in time order): a measuring instrument for structure, not a structure guess for a next stage."""
     from . import capi
-    conv = np.where(np.asarray(local["info"]) == 1)[0]
-    z = np.asarray(local["z"])[conv]
-    own = np.tile(np.asarray(ctx.get_params()), (len(conv), 1)) if params is None else np.asarray(params)[conv]
-    levels = np.stack([-2.0 * own[:, 6] * own[:, 4], np.zeros(len(conv))], axis=1)
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.events_out)
+    held = np.tile(np.asarray(ctx.get_params()), (len(conv), 1)) if own is None else own
+    levels = np.stack([-2.0 * held[:, 6] * held[:, 4], np.zeros(len(conv))], axis=1)
     t0 = time.perf_counter()
-    t, ident, count = ctx.events_batch(z, [0, 0], levels, refine=args.events_refine, params=None if params is None else params[conv])
+    t, ident, count = ctx.events_batch(z, [0, 0], levels, refine=args.events_refine, params=own)
     wall = time.perf_counter() - t0
-    path = "%s.rank%d.npz" % (args.events_out, rank)
-    np.savez(path, index=lo + conv, t=t, id=ident, count=count)
+    np.savez(path, index=index, t=t, id=ident, count=count)
     signatures = {}
     for _times, ids in capi.merge_events(t, ident, count):
         key = ",".join("%+d" % i for i in ids)
@@ -351,18 +353,16 @@ def regrid_local(ctx, args, local, lo, rank, params=None):
     block when the chains have one), written to PATH.rank<r>.npz: z [k][n2] = the unknown vectors of the new structure, time [k][M2+1]
     and xnode [k][M2+1][14] = its boundary blocks, index [k] = position of the chain in the sweep's start table, source [k][n] = the
     solutions moved.  Runs after the timed solve.  Returns the record entry of this rank."""
-    conv = np.where(np.asarray(local["info"]) == 1)[0]
-    z = np.asarray(local["z"])[conv]
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.regrid_out)
     M2 = args.regrid_segments
     T2 = np.empty((len(conv), M2 + 1))
     for k, zk in enumerate(z):
         tl = ctx.timeline(zk)
         T2[k] = np.linspace(tl[0], tl[-1], M2 + 1)
     t0 = time.perf_counter()
-    r = ctx.regrid_batch(z, regrid_structure(args), T2, params=None if params is None else params[conv])
+    r = ctx.regrid_batch(z, regrid_structure(args), T2, params=own)
     seconds = time.perf_counter() - t0
-    path = "%s.rank%d.npz" % (args.regrid_out, rank)
-    np.savez(path, index=lo + conv, z=r["z"], time=r["time"], xnode=r["xnode"], source=z)
+    np.savez(path, index=index, z=r["z"], time=r["time"], xnode=r["xnode"], source=z)
     return {"count": int(len(conv)), "n2": int(r["z"].shape[1]), "seconds": seconds}
 
 
@@ -563,29 +563,17 @@ def main():
     if world > 1:
         dist.all_reduce(traj)
     extra = {}
+    blocks = None
+    if chain_kw is not None:                            # for the four below: every chain at the KD it reached, then the context's two switching times
+        blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
+        blocks[:, 2] = local["param_final"]
     if args.trace_out:
-        blocks = None
-        if chain_kw is not None:                        # every chain at the KD it reached, then the context's two switching times
-            blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
-            blocks[:, 2] = local["param_final"]
-        extra = {"trace_rank%d" % rank: trace_local(ctx, args, local, lo_w, rank, blocks)}
+        extra["trace_rank%d" % rank] = trace_local(ctx, args, local, lo_w, rank, blocks)
     if args.cost_out:
-        blocks = None
-        if chain_kw is not None:                        # as for the trace: every chain at the KD it reached
-            blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
-            blocks[:, 2] = local["param_final"]
         extra["cost_rank%d" % rank] = cost_local(ctx, args, local, lo_w, rank, blocks)
     if args.regrid_out:
-        blocks = None
-        if chain_kw is not None:                        # as for the trace: every chain at the KD it reached
-            blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
-            blocks[:, 2] = local["param_final"]
         extra["regrid_rank%d" % rank] = regrid_local(ctx, args, local, lo_w, rank, blocks)
     if args.events_out:
-        blocks = None
-        if chain_kw is not None:                        # as for the trace: every chain at the KD it reached
-            blocks = np.concatenate([params[lo_w:hi_w], np.zeros((hi_w - lo_w, 2))], axis=1)
-            blocks[:, 2] = local["param_final"]
         extra["events_rank%d" % rank] = events_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)

@@ -9,8 +9,9 @@ line (profiles/launch_tables_census.txt).  No test can see which Goddard control
 agree in every bit there -- so the choice is compared launch by launch.
 
 Goddard, the C1 problem of tests/test_gpu_cost_batch.py (B = 3, 4 steps): integrate_batch, eval_batch (all three quantities),
-integrate_dense, residual_batch, fd_jacobian, fd_rows, trace_batch, cost_batch, move_batch -- with mu2 = 0 and mu2 = 1, both variants,
-both integrators (the cost has the fixed-step one only), without per-problem blocks and with them: socp_problem_blocks_all_smooth 0
+integrate_dense, residual_batch, fd_jacobian, fd_rows, trace_batch, cost_batch, move_batch, events_batch, regrid_batch (onto two
+segments) -- with mu2 = 0 and mu2 = 1, both variants, both integrators (the cost and the events have the fixed-step one only), without
+per-problem blocks and with them (so all six _blocks entry points run both ways): socp_problem_blocks_all_smooth 0
 (the blocks carry the context's mu2) and 1 (the blocks carry mu2 = 1 whatever the context holds, so the promise is true).  Then
 the same calls once per variant for the double integrator (and var_jacobian) and for covid19."""
 import argparse
@@ -35,9 +36,11 @@ def names(trace_dir):
         print("grid %5d  %s" % (grid, name))
 
 
-def problem_calls(ctx, Z, blocks, cost=True):
-    """Every entry point that reads the shooting problem; blocks: None or (params, time, xnode), one row per row of Z."""
+def problem_calls(ctx, Z, blocks, fixed=True):
+    """Every entry point that reads the shooting problem; blocks: None or (params, time, xnode), one row per row of Z; fixed: the
+    context integrates with fixed steps (the cost and the events have that integrator only)."""
     import torch
+    from socp_amd import capi
     kw = dict(zip(("params", "time", "xnode"), blocks)) if blocks else {}
     F = ctx.residual_batch_blocks(Z, **kw)
     keep = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in blocks] if blocks else []
@@ -48,10 +51,13 @@ def problem_calls(ctx, Z, blocks, cost=True):
     if blocks:
         ctx._chk(ctx.L.socp_problem_set_blocks_dev(ctx.h, None, 0, None, None))
     ctx.trace_batch(Z, stride=2, cap=8, **kw)
-    if cost:
+    if fixed:
         ctx.cost_batch(Z, xend=True, **kw)
     tl = np.stack([ctx.timeline(z) for z in Z])
     ctx.move_batch(Z, 0.5 * (tl[:, :-1] + tl[:, 1:]), **kw)
+    if fixed and ctx.event_channels() > 0:
+        ctx.events_batch(Z, [0], [0.0], **kw)
+    ctx.regrid_batch(Z, [capi.FIXED, capi.CONTINUOUS, capi.FREE], np.linspace(tl[:, 0], tl[:, -1], 3, axis=1), **kw)
 
 
 def free_calls(ctx, X0, tf):
@@ -75,7 +81,7 @@ def goddard(variant, integrator, mu2):
     fixed = integrator == capi.INT_RK4
     print("goddard %s integrator %d mu2 %g" % (variant, integrator, mu2), flush=True)
     free_calls(ctx, Z[:, :14], 0.01)
-    problem_calls(ctx, Z, None, cost=fixed)
+    problem_calls(ctx, Z, None, fixed=fixed)
     B = len(Z)
     time = np.tile(prob.time, (B, 1))
     xnode = np.tile(prob.xnode.ravel(), (B, 1))
@@ -84,7 +90,7 @@ def goddard(variant, integrator, mu2):
         if smooth:
             params[:, 6] = 1.0
         ctx._chk(ctx.L.socp_problem_blocks_all_smooth(ctx.h, smooth))
-        problem_calls(ctx, Z, (params, time, xnode), cost=fixed)
+        problem_calls(ctx, Z, (params, time, xnode), fixed=fixed)
     ctx.close()
 
 
