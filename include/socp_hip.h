@@ -20,6 +20,8 @@
 #ifndef SOCP_HIP_H_
 #define SOCP_HIP_H_
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -393,6 +395,69 @@ int socp_var_jacobian(socp_ctx *ctx, const double *z, double *fjac);
 /* The same for `np` unknown vectors of one problem structure, device pointers: Z[np][n] -> Fjac[np][n*n]; one wavefront per
  * (problem, segment); per-problem blocks (socp_problem_set_blocks_dev) apply. */
 int socp_var_jacobian_multi_dev(socp_ctx *ctx, int np, const double *d_Z, double *d_Fjac);
+
+/* Parameter sensitivities of a whole batch of converged unknown vectors: the tangent dz/dtheta of the solution branch
+ * F(z; theta) = 0, i.e. the solution of J dz = -dF/dtheta with J the shooting Jacobian (implicit-function theorem).  [ext] The
+ * reference restarts every continuation step from the previous solution (shooting.cpp:598-778); z + dtheta dz is the first-order
+ * predictor, dp0/dx0 the gain of the neighbouring-extremal guidance law around a stored extremal.  A direction names ONE entry theta
+ * of a row's blocks (its own when socp_problem_set_blocks_dev is in force, the shared tables otherwise): */
+#define SOCP_DIR_PARAM 0   /* index: slot of the packed block, 0 .. nparams+1 (the two trailing slots are sw0, sw1) */
+#define SOCP_DIR_TIME  1   /* index: node j, 0 .. M        (time[b][j]) */
+#define SOCP_DIR_XNODE 2   /* index: j*2d + c, c < d       (xnode[b][j][c]; only the first d of a node row are read) */
+/* Z[B][n], K directions (dir_kind[K], dir_index[K]: HOST arrays, read before the call returns -- they travel as a kernel argument;
+ * 1 <= K <= 16) -> dZ[B][K][n], info[B], Fp[B][K][n] (may be NULL: dF/dtheta_k as differenced).  Per row b:
+ *   1. e = sqrt(max(epsfcn, DBL_EPSILON))                   (the step rule of MINPACK's fdjac1, as socp_fd_jacobian)
+ *   2. F0 = F(z; blocks)
+ *   3. per direction k, theta the addressed entry: h = e |theta|, or e when theta == 0.0 (so h > 0, and mu2 + h > 0 when mu2 > 0);
+ *      Fk = the residual with that ONE entry replaced by theta + h;  G[k][i] = (Fk[i] - F0[i]) / h.  The time of a FREE node, an
+ *      xnode entry the modes never read or a parameter the model ignores is not refused: G = 0 and dz = -+0
+ *   4. jac == 0: J = the forward-difference Jacobian of socp_fd_jacobian_multi_dev at (z, F0) with this epsfcn and dedup on;
+ *      jac == 1: the variational Jacobian of socp_var_jacobian_multi_dev (a model without one: SOCP_ERR_UNSUPPORTED)
+ *   5. dZ[b][k] = the solution of J x = -G[k] (the negation is exact) by the elimination of 6.
+ *   6. on the column-major A and the right-hand sides y, for k = 0 .. n-1:
+ *        best = |a_kk|, p = k;  for i = k+1 .. n-1 in order: if (|a_ik| > best) (best, p) = (|a_ik|, i)      (the first maximum wins; a
+ *                                                                             NaN is never chosen over a number)
+ *        if (!(best > 0.0) or best is infinite): info = k + 1, all K solution rows of this problem = NaN, stop
+ *        swap rows k and p of A (all columns) and of every y;  l_i = a_ik / a_kk;
+ *        a_ij <- a_ij - l_i a_kj,  y_i <- y_i - l_i y_k   for i, j > k
+ *      then for k = n-1 .. 0:  x_k = y_k / a_kk;  y_i <- y_i - a_ik x_k for i < k;   info = 0, or n + 1 when a solution entry is not
+ *      finite.  Every operation is element-wise and the pivot search is the only reduction, so the result does not depend on how the
+ *      work is spread over lanes; in reference-order contexts (SOCP_VARIANT_AUTO / LANE_EXACT) each operation is one IEEE rounding
+ *      (no contraction), in SOCP_VARIANT_LANE_FAST contexts the updates are fused multiply-adds.
+ * All models, both variants, both integrators: only the launch-table entries residual, fdjac and var_jacobian are used, so a plugin
+ * has the call without change.  A Goddard smooth-law promise (socp_problem_blocks_all_smooth) covers the moved blocks.
+ * socp_tangent_work_bytes: the bytes of d_work for (B, K) on this context's problem (0 for arguments the call would refuse): the
+ * block rows, replicated unknowns and residual rows of the B (K + 1) launched rows, J[B][n*n], h[B][K], and on a model with
+ * variational equations what socp_var_jacobian_multi_dev integrates in.
+ * Launches of the _dev form: the block rows; ONE residual launch of B (K + 1) rows (the base rows wait for nothing); the Jacobian
+ * (1 launch, variational: 3); the differences; the elimination.  socp_ctx_counters advances by B (K + 1) M trajectories plus the
+ * Jacobian's (np T of the dedup list, or B M) and by 5 launches (variational: 7).
+ * SOCP_ERR_ARG: no problem set, B < 0, K outside 1 .. 16, a kind outside 0 .. 2 or an index outside its range, jac outside 0 .. 1, a
+ * NULL required pointer (dir_kind, dir_index; with B > 0: Z, dZ, info, d_work), work_bytes below socp_tangent_work_bytes, _blocks
+ * with params and param_stride != nparams + 2; B == 0: SOCP_OK without a launch; SOCP_ERR_UNSUPPORTED: jac == 1 without
+ * variational equations, n above the elimination's limit (below).  An error leaves the context unchanged.
+ * The _dev form takes device pointers (the directions stay host arrays), only enqueues on the context's stream and neither
+ * allocates, copies nor synchronises: the caller owns d_work.  The host forms stage through that stream, take the workspace from
+ * the context's grow-only buffers and return when the results are in the caller's arrays.  _blocks: per-row blocks like
+ * socp_residual_batch_blocks (any of params / time / xnode may be NULL); the context's own blocks are restored afterwards.
+ * Not covered: no predictor inside socp_chains_solve, no condition estimate (info says singular, not ill-conditioned), one GPU. */
+size_t socp_tangent_work_bytes(const socp_ctx *ctx, int B, int K);
+int socp_tangent_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int K, const int *dir_kind, const int *dir_index,
+                           double epsfcn, int jac, void *d_work, size_t work_bytes,
+                           double *d_dZ, int *d_info, double *d_Fp);
+int socp_tangent_batch(socp_ctx *ctx, int B, const double *Z, int K, const int *dir_kind, const int *dir_index,
+                       double epsfcn, int jac, double *dZ, int *info, double *Fp);
+int socp_tangent_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
+                              const double *time, const double *xnode, int K, const int *dir_kind, const int *dir_index,
+                              double epsfcn, int jac, double *dZ, int *info, double *Fp);
+/* The linear-algebra half on its own, on the context's stream and in its variant: A[B][n*n] column-major, Y[B][K][n] (overwritten by
+ * the solutions X), info[B]: the elimination of 6. above.  One problem per workgroup (n <= 16: four per workgroup); when the matrix
+ * and its right-hand sides fit 64 KiB of LDS they are eliminated there and A is left as it was, otherwise A is eliminated in place in
+ * HBM with the pivot row and the multiplier column of each step staged in LDS -- which bounds n and K: 2 n + K + 16 doubles (for
+ * n <= 16: four times that) must fit 64 KiB.  What A holds after a call on the HBM path is unspecified (work in progress of the
+ * elimination); callers that need A afterwards keep a copy.
+ * SOCP_ERR_ARG: B < 0, n < 1, K < 1, n above that bound, a NULL pointer with B > 0; B == 0: SOCP_OK without a launch.  One launch. */
+int socp_linsolve_batch_dev(socp_ctx *ctx, int B, int n, int K, double *d_A, double *d_Y, int *d_info);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@ EVAL_RHS, EVAL_CONTROL, EVAL_HAMILTONIAN = 0, 1, 2
 REQ_DONE, REQ_FVEC, REQ_JAC = 0, 1, 2
 INT_RK4, INT_DOPRI5 = 0, 1
 GODDARD_PARAM_NAMES = ["C", "b", "KD", "kr", "u_max", "mu1", "mu2", "singularControl"]
+DIR_PARAM, DIR_TIME, DIR_XNODE = 0, 1, 2      # what a direction of tangent_batch addresses (SOCP_DIR_*)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -146,6 +147,13 @@ def lib():
         L.socp_regrid_num_param.argtypes = [_vp, C.c_int, _ip]
         L.socp_regrid_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _vp, _vp, _vp]
         L.socp_regrid_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _dp, _dp, _dp]
+        L.socp_tangent_work_bytes.argtypes = [_vp, C.c_int, C.c_int]
+        L.socp_tangent_work_bytes.restype = C.c_size_t
+        L.socp_tangent_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _ip, C.c_double, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp]
+        L.socp_tangent_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _ip, C.c_double, C.c_int, _dp, _ip, _dp]
+        L.socp_tangent_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, C.c_double, C.c_int, _dp, _ip,
+                                                _dp]
+        L.socp_linsolve_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
         L.socp_ctx_get_switching_times.argtypes = [_vp, _dp]
         L.socp_chains_solve.argtypes = [_vp, C.c_int, C.POINTER(ChainOptions), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip,
                                         _ip, _dp, _dp, _dp, C.POINTER(ChainStats)]
@@ -283,6 +291,12 @@ def _block_args(B, params, time, xnode):
     """The (params, param_stride, time, xnode) arguments of a _blocks entry point from per-row blocks of B rows each (None: absent)."""
     pp, tt, xx = (_f64(a).reshape(B, -1) if a is not None else None for a in (params, time, xnode))
     return _d(pp), pp.shape[1] if pp is not None else 0, _d(tt), _d(xx)
+
+
+def _dirs(dirs):
+    """(kind[K], index[K]) int32 arrays from a list of (kind, index) pairs."""
+    d = np.ascontiguousarray(dirs, dtype=np.int32).reshape(-1, 2)
+    return np.ascontiguousarray(d[:, 0]), np.ascontiguousarray(d[:, 1])
 
 
 def _call_with_enough_cap(call, cap):
@@ -685,6 +699,41 @@ class Context:
         X2 = np.full((B, M2 + 1, self.s), np.nan) if want_xnode else None
         self._chk(self.L.socp_regrid_batch_blocks(self.h, B, _d(Z), *blocks, M2, mt.ctypes.data_as(_ip), _d(T2), _d(Z2), _d(X2)))
         return dict(z=Z2, time=T2, xnode=X2)
+
+    # -- batched tangent
+    def tangent_work_bytes(self, B, K):
+        """Bytes of the workspace tangent_batch_dev needs for B rows and K directions (socp_tangent_work_bytes)."""
+        return int(self.L.socp_tangent_work_bytes(self.h, int(B), int(K)))
+
+    def tangent_batch_dev(self, B, d_Z, dirs, epsfcn, jac, d_work, work_bytes, d_dZ, d_info, d_Fp=None):
+        """Device pointers (ints; d_Fp may be None), dirs a host list of (kind, index); enqueue only, no allocation, no copy, no
+        synchronise (socp_tangent_batch_dev)."""
+        kinds, index = _dirs(dirs)
+        self._chk(self.L.socp_tangent_batch_dev(self.h, int(B), _vp(d_Z), len(kinds), kinds.ctypes.data_as(_ip), index.ctypes.data_as(_ip),
+                                                float(epsfcn), int(jac), _vp(d_work), int(work_bytes), _vp(d_dZ), _vp(d_info), _vp(d_Fp)))
+
+    def tangent_batch(self, Z, dirs, epsfcn=1e-15, jac=0, params=None, time=None, xnode=None, fp=False):
+        """dz/dtheta of every row of Z for the K directions dirs = [(kind, index), ...] (DIR_PARAM: slot of the packed block,
+        DIR_TIME: node, DIR_XNODE: node * 2d + component): the solution of J dz = -dF/dtheta, J the forward-difference (jac=0) or
+        variational (jac=1) shooting Jacobian (include/socp_hip.h has the definition).  Returns dict(dz[B][K][n], info[B] (0: solved,
+        k + 1: no pivot at step k, n + 1: a solution entry is not finite), fp[B][K][n] = dF/dtheta or None).  params / time / xnode:
+        per-row blocks as in residual_batch_blocks."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        kinds, index = _dirs(dirs)
+        K = len(kinds)
+        blocks = _block_args(B, params, time, xnode)
+        dz = np.full((B, K, self.n), np.nan)
+        info = np.zeros(B, dtype=np.int32)
+        G = np.full((B, K, self.n), np.nan) if fp else None
+        self._chk(self.L.socp_tangent_batch_blocks(self.h, B, _d(Z), *blocks, K, kinds.ctypes.data_as(_ip), index.ctypes.data_as(_ip),
+                                                   float(epsfcn), int(jac), _d(dz), info.ctypes.data_as(_ip), _d(G)))
+        return dict(dz=dz, info=info, fp=G)
+
+    def linsolve_batch_dev(self, B, n, K, d_A, d_Y, d_info):
+        """Device pointers (ints): A[B][n*n] column-major, Y[B][K][n] overwritten by the solutions, info[B]; enqueue only
+        (socp_linsolve_batch_dev)."""
+        self._chk(self.L.socp_linsolve_batch_dev(self.h, int(B), int(n), int(K), _vp(d_A), _vp(d_Y), _vp(d_info)))
 
     def chains_solve(self, Z0, kind=CHAIN_PLAIN, param_index=0, step=1.0, step_min=1e-12, goal=None, params=None,
                      time_prev=None, x_prev=None, time_goal=None, x_goal=None, xtol=1e-8, maxfev=10000, epsfcn=1e-15,

@@ -153,6 +153,22 @@ bool has_var(const socp_ctx *c) { return c->vt->var_traj && c->vt->var_jacobian 
 
 double fd_eps(double epsfcn) { return std::sqrt(epsfcn > DBL_EPSILON ? epsfcn : DBL_EPSILON); }
 
+// the variational Jacobian of np problems (socp_var_jacobian_multi_dev, socp_tangent_batch_dev with jac = 1): what it integrates in
+// -- the augmented start and end states of the np M trajectories, their start and end times -- and its launch
+size_t var_work_doubles(const socp_ctx *c, size_t np)
+{
+    const size_t segs = np * c->M, L = (size_t)(c->S + 1) * c->S;
+    return 2 * segs * L + 2 * segs;
+}
+
+hipError_t run_var_jacobian(socp_ctx *c, int np, const double *d_Z, double *work, double *d_Fjac)
+{
+    const size_t segs = (size_t)np * c->M, L = (size_t)(c->S + 1) * c->S;
+    double *Xaug = work, *Xtf = Xaug + segs * L, *t0 = Xtf + segs * L, *tf = t0 + segs;
+    c->n_traj += (long long)segs; c->n_launch += 3;
+    return c->vt->var_jacobian(c->stream, c->P, c->pb, np, d_Z, Xaug, Xtf, t0, tf, d_Fjac);
+}
+
 // ---- staging of the host-pointer entry points: copies travel on the context's stream, the entry point synchronises once at its end
 template <class T> hipError_t copy_up(socp_ctx *c, T *dev, const T *host, size_t count)
 {
@@ -1305,11 +1321,8 @@ int socp_var_jacobian_multi_dev(socp_ctx *c, int np, const double *d_Z, double *
         return fail(c, SOCP_ERR_UNSUPPORTED, "var_jacobian: this model has no variational equations (modelOrder 0)");
     if (np == 0) return SOCP_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t M = c->M, L = (size_t)(c->S + 1) * c->S, B = (size_t)np * M;
-    HIP_TRY(c, c->s_var.reserve(sizeof(double) * (2 * B * L + 2 * B)));
-    double *Xaug = c->s_var.as<double>(), *Xtf = Xaug + B * L, *t0 = Xtf + B * L, *tf = t0 + B;
-    c->n_traj += (long long)B; c->n_launch += 3;
-    HIP_TRY(c, c->vt->var_jacobian(c->stream, c->P, c->pb, np, d_Z, Xaug, Xtf, t0, tf, d_Fjac));
+    HIP_TRY(c, c->s_var.reserve(sizeof(double) * var_work_doubles(c, np)));
+    HIP_TRY(c, run_var_jacobian(c, np, d_Z, c->s_var.as<double>(), d_Fjac));
     return SOCP_OK;
 }
 
@@ -1327,6 +1340,165 @@ int socp_var_jacobian(socp_ctx *c, const double *z, double *fjac)
     HIP_TRY(c, copy_down(c, fjac, c->s_out.as<double>(), n * n));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SOCP_OK;
+}
+
+/* ---- batched tangent ----------------------------------------------------------------------- */
+
+namespace {
+// the workspace of socp_tangent_batch_dev, in doubles from its start: block rows, replicated unknowns and residual rows of the
+// R = B (K + 1) launched rows, the Jacobians, the steps; then what the variational Jacobian integrates in (models that have one)
+struct TangentWork {
+    size_t params, time, xnode, Z, F, J, h, var, total;
+};
+
+TangentWork tangent_layout(const socp_ctx *c, int B, int K)
+{
+    const size_t R = (size_t)B * (K + 1), nodes = (size_t)c->M + 1, n = c->n;
+    TangentWork w{};
+    size_t at = 0;
+    auto take = [&](size_t count) { const size_t here = at; at += (count + 1) & ~(size_t)1; return here; };      // 16-byte aligned pieces
+    w.params = take(R * (c->nparams + 2));
+    w.time = take(R * nodes);
+    w.xnode = take(R * nodes * c->S);
+    w.Z = take(R * n);
+    w.F = take(R * n);
+    w.J = take((size_t)B * n * n);
+    w.h = take((size_t)B * K);
+    w.var = take(has_var(c) ? var_work_doubles(c, B) : 0);
+    w.total = at;
+    return w;
+}
+
+// *dirs: the directions as they travel to the kernel (the host arrays are read here)
+int tangent_args(socp_ctx *c, const char *who, int B, int K, const int *dir_kind, const int *dir_index, int jac, TangentDirs *dirs)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (K < 1 || K > kMaxTangentDirs) return fail(c, SOCP_ERR_ARG, w + ": 1 <= K <= 16 directions are required");
+    if (!dir_kind || !dir_index) return fail(c, SOCP_ERR_ARG, w + ": null direction table");
+    if (jac != 0 && jac != 1) return fail(c, SOCP_ERR_ARG, w + ": jac must be 0 (forward differences) or 1 (variational)");
+    for (int k = 0; k < K; k++) {
+        const int kind = dir_kind[k], index = dir_index[k];
+        int range = -1;
+        if (kind == SOCP_DIR_PARAM) range = c->nparams + 2;
+        else if (kind == SOCP_DIR_TIME) range = c->M + 1;
+        else if (kind == SOCP_DIR_XNODE) range = (c->M + 1) * c->S;
+        if (range < 0) return fail(c, SOCP_ERR_ARG, w + ": direction " + std::to_string(k) + " has kind " + std::to_string(kind) + " (0 .. 2)");
+        // only the first d entries of a node's row are boundary values the residual reads
+        if (index < 0 || index >= range || (kind == SOCP_DIR_XNODE && index % c->S >= c->dim))
+            return fail(c, SOCP_ERR_ARG, w + ": direction " + std::to_string(k) + " has index " + std::to_string(index) + " outside its range");
+        dirs->kind[k] = kind; dirs->index[k] = index;
+    }
+    for (int k = K; k < kMaxTangentDirs; k++) dirs->kind[k] = dirs->index[k] = -1;
+    if (jac == 1 && !has_var(c))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": this model has no variational equations (modelOrder 0): jac = 1 needs them");
+    return SOCP_OK;
+}
+}  // namespace
+
+size_t socp_tangent_work_bytes(const socp_ctx *c, int B, int K)
+{
+    if (!c || !c->has_problem || B < 0 || K < 1 || K > kMaxTangentDirs) return 0;
+    return sizeof(double) * tangent_layout(c, B, K).total;
+}
+
+int socp_linsolve_batch_dev(socp_ctx *c, int B, int n, int K, double *d_A, double *d_Y, int *d_info)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (B < 0 || n < 1 || K < 1) return fail(c, SOCP_ERR_ARG, "linsolve_batch: B >= 0, n >= 1 and K >= 1 are required");
+    if (!linsolve_fits(n, K))
+        return fail(c, SOCP_ERR_ARG, "linsolve_batch: a pivot row and a multiplier column (2 n + K doubles; n <= 16: of four problems) must fit 64 KiB of LDS");
+    if (B > 0 && (!d_A || !d_Y || !d_info)) return fail(c, SOCP_ERR_ARG, "linsolve_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_launch += 1;
+    HIP_TRY(c, (c->variant == SOCP_VARIANT_LANE_FAST ? linsolve_fast : linsolve)(c->stream, B, n, K, d_A, d_Y, d_info));
+    return SOCP_OK;
+}
+
+int socp_tangent_batch_dev(socp_ctx *c, int B, const double *d_Z, int K, const int *dir_kind, const int *dir_index, double epsfcn, int jac,
+                           void *d_work, size_t work_bytes, double *d_dZ, int *d_info, double *d_Fp)
+{
+    if (!c) return SOCP_ERR_ARG;
+    TangentDirs dirs;
+    const int rc = tangent_args(c, "tangent_batch", B, K, dir_kind, dir_index, jac, &dirs);
+    if (rc != SOCP_OK) return rc;
+    if (B > 0 && (!d_Z || !d_work || !d_dZ || !d_info)) return fail(c, SOCP_ERR_ARG, "tangent_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    const TangentWork w = tangent_layout(c, B, K);
+    if (work_bytes < sizeof(double) * w.total) return fail(c, SOCP_ERR_ARG, "tangent_batch: the workspace is smaller than socp_tangent_work_bytes");
+    // the elimination stages a pivot row and a multiplier column in LDS when the matrix does not fit there
+    if (!linsolve_fits(c->n, K))
+        return fail(c, SOCP_ERR_UNSUPPORTED, "tangent_batch: too many unknowns for the batched linear solve (2 n + K doubles must fit 64 KiB of LDS)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool fast = c->variant == SOCP_VARIANT_LANE_FAST;
+    double *wk = static_cast<double *>(d_work);
+    double *wP = wk + w.params, *wT = wk + w.time, *wX = wk + w.xnode, *wZ = wk + w.Z, *wF = wk + w.F, *wJ = wk + w.J, *wH = wk + w.h;
+    const int R = B * (K + 1);
+    // launch 1: the block rows (row kk B + b: direction kk - 1 of row b; kk = 0 its own block), the replicated unknowns, the steps
+    c->n_launch += 1;
+    HIP_TRY(c, (fast ? tangent_expand_fast : tangent_expand)(c->stream, c->P, c->pb, c->nparams, B, K, dirs, fd_eps(epsfcn), d_Z, wP, wT, wX, wZ, wH));
+    // launch 2: F0 and every Fk, each row with its own block.  A smooth-law promise (or, with shared parameters, the context's own
+    // mu2 > 0) covers the moved blocks: a moved mu2 is mu2 + e |mu2|
+    {
+        BlocksGuard guard(c);
+        const int smooth = c->pb.pp_params ? c->pb.pp_smooth : (c->model_id == SOCP_MODEL_GODDARD && c->P.p[6] > 0 ? 1 : 0);
+        c->pb.pp_params = wP; c->pb.pp_stride = c->nparams + 2; c->pb.pp_time = wT; c->pb.pp_xnode = wX; c->pb.pp_smooth = smooth;
+        HIP_TRY(c, run_residual(c, R, wZ, wF));
+    }
+    // launch 3: the Jacobian at (z, F0) with the row's own blocks (rows 0 .. B-1 of F are the base rows)
+    if (jac == 0) {
+        const int r = socp_fd_jacobian_multi_dev(c, B, d_Z, wF, epsfcn, wJ, 1);
+        if (r != SOCP_OK) return r;
+    } else {
+        HIP_TRY(c, run_var_jacobian(c, B, d_Z, wk + w.var, wJ));
+    }
+    // launches 4, 5: -G into dZ, G into Fp; J x = -G in place
+    c->n_launch += 2;
+    HIP_TRY(c, (fast ? tangent_diff_fast : tangent_diff)(c->stream, B, K, c->n, wF, wH, d_dZ, d_Fp));
+    HIP_TRY(c, (fast ? linsolve_fast : linsolve)(c->stream, B, c->n, K, wJ, d_dZ, d_info));
+    return SOCP_OK;
+}
+
+int socp_tangent_batch(socp_ctx *c, int B, const double *Z, int K, const int *dir_kind, const int *dir_index, double epsfcn, int jac,
+                       double *dZ, int *info, double *Fp)
+{
+    if (!c) return SOCP_ERR_ARG;
+    TangentDirs dirs;
+    const int rc0 = tangent_args(c, "tangent_batch", B, K, dir_kind, dir_index, jac, &dirs);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B > 0 && (!Z || !dZ || !info)) return fail(c, SOCP_ERR_ARG, "tangent_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nZ = (size_t)B * c->n, nD = (size_t)B * K * c->n, nF = Fp ? nD : 0, bytes = socp_tangent_work_bytes(c, B, K);
+    double *d_Z;
+    HIP_TRY(c, c->s_var.reserve(bytes));
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (nD + nF) + sizeof(int) * (size_t)B));
+    double *dD = c->s_out.as<double>(), *dF = dD + nD;
+    int *dI = reinterpret_cast<int *>(dF + nF);
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, d_Z));
+    const int rc = socp_tangent_batch_dev(c, B, d_Z, K, dir_kind, dir_index, epsfcn, jac, c->s_var.p, bytes, dD, dI, Fp ? dF : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, dZ, dD, nD));
+    if (Fp) HIP_TRY(c, copy_down(c, Fp, dF, nF));
+    HIP_TRY(c, copy_down(c, info, dI, (size_t)B));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_tangent_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                              const double *xnode, int K, const int *dir_kind, const int *dir_index, double epsfcn, int jac, double *dZ,
+                              int *info, double *Fp)
+{
+    if (!c) return SOCP_ERR_ARG;
+    TangentDirs dirs;
+    const int rc0 = tangent_args(c, "tangent_batch_blocks", B, K, dir_kind, dir_index, jac, &dirs);
+    if (rc0 != SOCP_OK) return rc0;
+    if (const int rc = blocks_stride(c, "tangent_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !dZ || !info)) return fail(c, SOCP_ERR_ARG, "tangent_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_tangent_batch(c, B, Z, K, dir_kind, dir_index, epsfcn, jac, dZ, info, Fp); });
 }
 
 }  // extern "C"

@@ -73,6 +73,32 @@ struct ModelLaunchers {
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
 hipError_t fd_diff(hipStream_t st, int n, int np, const double *z, double eps, const double *rows, double *fjac);
+// socp_tangent_batch (kernels_tangent.hip, built once per flavour: the plain names are the no-contraction object's, the _fast names
+// the contraction-on object's).  The directions travel as a kernel argument.
+constexpr int kMaxTangentDirs = 16;
+constexpr int kLinsolveLdsBytes = 64 * 1024;         // LDS a linsolve workgroup may take: two such workgroups share a CU's 160 KiB
+constexpr int kLinsolveScratch = 16;                  // doubles per team behind its matrix: candidate values, candidate rows, the not-finite flag
+// team geometry of the elimination from n: W wavefronts per problem, T problems per workgroup (kernels_tangent.hip)
+inline int linsolve_waves(int n) { return n <= 64 ? 1 : (n <= 128 ? 2 : 4); }
+inline int linsolve_teams(int n) { return n <= 16 ? 4 : 1; }
+// whether a workgroup's teams fit the LDS at least on the HBM path (a pivot row, a multiplier column and the scratch per team)
+inline bool linsolve_fits(int n, int K)
+{
+    return sizeof(double) * linsolve_teams(n) * ((size_t)2 * n + K + kLinsolveScratch) <= (size_t)kLinsolveLdsBytes;
+}
+struct TangentDirs { int kind[kMaxTangentDirs], index[kMaxTangentDirs]; };
+// block rows r = kk B + b (kk = 0: row b's own block or the shared one; kk = k + 1: direction k's entry moved by h[b][k]) into
+// wP[R][nparams + 2], wT[R][M+1], wX[R][(M+1) 2d], the replicated unknowns into wZ[R][n], the steps into wH[B][K];  R = B (K + 1)
+hipError_t tangent_expand(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int nparams, int B, int K, const TangentDirs &dirs,
+                          double e, const double *Z, double *wP, double *wT, double *wX, double *wZ, double *wH);
+hipError_t tangent_expand_fast(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int nparams, int B, int K, const TangentDirs &dirs,
+                               double e, const double *Z, double *wP, double *wT, double *wX, double *wZ, double *wH);
+// G = (F[(k+1) B + b] - F[b]) / h[b][k] from the residual rows F[R][n]: -G into rhs[B][K][n], G into Fp[B][K][n] unless null
+hipError_t tangent_diff(hipStream_t st, int B, int K, int n, const double *F, const double *H, double *rhs, double *Fp);
+hipError_t tangent_diff_fast(hipStream_t st, int B, int K, int n, const double *F, const double *H, double *rhs, double *Fp);
+// A[B][n*n] column-major, Y[B][K][n] -> the solutions in Y, info[B]; hipErrorInvalidValue unless linsolve_fits(n, K)
+hipError_t linsolve(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
+hipError_t linsolve_fast(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
 // flavour- and model-independent: total[b] = sum of cost[b][0 .. M), left to right
 hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *total);
 // flavour- and model-independent: the unknown vectors Z2[B][n2] of a re-grid's target structure from the moved node states

@@ -339,6 +339,26 @@ def events_local(ctx, args, local, lo, rank, params=None):
             "signatures": signatures, "wall_s": wall, "file": path}
 
 
+def tangent_local(ctx, args, local, lo, rank, params=None):
+    """--tangent-out: the sensitivity dz/dtheta (socp_tangent_batch) of this rank's CONVERGED chains to the packed parameter
+    --tangent-param, each chain with its own parameter block when the chains have one, written to PATH.rank<r>.npz: index [k] =
+    position of the chain in the sweep's start table, dz [k][n], info [k] (0: solved), theta [k] = the chain's value of the parameter,
+    z [k][n] = the unknown vectors differentiated.
+    Runs after the timed solve.  Returns the record entry of this rank: which roots are stiff in the parameter and which are not."""
+    from . import capi
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.tangent_out)
+    slot = capi.GODDARD_PARAM_NAMES.index(args.tangent_param)
+    theta = np.full(len(conv), ctx.get_params()[slot]) if own is None else own[:, slot].copy()
+    t0 = time.perf_counter()
+    r = ctx.tangent_batch(z, [(capi.DIR_PARAM, slot)], params=own)
+    wall = time.perf_counter() - t0
+    dz, info = r["dz"][:, 0, :], r["info"]
+    np.savez(path, index=index, dz=dz, info=info, theta=theta, z=z)
+    solved = info == 0
+    return {"parameter": args.tangent_param, "chains": int(len(conv)), "info_nonzero": int(np.sum(~solved)),
+            "median_norm_dz": float(np.median(np.linalg.norm(dz[solved], axis=1))) if solved.any() else None, "wall_s": wall, "file": path}
+
+
 def regrid_structure(args):
     """--regrid-segments: time modes of the target structure -- goddard_multiple_shooting_problem(M2)'s (free final time) for a
     multiple-shooting sweep, FIXED end times for single shooting (whose final time is fixed)."""
@@ -468,6 +488,15 @@ def main():
                          "id, count) and adds events_rank<r> {chains, refine, events_per_segment_max, signatures, wall_s, file} to the "
                          "record, signatures = chains per tuple of event ids in time order.  Not with --model interceptor.  Absent: "
                          "the timed wall and the printed record are unchanged")
+    ap.add_argument("--tangent-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank computes the sensitivity dz/dtheta of the converged chains of its own block to "
+                         "one packed parameter in one batch (socp_tangent_batch), with the chains' own parameter blocks, writes "
+                         "PATH.rank<r>.npz (index, dz, info, theta, z) and adds tangent_rank<r> {parameter, chains, info_nonzero, "
+                         "median_norm_dz, wall_s, file} to the record.  Not with --model interceptor.  Absent: the timed wall and the "
+                         "printed record are unchanged")
+    ap.add_argument("--tangent-param", default="KD", metavar="NAME",
+                    help="with --tangent-out: the parameter, by its name in the model's packed block (C, b, KD, kr, u_max, mu1, mu2, "
+                         "singularControl)")
     ap.add_argument("--events-refine", type=int, default=2, metavar="R",
                     help="with --events-out: false-position steps per event, 0 .. 8 (0: linear interpolation over the step)")
     args = ap.parse_args()
@@ -481,6 +510,12 @@ def main():
         ap.error("--regrid-out is implemented for the Goddard sweeps")
     if args.trace_stride < 1:
         ap.error("--trace-stride must be >= 1")
+    if args.tangent_out and args.model == "interceptor":
+        ap.error("--tangent-out is implemented for the Goddard sweeps")
+    if args.tangent_out:
+        from .capi import GODDARD_PARAM_NAMES            # (the module only: the library is loaded by the first context)
+        if args.tangent_param not in GODDARD_PARAM_NAMES:
+            ap.error("--tangent-param: not a name of the packed parameter block (%s)" % ", ".join(GODDARD_PARAM_NAMES))
     if args.cost_out and args.model == "interceptor":
         ap.error("--cost-out: the interceptor has no running-cost kernel (its chart changes rewrite the costate in mid-trajectory)")
 
@@ -575,6 +610,8 @@ def main():
         extra["regrid_rank%d" % rank] = regrid_local(ctx, args, local, lo_w, rank, blocks)
     if args.events_out:
         extra["events_rank%d" % rank] = events_local(ctx, args, local, lo_w, rank, blocks)
+    if args.tangent_out:
+        extra["tangent_rank%d" % rank] = tangent_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
