@@ -459,6 +459,53 @@ int socp_tangent_batch_blocks(socp_ctx *ctx, int B, const double *Z, const doubl
  * SOCP_ERR_ARG: B < 0, n < 1, K < 1, n above that bound, a NULL pointer with B > 0; B == 0: SOCP_OK without a launch.  One launch. */
 int socp_linsolve_batch_dev(socp_ctx *ctx, int B, int n, int K, double *d_A, double *d_Y, int *d_info);
 
+/* The distinct roots of a whole sweep: which distinct rows does a table hold, how many rows went to each, and which row went where.
+ * Model-independent (no problem has to be set, no launch table is used).
+ * Rows V[B][ld]; the first n <= ld entries of a row are compared.  Greedy leader grouping IN ROW ORDER:
+ *
+ *   G = 0
+ *   for b = 0 .. B-1:
+ *       if mask != NULL and mask[b] == 0:      label[b] = SOCP_GROUP_MASKED    (-3); continue
+ *       if any of V[b][0..n) is not finite:    label[b] = SOCP_GROUP_NOTFINITE (-2); continue
+ *       for g = 0 .. G-1 (in this order): if near(V[b], V[leader[g]]): label[b] = g; break
+ *       else if G < max_groups:  leader[G] = b; label[b] = G; G += 1
+ *       else:                    label[b] = SOCP_GROUP_OVERFLOW (-1)
+ *
+ *   near(v, l)  <=>  for every i < n:  |fl(v_i - l_i)| <= fl(atol + fl(rtol * |l_i|))      (inclusive; no contraction)
+ *
+ * A row joins the FIRST leader it is near, not the nearest.  The relation is not transitive, and this rule is what makes the result
+ * unique.
+ * Outputs:
+ *   label[B]
+ *   leader[max_groups]   the leader's row index, ascending; unused slots are -1
+ *   count[max_groups]    the number of members, leader included; unused slots are 0
+ *   radius[max_groups]   the maximum over a group's members and over i of |fl(v_i - l_i)|; unused slots are 0
+ *   summary[4]           G, and the number of overflow, non-finite and masked rows
+ * Every output is independent of summation order: label, leader, count and summary are integers, radius is a maximum of exactly
+ * rounded differences.  So there is ONE build of the kernels, compiled without contraction, and it serves both arithmetic flavours
+ * (every SOCP_VARIANT_*) bit for bit.
+ * On the device one round per group: in round g the leader is the lowest row still unassigned, and every unassigned row near it
+ * takes label g (kernels_group.hip has the equivalence argument).  A round reads the 4 B bytes of the labels and the rows still
+ * unassigned; the cost is G rounds, and a table of all-distinct rows costs max_groups rounds and ends in overflow labels.  Rounds are
+ * enqueued in chunks (1, 2, 4, 8, then 16 at a time) and the "next leader" word is read back once per chunk: BOTH forms synchronise
+ * the context's stream, the _dev form once per chunk.  Launches: two to begin (one when B == 0), the rounds, one to end;
+ * socp_ctx_counters advances by them and by no trajectory.
+ * The _dev form takes device pointers; its scratch (max_groups + 1 words) comes from the context's grow-only workspace.  The host
+ * form stages through the context's stream and returns when the results are in the caller's arrays.  All element offsets are 64-bit
+ * (B ld may exceed 2^31).
+ * SOCP_ERR_ARG (with a message): B < 0, n < 1, ld < n, max_groups < 1; atol or rtol negative or not finite; a NULL output pointer
+ * (label may be NULL when B == 0); V NULL with B > 0.  An error writes nothing.  B == 0: SOCP_OK, summary all zero and the slots
+ * filled as unused. */
+#define SOCP_GROUP_OVERFLOW  -1
+#define SOCP_GROUP_NOTFINITE -2
+#define SOCP_GROUP_MASKED    -3
+int socp_group_batch_dev(socp_ctx *ctx, int B, int n, int ld, const double *d_V, const int *d_mask /* or NULL */,
+                         double atol, double rtol, int max_groups,
+                         int *d_label, int *d_leader, int *d_count, double *d_radius, int *d_summary);
+int socp_group_batch    (socp_ctx *ctx, int B, int n, int ld, const double *V, const int *mask,
+                         double atol, double rtol, int max_groups,
+                         int *label, int *leader, int *count, double *radius, int *summary);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ REQ_DONE, REQ_FVEC, REQ_JAC = 0, 1, 2
 INT_RK4, INT_DOPRI5 = 0, 1
 GODDARD_PARAM_NAMES = ["C", "b", "KD", "kr", "u_max", "mu1", "mu2", "singularControl"]
 DIR_PARAM, DIR_TIME, DIR_XNODE = 0, 1, 2      # what a direction of tangent_batch addresses (SOCP_DIR_*)
+GROUP_OVERFLOW, GROUP_NOTFINITE, GROUP_MASKED = -1, -2, -3      # the negative labels of group_batch (SOCP_GROUP_*)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -154,6 +155,8 @@ def lib():
         L.socp_tangent_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, C.c_double, C.c_int, _dp, _ip,
                                                 _dp]
         L.socp_linsolve_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
+        L.socp_group_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]
+        L.socp_group_batch.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _ip, C.c_double, C.c_double, C.c_int, _ip, _ip, _ip, _dp, _ip]
         L.socp_ctx_get_switching_times.argtypes = [_vp, _dp]
         L.socp_chains_solve.argtypes = [_vp, C.c_int, C.POINTER(ChainOptions), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip,
                                         _ip, _dp, _dp, _dp, C.POINTER(ChainStats)]
@@ -734,6 +737,38 @@ class Context:
         """Device pointers (ints): A[B][n*n] column-major, Y[B][K][n] overwritten by the solutions, info[B]; enqueue only
         (socp_linsolve_batch_dev)."""
         self._chk(self.L.socp_linsolve_batch_dev(self.h, int(B), int(n), int(K), _vp(d_A), _vp(d_Y), _vp(d_info)))
+
+    # -- row grouping
+    def group_batch_dev(self, B, n, ld, d_V, d_mask, atol, rtol, max_groups, d_label, d_leader, d_count, d_radius, d_summary):
+        """Device pointers (ints; d_mask may be None): V[B][ld], label[B], leader / count / radius[max_groups], summary[4].  Enqueues on
+        the context's stream and synchronises it once per chunk of rounds (socp_group_batch_dev)."""
+        self._chk(self.L.socp_group_batch_dev(self.h, int(B), int(n), int(ld), _vp(d_V), _vp(d_mask), float(atol), float(rtol), int(max_groups),
+                                              _vp(d_label), _vp(d_leader), _vp(d_count), _vp(d_radius), _vp(d_summary)))
+
+    def group_batch(self, V, n=None, mask=None, atol=0.0, rtol=1e-6, max_groups=1024):
+        """The distinct rows of the table V[B][ld], compared on their first n entries (default: all): greedy leader grouping in row
+        order -- a row joins the FIRST leader l with |v_i - l_i| <= atol + rtol |l_i| for every i < n, or becomes the next leader
+        (include/socp_hip.h has the definition).  mask[B]: rows with mask == 0 take no part.  Returns dict(label[B] (the group, or
+        GROUP_OVERFLOW / GROUP_NOTFINITE / GROUP_MASKED), leader[G] (row indices, ascending), count[G], radius[G] (max |v_i - l_i|
+        over a group), summary = [G, overflow rows, non-finite rows, masked rows]).  Needs no problem."""
+        V = _f64(V)
+        V = V.reshape(-1, V.shape[-1]) if V.ndim >= 2 else V.reshape(-1, 1)
+        B, ld = V.shape
+        n = ld if n is None else int(n)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).ravel() != 0, dtype=np.int32)
+            if m.size != B:
+                raise ValueError("group_batch: mask must have one entry per row")
+        cap = max(int(max_groups), 1)
+        label = np.empty(B, dtype=np.int32)
+        leader, count, radius = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32), np.empty(cap)
+        summary = np.zeros(4, dtype=np.int32)
+        ip_ = lambda a: a.ctypes.data_as(_ip) if a is not None else None      # noqa: E731
+        self._chk(self.L.socp_group_batch(self.h, B, n, ld, _d(V), ip_(m), float(atol), float(rtol), int(max_groups), ip_(label), ip_(leader),
+                                          ip_(count), _d(radius), ip_(summary)))
+        G = int(summary[0])
+        return dict(label=label, leader=leader[:G].copy(), count=count[:G].copy(), radius=radius[:G].copy(), summary=summary)
 
     def chains_solve(self, Z0, kind=CHAIN_PLAIN, param_index=0, step=1.0, step_min=1e-12, goal=None, params=None,
                      time_prev=None, x_prev=None, time_goal=None, x_goal=None, xtol=1e-8, maxfev=10000, epsfcn=1e-15,

@@ -1501,4 +1501,78 @@ int socp_tangent_batch_blocks(socp_ctx *c, int B, const double *Z, const double 
                        [&] { return socp_tangent_batch(c, B, Z, K, dir_kind, dir_index, epsfcn, jac, dZ, info, Fp); });
 }
 
+/* ---- row grouping --------------------------------------------------------------------------- */
+
+namespace {
+constexpr int kGroupChunk = 16;       // rounds enqueued between two read-backs of the "next leader" word, once the first few came singly
+
+int group_args(socp_ctx *c, int B, int n, int ld, const double *V, double atol, double rtol, int max_groups, const int *label,
+               const int *leader, const int *count, const double *radius, const int *summary)
+{
+    if (B < 0 || n < 1 || ld < n || max_groups < 1)
+        return fail(c, SOCP_ERR_ARG, "group_batch: B >= 0, n >= 1, ld >= n and max_groups >= 1 are required");
+    if (!(atol >= 0.0) || !(rtol >= 0.0) || !std::isfinite(atol) || !std::isfinite(rtol))
+        return fail(c, SOCP_ERR_ARG, "group_batch: atol and rtol must be finite and not negative");
+    if (!leader || !count || !radius || !summary || (B > 0 && !label)) return fail(c, SOCP_ERR_ARG, "group_batch: null output pointer");
+    if (B > 0 && !V) return fail(c, SOCP_ERR_ARG, "group_batch: null table");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_group_batch_dev(socp_ctx *c, int B, int n, int ld, const double *d_V, const int *d_mask, double atol, double rtol, int max_groups,
+                         int *d_label, int *d_leader, int *d_count, double *d_radius, int *d_summary)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = group_args(c, B, n, ld, d_V, atol, rtol, max_groups, d_label, d_leader, d_count, d_radius, d_summary)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->s_var.reserve(sizeof(int) * ((size_t)max_groups + 1)));
+    int *next = c->s_var.as<int>();
+    c->n_launch += B > 0 ? 2 : 1;
+    HIP_TRY(c, group_begin(c->stream, B, n, ld, d_V, d_mask, max_groups, d_label, d_leader, d_count, d_radius, d_summary, next));
+    if (B == 0) return SOCP_OK;
+    // rounds g .. g + chunk - 1, then the leader of round g + chunk back: none, and the rows ran out (rounds enqueued behind the last
+    // group found no leader and returned at once)
+    for (int g = 0, chunk = 1; g < max_groups; chunk = chunk < kGroupChunk ? 2 * chunk : kGroupChunk) {
+        const int end = max_groups - g < chunk ? max_groups : g + chunk;
+        for (; g < end; g++) {
+            c->n_launch += 1;
+            HIP_TRY(c, group_round(c->stream, B, n, ld, d_V, atol, rtol, g, d_label, d_leader, d_count, d_radius, d_summary, next));
+        }
+        if (g == max_groups) break;
+        int lead = 0;
+        HIP_TRY(c, copy_down(c, &lead, next + g, 1));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (lead < 0 || lead >= B) break;
+    }
+    c->n_launch += 1;
+    HIP_TRY(c, group_end(c->stream, B, d_label, d_summary));
+    return SOCP_OK;
+}
+
+int socp_group_batch(socp_ctx *c, int B, int n, int ld, const double *V, const int *mask, double atol, double rtol, int max_groups,
+                     int *label, int *leader, int *count, double *radius, int *summary)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = group_args(c, B, n, ld, V, atol, rtol, max_groups, label, leader, count, radius, summary)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nV = (size_t)B * ld, nB = (size_t)B, nG = (size_t)max_groups;
+    double *d_V = nullptr;
+    int *d_mask = nullptr;
+    // radius[G] first (8-byte aligned), then label[B], leader[G], count[G], summary[4]
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * nG + sizeof(int) * (nB + 2 * nG + 4)));
+    double *dR = c->s_out.as<double>();
+    int *dL = reinterpret_cast<int *>(dR + nG), *dLead = dL + nB, *dCount = dLead + nG, *dSum = dCount + nG;
+    if (B > 0) HIP_TRY(c, stage_up(c, c->s_in, V, nV, d_V));
+    if (B > 0 && mask) HIP_TRY(c, stage_up(c, c->s_aux, mask, nB, d_mask));
+    const int rc = socp_group_batch_dev(c, B, n, ld, d_V, d_mask, atol, rtol, max_groups, dL, dLead, dCount, dR, dSum);
+    if (rc != SOCP_OK) return rc;
+    if (B > 0) HIP_TRY(c, copy_down(c, label, dL, nB));
+    HIP_TRY(c, copy_down(c, leader, dLead, nG));
+    HIP_TRY(c, copy_down(c, count, dCount, nG));
+    HIP_TRY(c, copy_down(c, radius, dR, nG));
+    HIP_TRY(c, copy_down(c, summary, dSum, (size_t)4));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
 }  // extern "C"

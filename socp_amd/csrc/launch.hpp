@@ -99,6 +99,17 @@ hipError_t tangent_diff_fast(hipStream_t st, int B, int K, int n, const double *
 // A[B][n*n] column-major, Y[B][K][n] -> the solutions in Y, info[B]; hipErrorInvalidValue unless linsolve_fits(n, K)
 hipError_t linsolve(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
 hipError_t linsolve_fast(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
+// socp_group_batch (kernels_group.hip; flavour- and model-independent, built without contraction).  next[max_groups + 1]: the
+// "next leader" words -- next[g] is the leader of round g (INT_MAX: no row is left), written by group_begin (g = 0) and by round g - 1
+// group_begin: leader / count / radius / summary / next filled, label = MASKED or unassigned (= OVERFLOW), next[0] = the first leader
+hipError_t group_begin(hipStream_t st, int B, int n, int ld, const double *V, const int *mask, int max_groups, int *label, int *leader,
+                       int *count, double *radius, int *summary, int *next);
+// round g: unassigned rows near row next[g] take label g; leader[g], count[g], radius[g], summary[0] = g + 1, next[g + 1].  Returns
+// at once on the device when next[g] holds no row
+hipError_t group_round(hipStream_t st, int B, int n, int ld, const double *V, double atol, double rtol, int g, int *label, int *leader,
+                       int *count, double *radius, int *summary, int *next);
+// the numbers of overflow, not-finite and masked rows into summary[1 .. 3]
+hipError_t group_end(hipStream_t st, int B, const int *label, int *summary);
 // flavour- and model-independent: total[b] = sum of cost[b][0 .. M), left to right
 hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *total);
 // flavour- and model-independent: the unknown vectors Z2[B][n2] of a re-grid's target structure from the moved node states

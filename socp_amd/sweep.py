@@ -359,6 +359,37 @@ def tangent_local(ctx, args, local, lo, rank, params=None):
             "median_norm_dz": float(np.median(np.linalg.norm(dz[solved], axis=1))) if solved.any() else None, "wall_s": wall, "file": path}
 
 
+def roots_global(ctx, args, table, n, with_cost=False, leader_blocks=None):
+    """--roots-out: the distinct roots of the WHOLE sweep (socp_group_batch), on rank 0 from the gathered table [P][n+3] as it is:
+    ld = n + 3, mask = (info == 1), grouping on the unknown vectors z only, greedy in start order.  Written to PATH.npz: label [P]
+    indexed by start (the group, or -1 overflow / -2 not finite / -3 not converged), leader [G] = the start that leads group g,
+    count [G], radius [G], z [G][n] = the leaders' unknown vectors and -- with_cost: the model has a running-cost kernel and the
+    integrator is the fixed-step one -- cost [G] = the integrated running cost (socp_cost_batch) of the G LEADERS, each with its own
+    parameter block (leader_blocks(leader) -> [G][nparams + 2]) when chains carry one.  Runs after the timed solve.  Returns the
+    record entry."""
+    info = table[:, -2].astype(int)
+    t0 = time.perf_counter()
+    r = ctx.group_batch(table, n=n, mask=(info == 1), atol=args.roots_atol, rtol=args.roots_rtol, max_groups=args.roots_max)
+    leader, count, radius = r["leader"], r["count"], r["radius"]
+    G = len(leader)
+    z = np.ascontiguousarray(table[leader, :n])
+    arrays = dict(label=r["label"], leader=leader, count=count, radius=radius, z=z)
+    cost = None
+    if with_cost:
+        cost = ctx.cost_batch(z, params=leader_blocks(leader) if leader_blocks is not None and G else None)["total"] if G else np.zeros(0)
+        arrays["cost"] = cost
+    wall = time.perf_counter() - t0
+    path = args.roots_out + ".npz"
+    np.savez(path, **arrays)
+    best = int(np.argmin(cost)) if cost is not None and G else None
+    entry = {"groups": G, "overflow": int(r["summary"][1]), "largest_count": int(count.max()) if G else 0,
+             "radius_max": float(radius.max()) if G else 0.0, "best_cost": float(cost[best]) if best is not None else None, "best_root": best,
+             "rtol": args.roots_rtol, "atol": args.roots_atol, "wall_s": wall, "file": path}
+    if leader_blocks is not None and args.kd_spread != 0.0:
+        entry["note"] = "chains have their own parameter goals (--kd-spread): grouping is on z only, roots of different problems may share a group"
+    return entry
+
+
 def regrid_structure(args):
     """--regrid-segments: time modes of the target structure -- goddard_multiple_shooting_problem(M2)'s (free final time) for a
     multiple-shooting sweep, FIXED end times for single shooting (whose final time is fixed)."""
@@ -420,6 +451,8 @@ def interceptor_sweep(args, torch, dist, capi, world, rank, local_rank, dev, rec
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n]
+        if args.roots_out:
+            extra["roots"] = roots_global(ctx, args, table, n)
         record = json.dumps({**extra, "sweep": "interceptor_config5_M21_n%d_%s" % (n, "rk4" if args.fixed_step else "dopri5_tol%g" % args.ode_tol),
                              "starts": args.starts, "eps": eps, "n_gpus": world, "variant": args.variant, "solver": args.solver, "xtol": args.xtol, "wall_s": wall,
                              "warmup_starts": args.warmup,
@@ -497,6 +530,17 @@ def main():
     ap.add_argument("--tangent-param", default="KD", metavar="NAME",
                     help="with --tangent-out: the parameter, by its name in the model's packed block (C, b, KD, kr, u_max, mu1, mu2, "
                          "singularControl)")
+    ap.add_argument("--roots-out", default=None, metavar="PATH",
+                    help="after the timed solve, rank 0 groups the converged rows of the gathered table into distinct roots in one call "
+                         "(socp_group_batch: greedy in start order, a row joins the FIRST leader l with |z_i - l_i| <= atol + rtol |l_i| for "
+                         "every i), writes PATH.npz (label per start, leader, count, radius, z of the leaders, and for Goddard cost = the "
+                         "integrated running cost of the leaders) and adds roots {groups, overflow, largest_count, radius_max, best_cost, "
+                         "best_root, rtol, atol, wall_s, file} to the record.  Both models.  Absent: the timed wall and the printed record "
+                         "are unchanged")
+    ap.add_argument("--roots-rtol", type=float, default=1e-6, metavar="R", help="with --roots-out: the relative tolerance (finite, >= 0)")
+    ap.add_argument("--roots-atol", type=float, default=0.0, metavar="A", help="with --roots-out: the absolute tolerance (finite, >= 0)")
+    ap.add_argument("--roots-max", type=int, default=1024, metavar="G",
+                    help="with --roots-out: at most G groups (one device round per group); converged rows beyond them are counted as overflow")
     ap.add_argument("--events-refine", type=int, default=2, metavar="R",
                     help="with --events-out: false-position steps per event, 0 .. 8 (0: linear interpolation over the step)")
     args = ap.parse_args()
@@ -516,6 +560,12 @@ def main():
         from .capi import GODDARD_PARAM_NAMES            # (the module only: the library is loaded by the first context)
         if args.tangent_param not in GODDARD_PARAM_NAMES:
             ap.error("--tangent-param: not a name of the packed parameter block (%s)" % ", ".join(GODDARD_PARAM_NAMES))
+    if args.roots_max < 1:
+        ap.error("--roots-max must be >= 1")
+    if not (np.isfinite(args.roots_rtol) and args.roots_rtol >= 0):
+        ap.error("--roots-rtol must be finite and >= 0")
+    if not (np.isfinite(args.roots_atol) and args.roots_atol >= 0):
+        ap.error("--roots-atol must be finite and >= 0")
     if args.cost_out and args.model == "interceptor":
         ap.error("--cost-out: the interceptor has no running-cost kernel (its chart changes rewrite the costate in mid-trajectory)")
 
@@ -615,6 +665,9 @@ def main():
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
+        if args.roots_out:                                 # (a converged chain has reached its goal: its own KD is the goal)
+            own = None if chain_kw is None else (lambda lead: np.concatenate([params[lead, :2], goals[lead, None], params[lead, 3:], np.zeros((len(lead), 2))], axis=1))
+            extra["roots"] = roots_global(ctx, args, table, n_unknown, with_cost=ctx.has_cost(), leader_blocks=own)
         spread = float(np.max(np.abs(conv - np.median(conv, axis=0))) / np.max(np.abs(conv))) if len(conv) else None
         record = json.dumps({**extra, "solution_spread_rel": spread, "max_fnorm_converged": float(np.max(table[info == 1, -3])) if len(conv) else None,
                           "sweep": ("goddard_kd_continuation_chains_M6_n85" if chain_kw is not None else
