@@ -344,6 +344,58 @@ int socp_events_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
                              const double *xnode, int E, const int *chan, const double *levels, int refine, int cap, double *tev,
                              int *id, int *count, double *Xev);
 
+/* Conjugate-time test of a whole batch of unknown vectors: the Jacobi fields along every extremal.  [ext] The reference never
+ * computes this; indirect shooting finds extremals, not minima, and the standard instrument for telling them apart (cotcot, HamPath)
+ * is J(t) = dx(t)/dp(t0), a d x d matrix with J(t0) = 0: the first time det J(t) changes sign is the first conjugate time, and a
+ * fixed-endpoint extremal stops being locally optimal beyond it.
+ * Z[B][n] -> tq[B][M][cap], det[B][M][cap], count[B][M], nchange[B][M], tconj[B][M], Jend[B][M][d][d] (may be NULL).
+ * SETUP.  For row b and segment i: the start state X0 = z[s i .. s i + s) = [x (d) ; p (d)]; timeline, switching times and
+ * per-problem blocks as the residual takes them (socp_problem_set_blocks_dev: row b reads block b);
+ * eps = sqrt(max(epsfcn, DBL_EPSILON)), formed as socp_fd_jacobian forms it.
+ * COLUMNS.  Column 0 is X0; column c = 1 .. d starts from X0 with X[d+c-1] + h_c, h_c = eps |X0[d+c-1]|, or eps when that is zero
+ * (MINPACK's rule).
+ * STEPS.  All d + 1 trajectories take the residual's fixed RK4 steps: dt = (t2 - t1) / N, accumulated t, clamped last step, no step
+ * when t2 <= t1 + dt / 2.  Steps are numbered k = 1 .. K.
+ * SAMPLES.  One after step k iff k % stride == 0 or k == K:  tq = tk + step (tk the accumulated time before the step, step its
+ * length);  J[r][c-1] = (X^c[r] - X^0[r]) / h_c for r = 0 .. d-1;  det as below.  The samples of slab [b][i] are stored in order up
+ * to cap; count[b][i] = their number (samples beyond cap are counted, not stored, nothing is written past the slab; entries at or
+ * beyond min(count, cap) keep what the buffer held).
+ * DETERMINANT, a fixed sequence of IEEE operations (tests/jacobi_reference.py restates it).  Any entry of J not finite: det = NaN.
+ * Otherwise Gaussian elimination with partial pivoting, for k = 0 .. d-1:
+ *   the pivot row p is the smallest r >= k with |a[r][k]| maximal (strict >); rows k and p are swapped in the columns >= k, a swap
+ *   with p != k flips the sign;  v_k = a[k][k];  v_k == 0.0: det = +0.0 and the elimination stops;
+ *   for r > k: l = a[r][k] / v_k (one division), for c > k: a[r][c] = a[r][c] - l * a[k][c] (a product and a subtraction, unfused,
+ *   in the reference-order flavour)
+ *   det = (((v_0 v_1) v_2) ...), negated at the end when the number of swaps is odd.
+ * DETECTION, neg(v) = (v < 0.0).  Consecutive samples j-1, j with j-1 >= skip are compared, those beyond cap included: a change is
+ * counted when both determinants are non-NaN and neg(d0) != neg(d1).  nchange[b][i] = the number of changes;
+ * tconj[b][i] = t0 + (t1 - t0) * (d0 / (d0 - d1)) at the FIRST change, in this operation order; NaN when there is none.
+ * Jend holds the matrix J[r][c] of the LAST sample, row-major: dx(t_{i+1})/dp(t_i), what a rank test other than the plain
+ * determinant needs (the free-final-time variant with x' in place of one column).  A zero-length or backward segment takes no
+ * step: count = 0, nchange = 0, tconj = NaN, Jend all +0.0.
+ * WHAT IT IS AND IS NOT.  A measuring instrument.  The classical statement holds for single shooting with a fixed initial state,
+ * M = 1 (socp_regrid_batch moves any solution onto M2 = 1); for M > 1 each segment's determinant is reported for its own start
+ * node.  The matrix is a forward difference: near t0 it is rank-deficient to rounding and the sign of its determinant is noise --
+ * that is what skip is for.  A non-smooth control law (goddard with mu2 = 0) makes the fields jump.  With a free final time the
+ * plain determinant is not the right test: use Jend.
+ * socp_ctx_has_jacobi: 1 when the context's model has the entry, else 0.
+ * SOCP_ERR_ARG: no problem set, B < 0, stride < 1, skip < 0, cap < 1, a NULL required pointer with B > 0 (all but Jend), _blocks with
+ * params and param_stride != nparams + 2; B == 0: SOCP_OK without a launch; SOCP_ERR_UNSUPPORTED (the message says which): the
+ * context's integrator is SOCP_INT_DOPRI5, or the model's launch table has no jacobi entry (a model with its own ComputeTraj -- the
+ * interceptor -- and vtolUAV, for which it is not offered).  An error leaves the context unchanged.
+ * One launch; socp_ctx_counters advances by B M (d + 1) trajectories.  The _dev form takes device pointers, enqueues on the
+ * context's stream and neither copies nor synchronises; the host forms stage through that stream (tq and det travel both ways) and
+ * return when the results are in the caller's arrays.  _blocks: per-row blocks like socp_residual_batch_blocks (any of params /
+ * time / xnode may be NULL); the context's own blocks are restored afterwards. */
+int socp_ctx_has_jacobi(const socp_ctx *ctx);          /* 1 / 0 */
+int socp_jacobi_batch_dev(socp_ctx *ctx, int B, const double *d_Z, double epsfcn, int stride, int skip, int cap, double *d_tq,
+                          double *d_det, int *d_count, int *d_nchange, double *d_tconj, double *d_Jend);
+int socp_jacobi_batch(socp_ctx *ctx, int B, const double *Z, double epsfcn, int stride, int skip, int cap, double *tq, double *det,
+                      int *count, int *nchange, double *tconj, double *Jend);
+int socp_jacobi_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                             const double *xnode, double epsfcn, int stride, int skip, int cap, double *tq, double *det, int *count,
+                             int *nchange, double *tconj, double *Jend);
+
 /* replaces: shooting::Move(tf) (shooting.cpp:383-437) for a whole batch: the state ON a stored solution at a query time, and the
  * re-grid the reference's multi-stage flows build from it (testGoddard.cpp:115-145: vX[i] = Move(vt[i]), then InitShooting(vt, vX)
  * on a new structure).  Z[B][n], tq[B][K] -> Xq[B][K][s]; tout[B][K] (may be NULL) = the time actually reached.

@@ -142,6 +142,11 @@ def lib():
         L.socp_events_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _ip, _ip, _dp]
         L.socp_events_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _ip,
                                                _ip, _dp]
+        L.socp_ctx_has_jacobi.argtypes = [_vp]
+        L.socp_jacobi_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.socp_jacobi_batch.argtypes = [_vp, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp]
+        L.socp_jacobi_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip,
+                                               _ip, _dp, _dp]
         L.socp_move_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
         L.socp_move_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]
         L.socp_move_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp]
@@ -652,6 +657,56 @@ class Context:
                                                       ident.ctypes.data_as(_ip), count.ctypes.data_as(_ip), _d(X)))
             return count, ((t, ident, count, X) if xev else (t, ident, count))
         return _call_with_enough_cap(call, cap)
+
+    # -- batched Jacobi fields
+    def has_jacobi(self):
+        """Whether this model has a Jacobi-field kernel (socp_ctx_has_jacobi); the interceptor and vtolUAV have none."""
+        return self.L.socp_ctx_has_jacobi(self.h) == 1
+
+    def jacobi_batch_dev(self, B, d_Z, epsfcn, stride, skip, cap, d_tq, d_det, d_count, d_nchange, d_tconj, d_Jend=None):
+        """Device pointers (ints; d_Jend may be None); enqueue only, no copy, no synchronise (socp_jacobi_batch_dev)."""
+        self._chk(self.L.socp_jacobi_batch_dev(self.h, int(B), _vp(d_Z), float(epsfcn), int(stride), int(skip), int(cap), _vp(d_tq), _vp(d_det),
+                                               _vp(d_count), _vp(d_nchange), _vp(d_tconj), _vp(d_Jend)))
+
+    def jacobi_batch(self, Z, stride=1, skip=0, cap=64, epsfcn=0.0, jend=False, blocks=None):
+        """Conjugate-time test of every segment of every row of Z (include/socp_hip.h): the determinant of J(t) = dx(t)/dp(t0), formed
+        from d + 1 trajectories along the residual's fixed RK4 steps and sampled every `stride` steps and after the last; sign changes
+        between consecutive samples from sample `skip` on.  Z: a host array or a torch tensor on the device.  Returns a dict of
+        DEVICE tensors, the work of the context's stream synchronised: tq[B][M][cap], det[B][M][cap] (NaN at or beyond count),
+        count[B][M], nchange[B][M], tconj[B][M] (NaN: no change) and, with jend=True, jend[B][M][d][d].  When a segment has more
+        than `cap` samples the call is repeated with the largest count.  blocks = (params, time, xnode): per-row blocks as in
+        residual_batch_blocks, each a host array, a device tensor or None; they replace blocks set with socp_problem_set_blocks_dev and are cleared afterwards.
+        A measuring instrument: the classical statement is for M = 1 with a fixed initial state; see the header for the rest."""
+        import torch
+        dev = torch.device("cuda")
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        Zd = up(Z).reshape(-1, self.n)
+        B, M, d = Zd.shape[0], self.M, self.dim
+        held = [up(a).reshape(B, -1) if a is not None else None for a in (blocks if blocks is not None else ())]
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+
+        def call(c):
+            out = dict(tq=torch.full((B, M, c), float("nan"), dtype=torch.float64, device=dev),
+                       det=torch.full((B, M, c), float("nan"), dtype=torch.float64, device=dev),
+                       count=torch.zeros((B, M), dtype=torch.int32, device=dev), nchange=torch.zeros((B, M), dtype=torch.int32, device=dev),
+                       tconj=torch.full((B, M), float("nan"), dtype=torch.float64, device=dev))
+            if jend:
+                out["jend"] = torch.zeros((B, M, d, d), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()
+            if B:
+                self.jacobi_batch_dev(B, Zd.data_ptr(), epsfcn, stride, skip, c, out["tq"].data_ptr(), out["det"].data_ptr(), out["count"].data_ptr(),
+                                      out["nchange"].data_ptr(), out["tconj"].data_ptr(), out["jend"].data_ptr() if jend else None)
+            self.synchronize()
+            return out["count"].cpu().numpy(), out
+
+        if not held:
+            return _call_with_enough_cap(call, cap)
+        pp, tt, xx = held
+        self._chk(self.L.socp_problem_set_blocks_dev(self.h, ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx)))
+        try:
+            return _call_with_enough_cap(call, cap)
+        finally:
+            self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
 
     # -- batched Move(tf) / re-grid
     def move_batch_dev(self, B, d_Z, K, d_tq, d_Xq, d_tout=None):

@@ -1147,6 +1147,81 @@ int socp_events_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
                        [&] { return socp_events_batch(c, B, Z, E, chan, levels, refine, cap, tev, id, count, Xev); });
 }
 
+/* ---- batched Jacobi fields ----------------------------------------------------------------- */
+
+int socp_ctx_has_jacobi(const socp_ctx *c) { return c ? (table_of(c)->jacobi ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+int jacobi_args(socp_ctx *c, const char *who, int B, int stride, int skip, int cap)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (stride < 1) return fail(c, SOCP_ERR_ARG, w + ": stride >= 1 is required");
+    if (skip < 0) return fail(c, SOCP_ERR_ARG, w + ": skip >= 0 is required");
+    if (cap < 1) return fail(c, SOCP_ERR_ARG, w + ": cap >= 1 is required");
+    return args_tail(c, w, table_of(c)->jacobi != nullptr,
+                     "jacobi entry (a model with its own ComputeTraj, or one the entry is not offered for)", "the Jacobi fields follow");
+}
+}  // namespace
+
+int socp_jacobi_batch_dev(socp_ctx *c, int B, const double *d_Z, double epsfcn, int stride, int skip, int cap, double *d_tq, double *d_det,
+                          int *d_count, int *d_nchange, double *d_tconj, double *d_Jend)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = jacobi_args(c, "jacobi_batch", B, stride, skip, cap)) return rc;
+    if (B > 0 && (!d_Z || !d_tq || !d_det || !d_count || !d_nchange || !d_tconj)) return fail(c, SOCP_ERR_ARG, "jacobi_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_traj += (long long)B * c->M * (c->S / 2 + 1); c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->jacobi(c->stream, c->P, c->pb, B, d_Z, fd_eps(epsfcn), stride, skip, cap, d_tq, d_det, d_count, d_nchange, d_tconj,
+                                   d_Jend));
+    return SOCP_OK;
+}
+
+int socp_jacobi_batch(socp_ctx *c, int B, const double *Z, double epsfcn, int stride, int skip, int cap, double *tq, double *det, int *count,
+                      int *nchange, double *tconj, double *Jend)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = jacobi_args(c, "jacobi_batch", B, stride, skip, cap)) return rc;
+    if (B > 0 && (!Z || !tq || !det || !count || !nchange || !tconj)) return fail(c, SOCP_ERR_ARG, "jacobi_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t d = (size_t)c->S / 2, segs = (size_t)B * c->M, slots = segs * cap, nZ = (size_t)B * c->n, nJ = Jend ? segs * d * d : 0;
+    double *dZ, *dT;
+    int *dC;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, dZ));
+    // tq and det travel both ways: what the kernel leaves untouched (entries at or beyond min(count, cap)) comes back as it went
+    HIP_TRY(c, stage_up(c, c->s_out, tq, slots, dT, 2 * slots + segs + nJ));
+    double *dD = dT + slots, *dTc = dD + slots, *dJ = dTc + segs;
+    HIP_TRY(c, copy_up(c, dD, det, slots));
+    HIP_TRY(c, c->s_var.reserve(sizeof(int) * 2 * segs));
+    dC = c->s_var.as<int>();
+    int *dN = dC + segs;
+    const int rc = socp_jacobi_batch_dev(c, B, dZ, epsfcn, stride, skip, cap, dT, dD, dC, dN, dTc, Jend ? dJ : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, tq, dT, slots));
+    HIP_TRY(c, copy_down(c, det, dD, slots));
+    HIP_TRY(c, copy_down(c, count, dC, segs));
+    HIP_TRY(c, copy_down(c, nchange, dN, segs));
+    HIP_TRY(c, copy_down(c, tconj, dTc, segs));
+    if (Jend) HIP_TRY(c, copy_down(c, Jend, dJ, nJ));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_jacobi_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                             const double *xnode, double epsfcn, int stride, int skip, int cap, double *tq, double *det, int *count,
+                             int *nchange, double *tconj, double *Jend)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = jacobi_args(c, "jacobi_batch_blocks", B, stride, skip, cap)) return rc;
+    if (const int rc = blocks_stride(c, "jacobi_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !tq || !det || !count || !nchange || !tconj)) return fail(c, SOCP_ERR_ARG, "jacobi_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_jacobi_batch(c, B, Z, epsfcn, stride, skip, cap, tq, det, count, nchange, tconj, Jend); });
+}
+
 int socp_regrid_num_param(const socp_ctx *c, int M2, const int *mode_t2)
 {
     unsigned long long bits[4];

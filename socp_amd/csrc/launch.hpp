@@ -39,9 +39,9 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 9;      // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 10;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
-                                   // 9: batched events launcher
+                                   // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -69,6 +69,11 @@ struct ModelLaunchers {
     int event_channels;
     hipError_t (*events)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, unsigned, const double *, int, int,
                          double *, int *, int *, double *);
+    // batched Jacobi fields (socp_jacobi_batch): Z[B][n], eps, stride, skip, cap -> tq[B][M][cap], det[B][M][cap], count[B][M],
+    // nchange[B][M], tconj[B][M] and, unless null, Jend[B][M][d][d]; fixed-step integrator only.  Null: the model has its own
+    // ComputeTraj, or the entry is not offered for it
+    hipError_t (*jacobi)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double, int, int, int, double *, double *,
+                         int *, int *, double *, double *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)

@@ -62,6 +62,7 @@ struct VtolT {
     static constexpr int NU = 3;
     static constexpr bool kRefOrder = !FAST;
     static constexpr bool kCustomFinal = true;
+    static constexpr bool kNoJacobi = true;          // socp_jacobi_batch is not offered for this model (plugin_impl.hpp)
 
     // vtolUAV.cpp:107-143
     __device__ static __forceinline__ void control_only(const ModelParams &P, double, double, double, const double (&X)[S], double (&u)[3])

@@ -44,9 +44,10 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
+#include "jacobi.hpp"
 #include "launch.hpp"
 #include "variational.hpp"
 #include "../../include/socp_plugin.h"
@@ -191,6 +192,25 @@ hipError_t events(hipStream_t st, const ModelParams &P, const ProblemDev &pb, in
     return hipGetLastError();
 }
 
+// optional model hint kNoJacobi: leave the jacobi entry of the table empty (and its kernels unbuilt) although the model could have one
+template <class M, class = void> struct no_jacobi : std::false_type {};
+template <class M> struct no_jacobi<M, std::void_t<decltype(M::kNoJacobi)>> : std::bool_constant<M::kNoJacobi> {};
+
+// batched Jacobi fields: fixed-step integrator only.  One group of D + 1 neighbouring lanes per (row, segment), 64 / (D + 1) groups
+// per single-wave workgroup (jacobi.hpp); the occupancy cap follows the number of waves like every other hot kernel
+template <class Mdl>
+hipError_t jacobi(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double eps, int stride, int skip, int cap,
+                  double *tq, double *det, int *count, int *nchange, double *tconj, double *Jend)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0 || stride < 1 || skip < 0 || cap < 1) return hipErrorInvalidValue;
+    constexpr int gpw = 64 / (Mdl::D + 1);
+    const long slabs = (long)B * pb.M;
+    SOCP_PLUGIN_LAUNCH_PB_LDS(jacobi_group_kernel, false, (unsigned)((slabs + gpw - 1) / gpw), 0, st, P, pb, B, Z, eps, stride, skip, cap, tq, det,
+                              count, nchange, tconj, Jend);
+    return hipGetLastError();
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -215,6 +235,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
         static_assert(event_channels<Mdl>::value <= 16, "a watch's channel travels in four bits");
         t.event_channels = event_channels<Mdl>::value; t.events = &events<Mdl>;
     }
+    if constexpr (!has_custom_traj<Mdl>::value && !no_jacobi<Mdl>::value) t.jacobi = &jacobi<Mdl>;   // nor Jacobi fields (their chart changes rewrite the costate)
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

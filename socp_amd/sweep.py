@@ -339,6 +339,26 @@ def events_local(ctx, args, local, lo, rank, params=None):
             "signatures": signatures, "wall_s": wall, "file": path}
 
 
+def jacobi_local(ctx, args, local, lo, rank, params=None):
+    """--jacobi-out: the conjugate-time test (socp_jacobi_batch) of this rank's CONVERGED chains, each with its own parameter block
+    when the chains have one: det of J(t) = dx(t)/dp(t0) sampled every --jacobi-stride steps of every segment, its sign changes
+    from sample --jacobi-skip on.  Written to PATH.rank<r>.npz: index [k] = position of the chain in the sweep's start table,
+    tq [k][M][cap], det [k][M][cap], count [k][M], nchange [k][M], tconj [k][M] (NaN: none).  Runs after the timed solve.  Returns
+    the record entry of this rank: how many rows show a change and where the first ones lie -- a measuring instrument (the
+    classical statement is for single shooting, --segments 1), not a verdict."""
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.jacobi_out)
+    t0 = time.perf_counter()
+    r = ctx.jacobi_batch(z, stride=args.jacobi_stride, skip=args.jacobi_skip, blocks=None if own is None else (own, None, None))
+    r = {k: v.cpu().numpy() for k, v in r.items()}
+    wall = time.perf_counter() - t0
+    np.savez(path, index=index, tq=r["tq"], det=r["det"], count=r["count"], nchange=r["nchange"], tconj=r["tconj"])
+    changed = r["nchange"].sum(axis=1) > 0 if len(conv) else np.zeros(0, dtype=bool)
+    first = np.array([np.nanmin(row) for row in r["tconj"][changed]]) if changed.any() else np.zeros(0)
+    return {"rows": int(len(conv)), "with_change": int(changed.sum()), "tconj_min": float(first.min()) if len(first) else None,
+            "tconj_median": float(np.median(first)) if len(first) else None, "stride": args.jacobi_stride, "skip": args.jacobi_skip,
+            "wall_s": wall, "file": path}
+
+
 def tangent_local(ctx, args, local, lo, rank, params=None):
     """--tangent-out: the sensitivity dz/dtheta (socp_tangent_batch) of this rank's CONVERGED chains to the packed parameter
     --tangent-param, each chain with its own parameter block when the chains have one, written to PATH.rank<r>.npz: index [k] =
@@ -541,6 +561,15 @@ def main():
     ap.add_argument("--roots-atol", type=float, default=0.0, metavar="A", help="with --roots-out: the absolute tolerance (finite, >= 0)")
     ap.add_argument("--roots-max", type=int, default=1024, metavar="G",
                     help="with --roots-out: at most G groups (one device round per group); converged rows beyond them are counted as overflow")
+    ap.add_argument("--jacobi-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank runs the conjugate-time test of the converged chains of its own block in one "
+                         "batch (socp_jacobi_batch): the determinant of dx(t)/dp(t0) along every segment and its sign changes, with the "
+                         "chains' own parameter blocks; writes PATH.rank<r>.npz (index, tq, det, count, nchange, tconj) and adds jacobi "
+                         "{rows, with_change, tconj_min, tconj_median, stride, skip, wall_s, file} to the record.  Not with --model "
+                         "interceptor.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--jacobi-stride", type=int, default=100, metavar="K", help="with --jacobi-out: sample every K-th step (and the last)")
+    ap.add_argument("--jacobi-skip", type=int, default=1, metavar="S",
+                    help="with --jacobi-out: compare the samples from the S-th on (near t0 the difference matrix is singular to rounding)")
     ap.add_argument("--events-refine", type=int, default=2, metavar="R",
                     help="with --events-out: false-position steps per event, 0 .. 8 (0: linear interpolation over the step)")
     args = ap.parse_args()
@@ -548,6 +577,10 @@ def main():
         ap.error("--events-refine must be 0 .. 8")
     if args.events_out and args.model == "interceptor":
         ap.error("--events-out: the interceptor has no event channels (its own ComputeTraj rewrites the costate in mid-trajectory)")
+    if args.jacobi_out and args.model == "interceptor":
+        ap.error("--jacobi-out: the interceptor has no Jacobi-field kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
+    if args.jacobi_stride < 1 or args.jacobi_skip < 0:
+        ap.error("--jacobi-stride must be >= 1 and --jacobi-skip >= 0")
     if bool(args.regrid_out) != (args.regrid_segments > 0) or not 0 <= args.regrid_segments <= 255:
         ap.error("--regrid-segments M2 (1 .. 255) and --regrid-out PATH go together")
     if args.regrid_out and args.model == "interceptor":
@@ -662,6 +695,8 @@ def main():
         extra["events_rank%d" % rank] = events_local(ctx, args, local, lo_w, rank, blocks)
     if args.tangent_out:
         extra["tangent_rank%d" % rank] = tangent_local(ctx, args, local, lo_w, rank, blocks)
+    if args.jacobi_out:
+        extra["jacobi" if rank == 0 else "jacobi_rank%d" % rank] = jacobi_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
