@@ -492,7 +492,8 @@ int socp_var_jacobian_multi_dev(socp_ctx *ctx, int np, const double *d_Z, double
  * allocates, copies nor synchronises: the caller owns d_work.  The host forms stage through that stream, take the workspace from
  * the context's grow-only buffers and return when the results are in the caller's arrays.  _blocks: per-row blocks like
  * socp_residual_batch_blocks (any of params / time / xnode may be NULL); the context's own blocks are restored afterwards.
- * Not covered: no predictor inside socp_chains_solve, no condition estimate (info says singular, not ill-conditioned), one GPU. */
+ * Not covered: no predictor inside socp_chains_solve, one GPU.  info says singular, not ill-conditioned: how close J is to singular
+ * is what socp_singular_batch (below) reports. */
 size_t socp_tangent_work_bytes(const socp_ctx *ctx, int B, int K);
 int socp_tangent_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int K, const int *dir_kind, const int *dir_index,
                            double epsfcn, int jac, void *d_work, size_t work_bytes,
@@ -510,6 +511,73 @@ int socp_tangent_batch_blocks(socp_ctx *ctx, int B, const double *Z, const doubl
  * elimination); callers that need A afterwards keep a copy.
  * SOCP_ERR_ARG: B < 0, n < 1, K < 1, n above that bound, a NULL pointer with B > 0; B == 0: SOCP_OK without a launch.  One launch. */
 int socp_linsolve_batch_dev(socp_ctx *ctx, int B, int n, int K, double *d_A, double *d_Y, int *d_info);
+
+/* How close to singular: the singular values of B small dense matrices, and of the shooting Jacobians of a whole sweep.
+ *
+ * socp_svd_batch_dev is the linear-algebra half: model-independent (no problem has to be set), on the context's stream and in its
+ * variant, ONE launch, no allocation, no synchronisation.  A[B][n*n] column-major, left as it was -> sigma[B][n] descending,
+ * Vt[B][n][n] (may be NULL; row j is the right singular vector of sigma[j]), sweeps[B], info[B].  One-sided Jacobi (Hestenes)
+ * rotations on the ROWS of the matrix, per matrix:
+ *   start.    W = a copy of A; w_p = its row p (entries A[p + i n], i = 0 .. n-1);  tol = n DBL_EPSILON (the error bound of an n-term
+ *             dot product relative to |w_p| |w_q|: below it gamma is rounding noise).  An entry of A that is not finite: info = 2,
+ *             sweeps = 0, sigma and Vt all NaN.
+ *   schedule. round-robin, all pairs of a step disjoint:  m = n + (n & 1);  steps s = 0 .. m-2, slots k = 0 .. m/2-1;
+ *             k == 0: (a, b) = (m-1, s);  else a = (s + k) mod (m-1), b = (s - k + m - 1) mod (m-1);  p = min(a, b), q = max(a, b);
+ *             the pair is skipped when q >= n (the phantom row of an odd n).  Every pair p < q occurs exactly once per sweep.
+ *   pair.     alpha = sum w_pi^2, beta = sum w_qi^2, gamma = sum w_pi w_qi: each sum starts from +0.0 and adds one rounded product
+ *             at a time, i = 0 .. n-1.  No rotation when gamma == 0 or |gamma| <= fl(fl(tol sqrt(alpha)) sqrt(beta)).  Otherwise
+ *               zeta = (beta - alpha) / (2 gamma);  t = (zeta >= 0 ? 1 : -1) / (|zeta| + sqrt(1 + zeta zeta));
+ *               c = 1 / sqrt(1 + t t);  s = c t;   for every i: (w_pi, w_qi) <- (c w_pi - s w_qi, s w_pi + c w_qi)
+ *   sweep.    all m - 1 steps.  The first sweep in which no pair rotates ends the iteration: info = 0 and sweeps counts that sweep
+ *             too.  If sweep max_sweeps still rotated: info = 1, sweeps = max_sweeps, the outputs come from W as it stands.
+ *   finish.   sigma_p = sqrt(sum_i w_pi^2), the same sequential sum; ordered descending, equal values by ascending row, ranked by
+ *             counting (so the result does not depend on how the work is spread);  the Vt row = w_p / sigma_p, all zeros when
+ *             sigma_p == 0, then negated if its entry of largest magnitude (the first among equals) is negative.
+ * In reference-order contexts (SOCP_VARIANT_AUTO / LANE_EXACT) every operation is one IEEE rounding: no contraction, IEEE division
+ * and square root, so the result is reproducible bit for bit and does not depend on how matrices are batched.  In
+ * SOCP_VARIANT_LANE_FAST contexts the sums and the updates may be fused multiply-adds and the sums may take any order.
+ * The right singular vectors come without accumulating anything, as the normalised rows; left singular vectors are not produced.
+ * The matrix lives in LDS (row stride n | 1), with its n row norms and 32 bytes of flags: n <= 142 is the largest that fits the
+ * 160 KiB of a compute unit -- so not the n = 253 and 832 of the large chains.  Accuracy: |sigma^ - sigma| is of the order
+ * n DBL_EPSILON sigma_max (an ABSOLUTE bound; tests/test_svd_cpu.py measures it against LAPACK); the relative accuracy of small
+ * singular values is not promised.
+ * SOCP_ERR_ARG: B < 0, n < 1, max_sweeps outside 1 .. 1000, a NULL required pointer (A, sigma, sweeps, info) with B > 0;
+ * SOCP_ERR_UNSUPPORTED: n > 142;  B == 0: SOCP_OK without a launch.  An error writes nothing. */
+int socp_svd_batch_dev(socp_ctx *ctx, int B, int n, const double *d_A, int max_sweeps,
+                       double *d_sigma, double *d_Vt, int *d_sweeps, int *d_info);
+/* The model half: Z[B][n] -> sigma[B][n] descending, vmin[B][n] (the right singular vector of sigma[n-1]: the direction in which a
+ * branch turns at a fold), colnorm[B][n] (may be NULL), sweeps[B], info[B].  Per row b:
+ *   1. F0 = F(z; blocks)
+ *   2. J exactly as step 4 of socp_tangent_batch: jac == 0 the forward-difference Jacobian of socp_fd_jacobian_multi_dev at (z, F0)
+ *      with this epsfcn and dedup on; jac == 1 the variational Jacobian (a model without one: SOCP_ERR_UNSUPPORTED)
+ *   3. scale == 1: colnorm_j = sqrt(sum_i J_ij^2), the sum in the order i = 0 .. n-1; a zero is replaced by 1; J_ij <- J_ij / colnorm_j
+ *      (what MINPACK's mode = 1 scaling does with the first Jacobian);  scale == 0: colnorm = 1
+ *   4. the decomposition above; vmin = the last row of Vt.  With scale == 1 it is in the scaled variables: x_j = colnorm_j z_j.
+ * All models, both variants, both integrators: only the launch-table entries residual, fdjac and var_jacobian are used, so a plugin
+ * has the call without change.
+ * socp_singular_work_bytes: the bytes of d_work for B rows on this context's problem (0 without a problem or for B < 0): F[B][n],
+ * J[B][n*n] and, on a model with variational equations, what socp_var_jacobian_multi_dev integrates in.
+ * Launches of the _dev form: the residual; the Jacobian (1 launch, variational: 3); the column norms (only when scale == 1 or colnorm
+ * is given); the decomposition.  socp_ctx_counters advances by B M trajectories plus the Jacobian's (np T of the dedup list, or B M)
+ * and by 3 or 4 launches (variational: 5 or 6).
+ * SOCP_ERR_ARG: no problem set, B < 0, jac or scale outside 0 .. 1, max_sweeps outside 1 .. 1000, a NULL required pointer with B > 0
+ * (Z, sigma, vmin, sweeps, info, d_work), work_bytes below socp_singular_work_bytes, _blocks with params and param_stride !=
+ * nparams + 2;  B == 0: SOCP_OK without a launch;  SOCP_ERR_UNSUPPORTED: jac == 1 without variational equations, n > 142.  An error
+ * leaves the context unchanged and writes nothing.
+ * The _dev form takes device pointers, only enqueues on the context's stream and neither allocates, copies nor synchronises.  The
+ * host forms stage through that stream, take the workspace from the context's grow-only buffers and return when the results are in
+ * the caller's arrays.  _blocks: per-row blocks like socp_residual_batch_blocks (any of params / time / xnode may be NULL); the
+ * context's own blocks are restored afterwards.
+ * Not covered: left singular vectors; n above 142 (n = 253 and 832); one GPU; relative accuracy of small singular values. */
+size_t socp_singular_work_bytes(const socp_ctx *ctx, int B);
+int socp_singular_batch_dev(socp_ctx *ctx, int B, const double *d_Z, double epsfcn, int jac, int scale, int max_sweeps,
+                            void *d_work, size_t work_bytes, double *d_sigma, double *d_vmin, double *d_colnorm,
+                            int *d_sweeps, int *d_info);
+int socp_singular_batch(socp_ctx *ctx, int B, const double *Z, double epsfcn, int jac, int scale, int max_sweeps,
+                        double *sigma, double *vmin, double *colnorm, int *sweeps, int *info);
+int socp_singular_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
+                               const double *time, const double *xnode, double epsfcn, int jac, int scale, int max_sweeps,
+                               double *sigma, double *vmin, double *colnorm, int *sweeps, int *info);
 
 /* The distinct roots of a whole sweep: which distinct rows does a table hold, how many rows went to each, and which row went where.
  * Model-independent (no problem has to be set, no launch table is used).

@@ -160,6 +160,13 @@ def lib():
         L.socp_tangent_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, C.c_double, C.c_int, _dp, _ip,
                                                 _dp]
         L.socp_linsolve_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
+        L.socp_svd_batch_dev.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]
+        L.socp_singular_work_bytes.argtypes = [_vp, C.c_int]
+        L.socp_singular_work_bytes.restype = C.c_size_t
+        L.socp_singular_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_double, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]
+        L.socp_singular_batch.argtypes = [_vp, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip]
+        L.socp_singular_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp,
+                                                 _ip, _ip]
         L.socp_group_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]
         L.socp_group_batch.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _ip, C.c_double, C.c_double, C.c_int, _ip, _ip, _ip, _dp, _ip]
         L.socp_ctx_get_switching_times.argtypes = [_vp, _dp]
@@ -792,6 +799,38 @@ class Context:
         """Device pointers (ints): A[B][n*n] column-major, Y[B][K][n] overwritten by the solutions, info[B]; enqueue only
         (socp_linsolve_batch_dev)."""
         self._chk(self.L.socp_linsolve_batch_dev(self.h, int(B), int(n), int(K), _vp(d_A), _vp(d_Y), _vp(d_info)))
+
+    # -- batched singular values
+    def svd_batch_dev(self, B, n, d_A, max_sweeps, d_sigma, d_Vt, d_sweeps, d_info):
+        """Device pointers (ints; d_Vt may be None): A[B][n*n] column-major (left as it was) -> sigma[B][n] descending, Vt[B][n][n],
+        sweeps[B], info[B] (0: converged, 1: max_sweeps reached, 2: an entry is not finite); one launch, enqueue only
+        (socp_svd_batch_dev).  Needs no problem."""
+        self._chk(self.L.socp_svd_batch_dev(self.h, int(B), int(n), _vp(d_A), int(max_sweeps), _vp(d_sigma), _vp(d_Vt), _vp(d_sweeps),
+                                            _vp(d_info)))
+
+    def singular_work_bytes(self, B):
+        """Bytes of the workspace singular_batch_dev needs for B rows (socp_singular_work_bytes)."""
+        return int(self.L.socp_singular_work_bytes(self.h, int(B)))
+
+    def singular_batch_dev(self, B, d_Z, epsfcn, jac, scale, max_sweeps, d_work, work_bytes, d_sigma, d_vmin, d_colnorm, d_sweeps, d_info):
+        """Device pointers (ints; d_colnorm may be None); enqueue only, no allocation, no copy, no synchronise
+        (socp_singular_batch_dev)."""
+        self._chk(self.L.socp_singular_batch_dev(self.h, int(B), _vp(d_Z), float(epsfcn), int(jac), int(scale), int(max_sweeps), _vp(d_work),
+                                                 int(work_bytes), _vp(d_sigma), _vp(d_vmin), _vp(d_colnorm), _vp(d_sweeps), _vp(d_info)))
+
+    def singular_batch(self, Z, epsfcn=1e-15, jac=0, scale=1, max_sweeps=60, params=None, time=None, xnode=None):
+        """The singular values of the shooting Jacobian at every row of Z (jac=0 forward differences, jac=1 variational), its columns
+        brought to unit norm first when scale=1 (include/socp_hip.h has the definition).  Returns dict(sigma[B][n] descending,
+        vmin[B][n] (the right singular vector of the smallest one), colnorm[B][n], sweeps[B], info[B] (0: converged, 1: max_sweeps
+        reached, 2: a Jacobian entry is not finite)).  params / time / xnode: per-row blocks as in residual_batch_blocks."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        blocks = _block_args(B, params, time, xnode)
+        sigma, vmin, colnorm = (np.full((B, self.n), np.nan) for _ in range(3))
+        sweeps, info = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        self._chk(self.L.socp_singular_batch_blocks(self.h, B, _d(Z), *blocks, float(epsfcn), int(jac), int(scale), int(max_sweeps), _d(sigma),
+                                                    _d(vmin), _d(colnorm), sweeps.ctypes.data_as(_ip), info.ctypes.data_as(_ip)))
+        return dict(sigma=sigma, vmin=vmin, colnorm=colnorm, sweeps=sweeps, info=info)
 
     # -- row grouping
     def group_batch_dev(self, B, n, ld, d_V, d_mask, atol, rtol, max_groups, d_label, d_leader, d_count, d_radius, d_summary):

@@ -1576,6 +1576,140 @@ int socp_tangent_batch_blocks(socp_ctx *c, int B, const double *Z, const double 
                        [&] { return socp_tangent_batch(c, B, Z, K, dir_kind, dir_index, epsfcn, jac, dZ, info, Fp); });
 }
 
+/* ---- batched singular values ----------------------------------------------------------------- */
+
+namespace {
+// the workspace of socp_singular_batch_dev, in doubles from its start: the residual rows, the Jacobians (scaled in place), then what
+// the variational Jacobian integrates in (models that have one)
+struct SingularWork {
+    size_t F, J, var, total;
+};
+
+SingularWork singular_layout(const socp_ctx *c, int B)
+{
+    const size_t n = c->n;
+    SingularWork w{};
+    size_t at = 0;
+    auto take = [&](size_t count) { const size_t here = at; at += (count + 1) & ~(size_t)1; return here; };      // 16-byte aligned pieces
+    w.F = take((size_t)B * n);
+    w.J = take((size_t)B * n * n);
+    w.var = take(has_var(c) ? var_work_doubles(c, B) : 0);
+    w.total = at;
+    return w;
+}
+
+bool svd_sweeps_ok(int max_sweeps) { return max_sweeps >= 1 && max_sweeps <= 1000; }
+
+int singular_args(socp_ctx *c, const char *who, int B, int jac, int scale, int max_sweeps)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (jac != 0 && jac != 1) return fail(c, SOCP_ERR_ARG, w + ": jac must be 0 (forward differences) or 1 (variational)");
+    if (scale != 0 && scale != 1) return fail(c, SOCP_ERR_ARG, w + ": scale must be 0 (J as it is) or 1 (columns of unit norm)");
+    if (!svd_sweeps_ok(max_sweeps)) return fail(c, SOCP_ERR_ARG, w + ": 1 <= max_sweeps <= 1000 is required");
+    if (jac == 1 && !has_var(c))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": this model has no variational equations (modelOrder 0): jac = 1 needs them");
+    if (!svd_fits(c->n))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": too many unknowns for the batched singular values (n <= " + std::to_string(kSvdMaxN) + ": the matrix must fit 160 KiB of LDS)");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_svd_batch_dev(socp_ctx *c, int B, int n, const double *d_A, int max_sweeps, double *d_sigma, double *d_Vt, int *d_sweeps,
+                       int *d_info)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (B < 0 || n < 1 || !svd_sweeps_ok(max_sweeps))
+        return fail(c, SOCP_ERR_ARG, "svd_batch: B >= 0, n >= 1 and 1 <= max_sweeps <= 1000 are required");
+    if (B > 0 && (!d_A || !d_sigma || !d_sweeps || !d_info)) return fail(c, SOCP_ERR_ARG, "svd_batch: null argument");
+    if (!svd_fits(n))
+        return fail(c, SOCP_ERR_UNSUPPORTED, "svd_batch: n <= " + std::to_string(kSvdMaxN) + " is required (the matrix must fit 160 KiB of LDS)");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_launch += 1;
+    HIP_TRY(c, (c->variant == SOCP_VARIANT_LANE_FAST ? svd_fast : svd)(c->stream, B, n, d_A, max_sweeps, d_Vt ? 1 : 0, d_sigma, d_Vt, d_sweeps,
+                                                                       d_info));
+    return SOCP_OK;
+}
+
+size_t socp_singular_work_bytes(const socp_ctx *c, int B)
+{
+    if (!c || !c->has_problem || B < 0) return 0;
+    return sizeof(double) * singular_layout(c, B).total;
+}
+
+int socp_singular_batch_dev(socp_ctx *c, int B, const double *d_Z, double epsfcn, int jac, int scale, int max_sweeps, void *d_work,
+                            size_t work_bytes, double *d_sigma, double *d_vmin, double *d_colnorm, int *d_sweeps, int *d_info)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc = singular_args(c, "singular_batch", B, jac, scale, max_sweeps);
+    if (rc != SOCP_OK) return rc;
+    if (B > 0 && (!d_Z || !d_work || !d_sigma || !d_vmin || !d_sweeps || !d_info)) return fail(c, SOCP_ERR_ARG, "singular_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    const SingularWork w = singular_layout(c, B);
+    if (work_bytes < sizeof(double) * w.total) return fail(c, SOCP_ERR_ARG, "singular_batch: the workspace is smaller than socp_singular_work_bytes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool fast = c->variant == SOCP_VARIANT_LANE_FAST;
+    double *wk = static_cast<double *>(d_work), *wF = wk + w.F, *wJ = wk + w.J;
+    // launch 1: F0; then the Jacobian at (z, F0) (1 launch, variational: 3), each row with its own blocks
+    HIP_TRY(c, run_residual(c, B, d_Z, wF));
+    if (jac == 0) {
+        const int r = socp_fd_jacobian_multi_dev(c, B, d_Z, wF, epsfcn, wJ, 1);
+        if (r != SOCP_OK) return r;
+    } else {
+        HIP_TRY(c, run_var_jacobian(c, B, d_Z, wk + w.var, wJ));
+    }
+    // the column norms (only when something is to be scaled or reported), then the decomposition
+    if (scale || d_colnorm) {
+        c->n_launch += 1;
+        HIP_TRY(c, (fast ? svd_colscale_fast : svd_colscale)(c->stream, B, c->n, scale, wJ, d_colnorm));
+    }
+    c->n_launch += 1;
+    HIP_TRY(c, (fast ? svd_fast : svd)(c->stream, B, c->n, wJ, max_sweeps, 2, d_sigma, d_vmin, d_sweeps, d_info));
+    return SOCP_OK;
+}
+
+int socp_singular_batch(socp_ctx *c, int B, const double *Z, double epsfcn, int jac, int scale, int max_sweeps, double *sigma, double *vmin,
+                        double *colnorm, int *sweeps, int *info)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = singular_args(c, "singular_batch", B, jac, scale, max_sweeps);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B > 0 && (!Z || !sigma || !vmin || !sweeps || !info)) return fail(c, SOCP_ERR_ARG, "singular_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nZ = (size_t)B * c->n, nC = colnorm ? nZ : 0, bytes = socp_singular_work_bytes(c, B);
+    double *d_Z;
+    HIP_TRY(c, c->s_var.reserve(bytes));
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (2 * nZ + nC) + sizeof(int) * 2 * (size_t)B));
+    double *dS = c->s_out.as<double>(), *dV = dS + nZ, *dC = dV + nZ;
+    int *dW = reinterpret_cast<int *>(dC + nC), *dI = dW + B;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, d_Z));
+    const int rc = socp_singular_batch_dev(c, B, d_Z, epsfcn, jac, scale, max_sweeps, c->s_var.p, bytes, dS, dV, colnorm ? dC : nullptr, dW, dI);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, sigma, dS, nZ));
+    HIP_TRY(c, copy_down(c, vmin, dV, nZ));
+    if (colnorm) HIP_TRY(c, copy_down(c, colnorm, dC, nC));
+    HIP_TRY(c, copy_down(c, sweeps, dW, (size_t)B));
+    HIP_TRY(c, copy_down(c, info, dI, (size_t)B));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_singular_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                               const double *xnode, double epsfcn, int jac, int scale, int max_sweeps, double *sigma, double *vmin,
+                               double *colnorm, int *sweeps, int *info)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = singular_args(c, "singular_batch_blocks", B, jac, scale, max_sweeps);
+    if (rc0 != SOCP_OK) return rc0;
+    if (const int rc = blocks_stride(c, "singular_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !sigma || !vmin || !sweeps || !info)) return fail(c, SOCP_ERR_ARG, "singular_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_singular_batch(c, B, Z, epsfcn, jac, scale, max_sweeps, sigma, vmin, colnorm, sweeps, info); });
+}
+
 /* ---- row grouping --------------------------------------------------------------------------- */
 
 namespace {

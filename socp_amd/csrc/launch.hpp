@@ -104,6 +104,37 @@ hipError_t tangent_diff_fast(hipStream_t st, int B, int K, int n, const double *
 // A[B][n*n] column-major, Y[B][K][n] -> the solutions in Y, info[B]; hipErrorInvalidValue unless linsolve_fits(n, K)
 hipError_t linsolve(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
 hipError_t linsolve_fast(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
+// socp_svd_batch_dev / socp_singular_batch (kernels_svd.hip, built once per flavour like kernels_tangent.hip).  One matrix per team
+// of L lanes, a lane per pair of rows; T teams per workgroup; the matrix, its n row norms and kSvdFlags doubles of flags in LDS
+constexpr int kSvdLdsBytes = 160 * 1024;             // the LDS of a CU: the most one workgroup can take
+constexpr int kSvdFlags = 4;                          // doubles per team behind its row norms: eight int flags
+constexpr int kSvdMaxN = 142;                         // the largest n whose matrix (row stride n | 1), norms and flags fit kSvdLdsBytes
+inline size_t svd_team_bytes(int n) { return sizeof(double) * ((size_t)n * (n | 1) + n + kSvdFlags); }
+inline bool svd_fits(int n) { return n >= 1 && svd_team_bytes(n) <= (size_t)kSvdLdsBytes; }
+// L: the power of two that holds the (n + (n & 1)) / 2 pairs of a step (so a lane owns at most two rows in the finish)
+inline int svd_lanes(int n)
+{
+    int L = 1;
+    while (L < (n + (n & 1)) / 2) L *= 2;
+    return L;
+}
+// T: the teams that fill a wavefront, halved while they take more than half a CU's LDS (two workgroups then share a CU)
+inline int svd_teams(int n)
+{
+    int T = svd_lanes(n) >= 64 ? 1 : 64 / svd_lanes(n);
+    while (T > 1 && T * svd_team_bytes(n) > (size_t)kSvdLdsBytes / 2) T /= 2;
+    return T;
+}
+inline size_t svd_lds_bytes(int n) { return svd_teams(n) * svd_team_bytes(n); }
+// A[B][n*n] column-major (left as it was) -> sigma[B][n], sweeps[B], info[B] and, by vt_mode, 0: nothing, 1: Vt[B][n][n], 2: only
+// the row of the smallest singular value, Vt[B][n]; hipErrorInvalidValue unless svd_fits(n)
+hipError_t svd(hipStream_t st, int B, int n, const double *A, int max_sweeps, int vt_mode, double *sigma, double *Vt, int *sweeps, int *info);
+hipError_t svd_fast(hipStream_t st, int B, int n, const double *A, int max_sweeps, int vt_mode, double *sigma, double *Vt, int *sweeps,
+                    int *info);
+// J[B][n*n] column-major: scale != 0: colnorm[b][j] = the norm of column j (a zero: 1) and the column divided by it, in place;
+// scale == 0: colnorm = 1.  colnorm may be null
+hipError_t svd_colscale(hipStream_t st, int B, int n, int scale, double *J, double *colnorm);
+hipError_t svd_colscale_fast(hipStream_t st, int B, int n, int scale, double *J, double *colnorm);
 // socp_group_batch (kernels_group.hip; flavour- and model-independent, built without contraction).  next[max_groups + 1]: the
 // "next leader" words -- next[g] is the leader of round g (INT_MAX: no row is left), written by group_begin (g = 0) and by round g - 1
 // group_begin: leader / count / radius / summary / next filled, label = MASKED or unassigned (= OVERFLOW), next[0] = the first leader

@@ -379,6 +379,28 @@ def tangent_local(ctx, args, local, lo, rank, params=None):
             "median_norm_dz": float(np.median(np.linalg.norm(dz[solved], axis=1))) if solved.any() else None, "wall_s": wall, "file": path}
 
 
+def singular_local(ctx, args, local, lo, rank, params=None):
+    """--sing-out: the singular values of the shooting Jacobian (socp_singular_batch) at this rank's CONVERGED chains, each with its
+    own parameter block when the chains have one; --sing-scale 1 brings the columns to unit norm first.  Written to PATH.rank<r>.npz:
+    index [k] = position of the chain in the sweep's start table, sigma [k][n] descending, vmin [k][n] (the right singular vector of
+    the smallest one), colnorm [k][n], sweeps [k], info [k] (0: converged).  Runs after the timed solve.  Returns the record entry of
+    this rank: how close to singular the roots the sweep found are."""
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.sing_out)
+    t0 = time.perf_counter()
+    r = ctx.singular_batch(z, scale=args.sing_scale, max_sweeps=args.sing_sweeps, params=own)
+    wall = time.perf_counter() - t0
+    np.savez(path, index=index, sigma=r["sigma"], vmin=r["vmin"], colnorm=r["colnorm"], sweeps=r["sweeps"], info=r["info"])
+    good = r["info"] == 0
+    smin = r["sigma"][good, -1]
+    with np.errstate(divide="ignore"):
+        cond = r["sigma"][good, 0] / smin
+    some = bool(good.any())
+    return {"rows": int(len(conv)), "not_converged": int(np.sum(~good)), "sigma_min_min": float(smin.min()) if some else None,
+            "sigma_min_median": float(np.median(smin)) if some else None, "cond_median": float(np.median(cond)) if some else None,
+            "cond_max": float(cond.max()) if some else None, "scale": args.sing_scale, "max_sweeps": args.sing_sweeps, "wall_s": wall,
+            "file": path}
+
+
 def roots_global(ctx, args, table, n, with_cost=False, leader_blocks=None):
     """--roots-out: the distinct roots of the WHOLE sweep (socp_group_batch), on rank 0 from the gathered table [P][n+3] as it is:
     ld = n + 3, mask = (info == 1), grouping on the unknown vectors z only, greedy in start order.  Written to PATH.npz: label [P]
@@ -570,6 +592,15 @@ def main():
     ap.add_argument("--jacobi-stride", type=int, default=100, metavar="K", help="with --jacobi-out: sample every K-th step (and the last)")
     ap.add_argument("--jacobi-skip", type=int, default=1, metavar="S",
                     help="with --jacobi-out: compare the samples from the S-th on (near t0 the difference matrix is singular to rounding)")
+    ap.add_argument("--sing-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank computes the singular values of the shooting Jacobian at the converged chains "
+                         "of its own block in one batch (socp_singular_batch), with the chains' own parameter blocks; writes "
+                         "PATH.rank<r>.npz (index, sigma, vmin, colnorm, sweeps, info) and adds singular {rows, not_converged, "
+                         "sigma_min_min, sigma_min_median, cond_median, cond_max, scale, max_sweeps, wall_s, file} to the record.  Not "
+                         "with --model interceptor.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--sing-scale", type=int, default=1, metavar="0|1",
+                    help="with --sing-out: 1 brings the Jacobian's columns to unit norm first (MINPACK's mode 1 scaling), 0 takes it as it is")
+    ap.add_argument("--sing-sweeps", type=int, default=60, metavar="N", help="with --sing-out: at most N Jacobi sweeps, 1 .. 1000")
     ap.add_argument("--events-refine", type=int, default=2, metavar="R",
                     help="with --events-out: false-position steps per event, 0 .. 8 (0: linear interpolation over the step)")
     args = ap.parse_args()
@@ -593,6 +624,12 @@ def main():
         from .capi import GODDARD_PARAM_NAMES            # (the module only: the library is loaded by the first context)
         if args.tangent_param not in GODDARD_PARAM_NAMES:
             ap.error("--tangent-param: not a name of the packed parameter block (%s)" % ", ".join(GODDARD_PARAM_NAMES))
+    if args.sing_out and args.model == "interceptor":
+        ap.error("--sing-out is implemented for the Goddard sweeps")
+    if args.sing_scale not in (0, 1):
+        ap.error("--sing-scale must be 0 or 1")
+    if not 1 <= args.sing_sweeps <= 1000:
+        ap.error("--sing-sweeps must be 1 .. 1000")
     if args.roots_max < 1:
         ap.error("--roots-max must be >= 1")
     if not (np.isfinite(args.roots_rtol) and args.roots_rtol >= 0):
@@ -697,6 +734,8 @@ def main():
         extra["tangent_rank%d" % rank] = tangent_local(ctx, args, local, lo_w, rank, blocks)
     if args.jacobi_out:
         extra["jacobi" if rank == 0 else "jacobi_rank%d" % rank] = jacobi_local(ctx, args, local, lo_w, rank, blocks)
+    if args.sing_out:
+        extra["singular" if rank == 0 else "singular_rank%d" % rank] = singular_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
