@@ -201,13 +201,15 @@ class Oracle:
         self.lib.orc_interceptor_init_analytical(C.byref(self.m), C.c_double(ti), _d(Xi), C.c_double(tf), _d(Xf))
         return Xi
 
-    def traj_dopri5(self, t0, X0, tf, tol):
-        """Adaptive Dormand-Prince segment, initial step (tf - t0)/stepNbr. Returns (Xf, accepted, rejected)."""
+    def traj_dopri5(self, t0, X0, tf, tol, is_jac=0):
+        """Adaptive Dormand-Prince segment, initial step (tf - t0)/stepNbr; is_jac = 1: on the augmented state [X ; dX/dX0].
+        Returns (Xf, accepted, rejected)."""
         X = np.array(X0, dtype=np.float64)
         rej = C.c_long(0)
-        self.lib.orc_integrate_dopri5.restype = C.c_long
-        n = self.lib.orc_integrate_dopri5(C.byref(self.m), _d(X), C.c_double(t0), C.c_double(tf),
-                                          C.c_double((tf - t0) / self.m.step_nbr), C.c_double(tol), C.byref(rej))
+        fn = self.lib.orc_integrate_dopri5_jac if is_jac else self.lib.orc_integrate_dopri5
+        fn.restype = C.c_long
+        n = fn(C.byref(self.m), _d(X), C.c_double(t0), C.c_double(tf),
+               C.c_double((tf - t0) / self.m.step_nbr), C.c_double(tol), C.byref(rej))
         return X, n, rej.value
 
     def integrate_batch(self, t0, tf, X0, aux_sw=None, is_jac=0):

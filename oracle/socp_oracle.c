@@ -418,7 +418,8 @@ static int dopri5_try_step(const orc_model *m, int n, int is_jac, const double *
 
 /* the same on the AUGMENTED state [X ; dX/dX0] (is_jac = 1): with -D_USE_BOOST every integrate() call of the reference goes through
  * the adaptive stepper, the variational trajectories of the hybrj path included (odeTools.cpp:129-134, model.hpp:395-414,
- * shooting.cpp:996-1130), the error norm taken over all (2d + 1) 2d entries.  [ext] parity unpinned like the state-only form. */
+ * shooting.cpp:996-1130), the error norm taken over all (2d + 1) 2d entries.  [ext] like the state-only form: pinned to the
+ * published pair and to a 240-bit replay (tests/test_dopri5_pin_cpu.py), agreement with Boost's own code unverified. */
 static long integrate_dopri5_any(orc_model *m, int is_jac, double *X, double t0, double tf, double dt, double tol, long *rejected,
                                  orc_step_hook hook);
 

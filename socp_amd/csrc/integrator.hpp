@@ -100,7 +100,11 @@ struct Lane {
 
     // ---- adaptive Dormand-Prince 5(4), what the reference runs when built with -D_USE_BOOST:
     // integrate_adaptive(make_dense_output<runge_kutta_dopri5>(tol, tol), ode, X, t0, tf, dt) (odeTools.cpp:129-134).
-    // [ext] Boost.Odeint is not vendored; restated from its published algorithm: FSAL stages
+    // [ext] Boost.Odeint is not vendored; restated from its published algorithm.  PINNED: the tableau to the
+    // published Dormand-Prince pair (order conditions in rational arithmetic, SciPy's copy) and every stage sum, the error estimate
+    // and every controller decision to a 240-bit step-by-step replay of this loop, at rounding level (tests/dopri5_reference.py,
+    // tests/test_gpu_dopri5_pin.py).  NOT verified: agreement with Boost's own code.  The interceptor's compute_traj drives this
+    // same template through its chart-change hook and is not pinned by scenarios of its own; vtolUAV is not pinned either.  FSAL stages
     // summed left to right, error max_i |e_i| / (tol + tol (|x_i| + dt |k1_i|)) on the OLD state, reject ->
     // dt *= max(0.9 err^-1/3, 0.2), accept with err < 0.5 -> dt *= 0.9 max(5^-5, err)^-1/5, stepping while
     // t + dt <= tf and finishing with dt = tf - t.  Step control is PER LANE: lanes of a wave take different

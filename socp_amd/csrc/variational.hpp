@@ -82,7 +82,11 @@ __global__ __launch_bounds__(64) void traj_var_wave_kernel(ModelParams P, const 
 // over all (s + 1) s entries.  One wavefront per trajectory as above, step control PER WAVE: every lane computes its elements'
 // share of the norm, a wave-wide maximum makes it uniform, and the whole wave accepts, rejects and resizes together.  The
 // controller, the stage sums and the step budget are those of Lane::dopri5_try / integrate_dopri5 (integrator.hpp) element for
-// element -- a restatement of Boost.Odeint's published algorithm, [ext] PARITY UNPINNED.
+// element -- a restatement of Boost.Odeint's published algorithm [ext].  This SECOND text of the tableau and the
+// controller is pinned like the first: the end states of saturated 156-element segments to a 240-bit replay of the whole loop, within
+// a derived rounding-level bound (tests/test_gpu_dopri5_pin.py).  The sensitivity elements of the double integrator are polynomial
+// in t and carry no truncation error, so the wave maximum is exercised from the state lanes only; the pp_params path has no door
+// that hands out an end state and is not pinned.  Agreement with Boost's own code remains unverified.
 template <class Mdl>
 __global__ __launch_bounds__(64) void traj_var_wave_dopri5_kernel(ModelParams P, const double *__restrict__ t0,
                                                                   const double *__restrict__ tf,

@@ -380,8 +380,9 @@ def test_dopri5_fast_flavour_agrees_with_reference_order(gctx, gfast):
 @pytest.mark.parametrize("flavour", ["exact", "fast"])
 def test_dopri5_dense_output_is_the_integrators_own_steps(goracle, flavour):
     """The observer form of the reference's adaptive integrate() (odeTools.cpp:103-123, Boost branch at :108): the trace of an
-    adaptive segment is the state at t0 and at the end of every ACCEPTED step.  Parity UNPINNED (no Boost
-    offline): checked by construction -- in the reference-order flavour the last row is the plain adaptive result bit for bit
+    adaptive segment is the state at t0 and at the end of every ACCEPTED step.  The algorithm itself is pinned at
+    rounding level by tests/test_gpu_dopri5_pin.py (accepted times, states and row counts of short segments against a 240-bit
+    replay; agreement with Boost's own code unverified, no Boost offline).  Here, on the whole flight, by construction -- in the reference-order flavour the last row is the plain adaptive result bit for bit
     (same arithmetic, same step-size decisions; the throughput flavour is contracted per kernel instantiation: rounding level),
     the rows sit on the trajectory (a fine fixed-step solution integrated to each row's time) within 100 x tol, and the number of
     steps is the restatement's (+-1: `pow` in the controller rounds differently on the device)."""
