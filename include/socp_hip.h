@@ -579,6 +579,105 @@ int socp_singular_batch_blocks(socp_ctx *ctx, int B, const double *Z, const doub
                                const double *time, const double *xnode, double epsfcn, int jac, int scale, int max_sweeps,
                                double *sigma, double *vmin, double *colnorm, int *sweeps, int *info);
 
+/* Past a fold: pseudo-arclength (Keller) predictor-corrector continuation of B rows at once.  [ext] The reference moves a parameter
+ * by natural-parameter homotopy (shooting.cpp:598-778; socp_chains_solve): it asks for the root at the NEXT parameter value, which
+ * does not exist behind a fold of the branch.  Here the parameter is an unknown like the others and the branch is followed by its
+ * arclength, so a fold is a point like any other.  What indirect-methods tools with a path-following layer (HamPath) do.
+ *
+ * Setting.  ONE direction (dir_kind, dir_index) for the call, with the meaning and the range checks of socp_tangent_batch; theta is
+ * that ONE entry of a row's blocks (its own when per-row blocks are in force, the shared tables otherwise).  The internal unknown is
+ * y = (z_0 .. z_{n-1}, lambda) with lambda = theta / wtheta: the caller's scale wtheta > 0 makes arclength meaningful when theta is
+ * ~310 and costates ~1e-2 (1.0: no scaling).  EVERY evaluation uses theta = fl(lambda wtheta), point 0's included, with
+ * lambda_0 = fl(theta_block / wtheta): with wtheta != 1 the start may be evaluated one ulp from the block's value. */
+typedef struct socp_branch_options {
+    double epsfcn;      /* the step rule of the differences, as socp_tangent_batch */
+    int jac;            /* 0 forward-difference Jacobian, 1 variational */
+    double wtheta;      /* the scale above: > 0 and finite */
+    int dir;            /* +1 or -1: the initial orientation in theta */
+    double h0, hmin, hmax, grow;   /* arclength step: the first, the smallest (below it: STEP_TOO_SMALL), the largest, the growth factor >= 1 */
+    int kfast;          /* a step accepted with at most this many corrector updates lets h grow */
+    int max_corr;       /* corrector updates allowed per step */
+    double ftol;        /* acceptance bar on ||F||inf */
+    int have_goal;      /* != 0: stop when theta crosses goal */
+    double goal;
+    int cap;            /* points kept per row, >= 2 */
+    int rounds;         /* number of rounds */
+} socp_branch_options;
+#define SOCP_BRANCH_RUNNING        0   /* the rounds ran out; the accepted points are valid, call again from the last one to go on */
+#define SOCP_BRANCH_REACHED        1   /* the goal was crossed */
+#define SOCP_BRANCH_FULL           2   /* cap points recorded */
+#define SOCP_BRANCH_STEP_TOO_SMALL 3   /* h fell below hmin */
+#define SOCP_BRANCH_SINGULAR       4   /* the tangent system was singular (a bifurcation is reported, not resolved) */
+#define SOCP_BRANCH_BAD_START      5   /* F at the start is not finite */
+/* Z[B][n] -> per row: Y[B][cap][n+1] (z then theta of every accepted point; unused slots NaN), ttheta[B][cap] (the unit tangent's
+ * lambda-component at that point), rnorm[B][cap] (||F||inf there), count[B], nfold[B], ifold[B] (index of the first point behind the
+ * first fold, -1 if none), status[B], nreject[B], hlast[B] (the step length the row holds at the end), zgoal[B][n] (may be NULL;
+ * NaN unless REACHED).
+ * One ROUND, for every row that is not finished; v is its evaluation point, y its last accepted point, t the unit tangent there, h the
+ * step length, k the number of corrector updates of this step:
+ *   1. evaluate at v, with e, h_theta and the moved value exactly as steps 1-3 of socp_tangent_batch on theta = fl(v_n wtheta):
+ *      F0 = F(v_z; theta), F1 = F(v_z; theta + h_theta) from ONE residual launch of 2B rows with expanded block rows;
+ *      g_i = fl(fl(fl(F1_i - F0_i) / h_theta) wtheta);  J exactly as step 4 of socp_tangent_batch at (v_z, F0) under the SAME expanded
+ *      blocks (so the base row's theta is the state's, not the caller's)
+ *   2. rn = max_i |F0_i|; a NaN when an entry is one
+ *   3. the bordered matrix M, (n+1) x (n+1): rows 0 .. n-1 = [J | g], row n = t^T (in a row's first round: dir e_{n+1}^T).  ONE
+ *      elimination serves every case: step 6 of socp_tangent_batch with size n + 1 and K = 1; only the right-hand side differs
+ *   4. start (the row's first round; v = (z, lambda_0)): rn not finite: BAD_START, nothing recorded.  Otherwise M tau = e_{n+1},
+ *        s = sum tau_i^2 (sequential, i = 0 .. n, from +0.0), t = tau / sqrt(s).  Point 0 is recorded (y = v, rnorm = rn, no acceptance
+ *        test).  info != 0, or s zero or not finite: SINGULAR, ttheta[0] stays NaN.  Otherwise h = h0 and predict.
+ *      accept (rn <= ftol): y <- v; t' from M tau = e_{n+1} as above -- row n is the OLD t, so t'.t > 0: the orientation is carried
+ *        along the branch and through folds.  The point is recorded.  Singular: SINGULAR, its ttheta stays NaN, nothing below happens.
+ *        fold: signbit(t'_n) != signbit(t_n): nfold += 1, ifold = this point's index if it was -1.
+ *        growth: k <= kfast: h = min(fl(h grow), hmax).
+ *        goal (have_goal): a = theta_prev - goal, b = theta_now - goal (the recorded thetas); REACHED if b == 0, or a != 0 and
+ *        (a < 0) != (b < 0); then zgoal = z_prev + w (z_now - z_prev), w = (goal - theta_prev) / (theta_now - theta_prev).
+ *        Otherwise count == cap: FULL.  Otherwise t <- t' and predict.
+ *      reject (rn not finite, or k == max_corr): nreject += 1, h <- h / 2; h < hmin: STEP_TOO_SMALL; y, t and the records stay;
+ *        otherwise predict.
+ *      correct (otherwise): M delta = (-F0, 0); dn = sqrt(sum delta_i^2), the same sequential sum; info != 0 or !(dn <= h): handled as
+ *        reject (the distance guard that keeps Newton from jumping to another branch).  Otherwise v <- v + delta, k += 1.  Every delta
+ *        is orthogonal to t: v stays in the hyperplane through the predictor.
+ *      predict: v_i = y_i + fl(h t_i), k = 0.
+ *   5. a finished row (status != 0) changes nothing any more; after `rounds` rounds an unfinished row is RUNNING.
+ * In reference-order contexts every operation above is one IEEE rounding (no contraction, IEEE division and square root): the call
+ * is a fixed sequence of roundings, independent of how rows are batched and of what the other rows do (tests/branch_reference.py
+ * restates it in numpy).  SOCP_VARIANT_LANE_FAST contexts may fuse products and sums; as built they do so only in the model's own
+ * launches (residual, Jacobian): the steps above -- the bordered matrix, the elimination, the state machine -- run in reference order in
+ * both flavours, so a throughput path deviates from the reference-order one by what its residual and Jacobian deviate, and no more.  Finished rows are still integrated (their
+ * results are not used): no output depends on it.
+ * All models, plugins included, both variants, both integrators: only the launch-table entries residual, fdjac and var_jacobian are
+ * used.  A Goddard smooth-law promise covers the moved blocks unless the direction is mu2 itself.
+ * socp_branch_work_bytes: the bytes of d_work for B rows (0 without a problem or for B < 0): the block rows, unknowns and residual
+ * rows of the 2B launched rows, J[B][n*n], M[B][(n+1)^2], the right-hand sides, the row state, and on a model with variational
+ * equations what socp_var_jacobian_multi_dev integrates in.
+ * Launches of the _dev form, per round: expand; ONE residual launch of 2B rows; the Jacobian (1 launch, variational: 3); assemble; the
+ * elimination; update.  socp_ctx_counters advances per round by 2 B M trajectories plus the Jacobian's (np T of the dedup list, or
+ * B M) and by 6 launches (variational: 8).
+ * SOCP_ERR_ARG: no problem set, B < 0, a bad kind or index, jac outside 0 .. 1, a NULL options pointer, wtheta <= 0 or not finite, dir
+ * not +-1, !(0 < hmin <= h0 <= hmax), grow < 1 (or NaN), max_corr < 1, kfast < 0, !(ftol > 0), cap < 2, rounds < 1, a NULL required
+ * pointer with B > 0 (all but zgoal), work_bytes below socp_branch_work_bytes, _blocks with params and param_stride != nparams + 2;
+ * SOCP_ERR_UNSUPPORTED: jac == 1 without variational equations, n + 1 beyond the elimination's bound;  B == 0: SOCP_OK without a
+ * launch.  An error writes nothing and leaves the context unchanged.
+ * The _dev form takes device pointers (the direction and the options are host values that travel as kernel arguments), only
+ * enqueues on the context's stream -- exactly `rounds` rounds, no host decision between them -- and neither allocates, copies nor
+ * synchronises.  The host forms stage through that stream and the context's grow-only buffers; they may stop early: the update
+ * kernel leaves the number of unfinished rows in a word of the workspace, the host reads it back every 8 rounds and stops when it is
+ * 0 (the counters then advance by the rounds that ran).  Their results equal the _dev form's with all rounds, since a finished row
+ * changes nothing.  _blocks: per-row blocks like socp_residual_batch_blocks; the context's own blocks are restored afterwards.
+ * Not covered: no change to socp_chains_solve; no branch switching at bifurcations; no resuming of a RUNNING row other than calling
+ * again from its last point; one GPU. */
+size_t socp_branch_work_bytes(const socp_ctx *ctx, int B);
+int socp_branch_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int dir_kind, int dir_index, const socp_branch_options *opt,
+                          void *d_work, size_t work_bytes, double *d_Y, double *d_ttheta, double *d_rnorm, int *d_count, int *d_nfold,
+                          int *d_ifold, int *d_status, int *d_nreject, double *d_hlast, double *d_zgoal);
+int socp_branch_batch(socp_ctx *ctx, int B, const double *Z, int dir_kind, int dir_index, const socp_branch_options *opt,
+                      double *Y, double *ttheta, double *rnorm, int *count, int *nfold, int *ifold, int *status, int *nreject,
+                      double *hlast, double *zgoal);
+int socp_branch_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                             const double *xnode, int dir_kind, int dir_index, const socp_branch_options *opt,
+                             double *Y, double *ttheta, double *rnorm, int *count, int *nfold, int *ifold, int *status, int *nreject,
+                             double *hlast, double *zgoal);
+
 /* The distinct roots of a whole sweep: which distinct rows does a table hold, how many rows went to each, and which row went where.
  * Model-independent (no problem has to be set, no launch table is used).
  * Rows V[B][ld]; the first n <= ld entries of a row are compared.  Greedy leader grouping IN ROW ORDER:

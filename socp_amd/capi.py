@@ -27,6 +27,7 @@ REQ_DONE, REQ_FVEC, REQ_JAC = 0, 1, 2
 INT_RK4, INT_DOPRI5 = 0, 1
 GODDARD_PARAM_NAMES = ["C", "b", "KD", "kr", "u_max", "mu1", "mu2", "singularControl"]
 DIR_PARAM, DIR_TIME, DIR_XNODE = 0, 1, 2      # what a direction of tangent_batch addresses (SOCP_DIR_*)
+BRANCH_RUNNING, BRANCH_REACHED, BRANCH_FULL, BRANCH_STEP_TOO_SMALL, BRANCH_SINGULAR, BRANCH_BAD_START = range(6)      # status of branch_batch (SOCP_BRANCH_*)
 GROUP_OVERFLOW, GROUP_NOTFINITE, GROUP_MASKED = -1, -2, -3      # the negative labels of group_batch (SOCP_GROUP_*)
 
 _dp = C.POINTER(C.c_double)
@@ -51,6 +52,20 @@ class ChainOptions(C.Structure):
                 ("xtol", C.c_double), ("maxfev", C.c_int), ("epsfcn", C.c_double), ("factor", C.c_double),
                 ("dedup", C.c_int), ("speculate", C.c_int), ("max_rounds", C.c_int), ("analytic_jac", C.c_int),
                 ("solver", C.c_int)]
+
+
+class BranchOptions(C.Structure):
+    """socp_branch_options (include/socp_hip.h)."""
+    _fields_ = [("epsfcn", C.c_double), ("jac", C.c_int), ("wtheta", C.c_double), ("dir", C.c_int), ("h0", C.c_double),
+                ("hmin", C.c_double), ("hmax", C.c_double), ("grow", C.c_double), ("kfast", C.c_int), ("max_corr", C.c_int),
+                ("ftol", C.c_double), ("have_goal", C.c_int), ("goal", C.c_double), ("cap", C.c_int), ("rounds", C.c_int)]
+
+
+def branch_options(epsfcn=1e-15, jac=0, wtheta=1.0, dir=1, h0=0.1, hmin=1e-8, hmax=1.0, grow=2.0, kfast=2, max_corr=6, ftol=1e-10,
+                   goal=None, cap=64, rounds=200):
+    """A BranchOptions with the defaults of branch_batch; goal=None: no goal."""
+    return BranchOptions(float(epsfcn), int(jac), float(wtheta), int(dir), float(h0), float(hmin), float(hmax), float(grow), int(kfast),
+                         int(max_corr), float(ftol), 0 if goal is None else 1, 0.0 if goal is None else float(goal), int(cap), int(rounds))
 
 
 class ChainStats(C.Structure):
@@ -161,6 +176,13 @@ def lib():
                                                 _dp]
         L.socp_linsolve_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
         L.socp_svd_batch_dev.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]
+        L.socp_branch_work_bytes.argtypes = [_vp, C.c_int]
+        L.socp_branch_work_bytes.restype = C.c_size_t
+        _bo = C.POINTER(BranchOptions)
+        L.socp_branch_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _bo, _vp, C.c_size_t] + [_vp] * 10
+        L.socp_branch_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _bo, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _dp, _dp]
+        L.socp_branch_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _bo, _dp, _dp, _dp, _ip, _ip,
+                                               _ip, _ip, _ip, _dp, _dp]
         L.socp_singular_work_bytes.argtypes = [_vp, C.c_int]
         L.socp_singular_work_bytes.restype = C.c_size_t
         L.socp_singular_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_double, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]
@@ -831,6 +853,41 @@ class Context:
         self._chk(self.L.socp_singular_batch_blocks(self.h, B, _d(Z), *blocks, float(epsfcn), int(jac), int(scale), int(max_sweeps), _d(sigma),
                                                     _d(vmin), _d(colnorm), sweeps.ctypes.data_as(_ip), info.ctypes.data_as(_ip)))
         return dict(sigma=sigma, vmin=vmin, colnorm=colnorm, sweeps=sweeps, info=info)
+
+    # -- batched branch following
+    def branch_work_bytes(self, B):
+        """Bytes of the workspace branch_batch_dev needs for B rows (socp_branch_work_bytes)."""
+        return int(self.L.socp_branch_work_bytes(self.h, int(B)))
+
+    def branch_batch_dev(self, B, d_Z, direction, opts, d_work, work_bytes, d_Y, d_ttheta, d_rnorm, d_count, d_nfold, d_ifold, d_status,
+                         d_nreject, d_hlast, d_zgoal=None):
+        """Device pointers (ints; d_zgoal may be None), direction = (kind, index), opts a BranchOptions; enqueues exactly opts.rounds
+        rounds, no allocation, no copy, no synchronise (socp_branch_batch_dev)."""
+        self._chk(self.L.socp_branch_batch_dev(self.h, int(B), _vp(d_Z), int(direction[0]), int(direction[1]), C.byref(opts), _vp(d_work),
+                                               int(work_bytes), _vp(d_Y), _vp(d_ttheta), _vp(d_rnorm), _vp(d_count), _vp(d_nfold), _vp(d_ifold),
+                                               _vp(d_status), _vp(d_nreject), _vp(d_hlast), _vp(d_zgoal)))
+
+    def branch_batch(self, Z, direction, opts=None, params=None, time=None, xnode=None, **kw):
+        """Pseudo-arclength continuation of every row of Z along direction = (kind, index) (DIR_PARAM / DIR_TIME / DIR_XNODE as
+        tangent_batch): theta is that entry of the row's blocks, followed past folds (include/socp_hip.h has the definition).  opts: a
+        BranchOptions, or keyword arguments of branch_options().  Returns dict(y[B][cap][n+1] (z then theta of every accepted point,
+        unused slots NaN), ttheta[B][cap], rnorm[B][cap], count[B], nfold[B], ifold[B], status[B] (BRANCH_*), nreject[B], hlast[B],
+        zgoal[B][n] (NaN unless BRANCH_REACHED)).  params / time / xnode: per-row blocks as in residual_batch_blocks."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        if opts is not None and kw:
+            raise TypeError("branch_batch: give a BranchOptions or keyword options, not both (%s)" % ", ".join(sorted(kw)))
+        opts = branch_options(**kw) if opts is None else opts
+        blocks = _block_args(B, params, time, xnode)
+        cap = max(int(opts.cap), 0)
+        Y = np.full((B, cap, self.n + 1), np.nan)
+        tth, rn = np.full((B, cap), np.nan), np.full((B, cap), np.nan)
+        hlast, zgoal = np.full(B, np.nan), np.full((B, self.n), np.nan)
+        count, nfold, ifold, status, nreject = (np.zeros(B, dtype=np.int32) for _ in range(5))
+        self._chk(self.L.socp_branch_batch_blocks(self.h, B, _d(Z), *blocks, int(direction[0]), int(direction[1]), C.byref(opts), _d(Y), _d(tth),
+                                                  _d(rn), *(a.ctypes.data_as(_ip) for a in (count, nfold, ifold, status, nreject)), _d(hlast),
+                                                  _d(zgoal)))
+        return dict(y=Y, ttheta=tth, rnorm=rn, count=count, nfold=nfold, ifold=ifold, status=status, nreject=nreject, hlast=hlast, zgoal=zgoal)
 
     # -- row grouping
     def group_batch_dev(self, B, n, ld, d_V, d_mask, atol, rtol, max_groups, d_label, d_leader, d_count, d_radius, d_summary):

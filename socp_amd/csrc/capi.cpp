@@ -1444,14 +1444,9 @@ TangentWork tangent_layout(const socp_ctx *c, int B, int K)
     return w;
 }
 
-// *dirs: the directions as they travel to the kernel (the host arrays are read here)
-int tangent_args(socp_ctx *c, const char *who, int B, int K, const int *dir_kind, const int *dir_index, int jac, TangentDirs *dirs)
+// the K directions checked against the problem's ranges and copied as they travel to the kernel (the host arrays are read here)
+int direction_args(socp_ctx *c, const std::string &w, int K, const int *dir_kind, const int *dir_index, TangentDirs *dirs)
 {
-    const std::string w(who);
-    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
-    if (K < 1 || K > kMaxTangentDirs) return fail(c, SOCP_ERR_ARG, w + ": 1 <= K <= 16 directions are required");
-    if (!dir_kind || !dir_index) return fail(c, SOCP_ERR_ARG, w + ": null direction table");
-    if (jac != 0 && jac != 1) return fail(c, SOCP_ERR_ARG, w + ": jac must be 0 (forward differences) or 1 (variational)");
     for (int k = 0; k < K; k++) {
         const int kind = dir_kind[k], index = dir_index[k];
         int range = -1;
@@ -1465,6 +1460,17 @@ int tangent_args(socp_ctx *c, const char *who, int B, int K, const int *dir_kind
         dirs->kind[k] = kind; dirs->index[k] = index;
     }
     for (int k = K; k < kMaxTangentDirs; k++) dirs->kind[k] = dirs->index[k] = -1;
+    return SOCP_OK;
+}
+
+int tangent_args(socp_ctx *c, const char *who, int B, int K, const int *dir_kind, const int *dir_index, int jac, TangentDirs *dirs)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (K < 1 || K > kMaxTangentDirs) return fail(c, SOCP_ERR_ARG, w + ": 1 <= K <= 16 directions are required");
+    if (!dir_kind || !dir_index) return fail(c, SOCP_ERR_ARG, w + ": null direction table");
+    if (jac != 0 && jac != 1) return fail(c, SOCP_ERR_ARG, w + ": jac must be 0 (forward differences) or 1 (variational)");
+    if (const int rc = direction_args(c, w, K, dir_kind, dir_index, dirs)) return rc;
     if (jac == 1 && !has_var(c))
         return fail(c, SOCP_ERR_UNSUPPORTED, w + ": this model has no variational equations (modelOrder 0): jac = 1 needs them");
     return SOCP_OK;
@@ -1708,6 +1714,202 @@ int socp_singular_batch_blocks(socp_ctx *c, int B, const double *Z, const double
     if (B == 0) return SOCP_OK;
     return with_blocks(c, B, params, pstride, time, xnode,
                        [&] { return socp_singular_batch(c, B, Z, epsfcn, jac, scale, max_sweeps, sigma, vmin, colnorm, sweeps, info); });
+}
+
+/* ---- batched branch following ---------------------------------------------------------------- */
+
+namespace {
+constexpr int kBranchChunk = 8;       // rounds the host forms enqueue between two read-backs of the "unfinished rows" word
+
+// the workspace of socp_branch_batch_dev, in doubles from its start: block rows, unknowns and residual rows of the 2B launched rows,
+// the Jacobians, the bordered matrices, the right-hand sides, the row state (BranchState; the int pieces take whole doubles), then
+// what the variational Jacobian integrates in (models that have one)
+struct BranchWork {
+    size_t params, time, xnode, Z, F, J, Mx, rhs, v, y, t, h, hth, rn, k, kase, info, live, var, total;
+};
+
+BranchWork branch_layout(const socp_ctx *c, int B)
+{
+    const size_t R = 2 * (size_t)B, nodes = (size_t)c->M + 1, n = c->n, n1 = n + 1, ints = ((size_t)B + 1) / 2;
+    BranchWork w{};
+    size_t at = 0;
+    auto take = [&](size_t count) { const size_t here = at; at += (count + 1) & ~(size_t)1; return here; };      // 16-byte aligned pieces
+    w.params = take(R * (c->nparams + 2));
+    w.time = take(R * nodes);
+    w.xnode = take(R * nodes * c->S);
+    w.Z = take(R * n);
+    w.F = take(R * n);
+    w.J = take((size_t)B * n * n);
+    w.Mx = take((size_t)B * n1 * n1);
+    w.rhs = take((size_t)B * n1);
+    w.v = take((size_t)B * n1);
+    w.y = take((size_t)B * n1);
+    w.t = take((size_t)B * n1);
+    w.h = take(B);
+    w.hth = take(B);
+    w.rn = take(B);
+    w.k = take(ints);
+    w.kase = take(ints);
+    w.info = take(ints);
+    w.live = take(2);
+    w.var = take(has_var(c) ? var_work_doubles(c, B) : 0);
+    w.total = at;
+    return w;
+}
+
+// the refusals all three forms share; *A: the direction and the options as they travel to the kernels
+int branch_args(socp_ctx *c, const char *who, int B, int kind, int index, const socp_branch_options *o, BranchArgs *A)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (!o) return fail(c, SOCP_ERR_ARG, w + ": null options");
+    TangentDirs dirs;
+    if (const int rc = direction_args(c, w, 1, &kind, &index, &dirs)) return rc;
+    if (o->jac != 0 && o->jac != 1) return fail(c, SOCP_ERR_ARG, w + ": jac must be 0 (forward differences) or 1 (variational)");
+    if (!(o->wtheta > 0.0) || !std::isfinite(o->wtheta)) return fail(c, SOCP_ERR_ARG, w + ": wtheta must be positive and finite");
+    if (o->dir != 1 && o->dir != -1) return fail(c, SOCP_ERR_ARG, w + ": dir must be +1 or -1");
+    if (!(0.0 < o->hmin && o->hmin <= o->h0 && o->h0 <= o->hmax) || !std::isfinite(o->hmax))
+        return fail(c, SOCP_ERR_ARG, w + ": 0 < hmin <= h0 <= hmax (finite) is required");
+    if (!(o->grow >= 1.0) || !std::isfinite(o->grow)) return fail(c, SOCP_ERR_ARG, w + ": grow >= 1 (finite) is required");
+    if (o->max_corr < 1 || o->kfast < 0) return fail(c, SOCP_ERR_ARG, w + ": max_corr >= 1 and kfast >= 0 are required");
+    if (!(o->ftol > 0.0)) return fail(c, SOCP_ERR_ARG, w + ": ftol > 0 is required");
+    if (o->cap < 2 || o->rounds < 1) return fail(c, SOCP_ERR_ARG, w + ": cap >= 2 and rounds >= 1 are required");
+    if (o->jac == 1 && !has_var(c))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": this model has no variational equations (modelOrder 0): jac = 1 needs them");
+    if (!linsolve_fits(c->n + 1, 1))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": too many unknowns for the batched linear solve (2 (n + 1) + 1 doubles must fit 64 KiB of LDS)");
+    A->kind = kind; A->index = index; A->dir = o->dir; A->kfast = o->kfast; A->max_corr = o->max_corr; A->have_goal = o->have_goal ? 1 : 0;
+    A->cap = o->cap; A->e = fd_eps(o->epsfcn); A->wtheta = o->wtheta; A->h0 = o->h0; A->hmin = o->hmin; A->hmax = o->hmax; A->grow = o->grow;
+    A->ftol = o->ftol; A->goal = o->goal;
+    return SOCP_OK;
+}
+
+// rounds [from, to) of a checked call, enqueued on the context's stream; d_live: where the update leaves the number of unfinished rows
+int branch_rounds(socp_ctx *c, int B, const double *d_Z, const BranchArgs &A, double epsfcn, int jac, void *d_work, const BranchOut &O,
+                  int from, int to, const int **d_live)
+{
+    const BranchWork w = branch_layout(c, B);
+    double *wk = static_cast<double *>(d_work);
+    double *wP = wk + w.params, *wT = wk + w.time, *wX = wk + w.xnode, *wZ = wk + w.Z, *wF = wk + w.F, *wJ = wk + w.J, *wM = wk + w.Mx, *wR = wk + w.rhs;
+    BranchState S;
+    S.v = wk + w.v; S.y = wk + w.y; S.t = wk + w.t; S.h = wk + w.h; S.hth = wk + w.hth; S.rn = wk + w.rn;
+    S.k = reinterpret_cast<int *>(wk + w.k); S.kase = reinterpret_cast<int *>(wk + w.kase); S.info = reinterpret_cast<int *>(wk + w.info);
+    S.live = reinterpret_cast<int *>(wk + w.live);
+    if (d_live) *d_live = S.live;
+    const int n = c->n;
+    for (int round = from; round < to; round++) {
+        const int first = round == 0;
+        // launch 1: the block rows of the evaluation points (theta, theta + h_theta) and their unknowns; the first round sets the state
+        c->n_launch += 1;
+        HIP_TRY(c, branch_expand(c->stream, c->P, c->pb, c->nparams, B, A, first, d_Z, S, O, wP, wT, wX, wZ));
+        {
+            // F0, F1 and the Jacobian at (v_z, F0) under the SAME expanded blocks.  A smooth-law promise covers them unless mu2 itself moves
+            BlocksGuard guard(c);
+            int smooth = c->pb.pp_params ? c->pb.pp_smooth : (c->model_id == SOCP_MODEL_GODDARD && c->P.p[6] > 0 ? 1 : 0);
+            if (c->model_id == SOCP_MODEL_GODDARD && A.kind == SOCP_DIR_PARAM && A.index == 6) smooth = 0;
+            c->pb.pp_params = wP; c->pb.pp_stride = c->nparams + 2; c->pb.pp_time = wT; c->pb.pp_xnode = wX; c->pb.pp_smooth = smooth;
+            HIP_TRY(c, run_residual(c, 2 * B, wZ, wF));
+            if (jac == 0) {
+                const int r = socp_fd_jacobian_multi_dev(c, B, wZ, wF, epsfcn, wJ, 1);
+                if (r != SOCP_OK) return r;
+            } else {
+                HIP_TRY(c, run_var_jacobian(c, B, wZ, wk + w.var, wJ));
+            }
+        }
+        // the row's case, the bordered matrix and its right-hand side; the elimination; the transitions
+        c->n_launch += 3;
+        HIP_TRY(c, branch_assemble(c->stream, B, n, A, first, wF, wJ, S, O.status, wM, wR));
+        HIP_TRY(c, linsolve(c->stream, B, n + 1, 1, wM, wR, S.info));      // reference order in both flavours
+        HIP_TRY(c, branch_update(c->stream, B, n, A, S, O, wR));
+    }
+    return SOCP_OK;
+}
+}  // namespace
+
+size_t socp_branch_work_bytes(const socp_ctx *c, int B)
+{
+    if (!c || !c->has_problem || B < 0) return 0;
+    return sizeof(double) * branch_layout(c, B).total;
+}
+
+int socp_branch_batch_dev(socp_ctx *c, int B, const double *d_Z, int dir_kind, int dir_index, const socp_branch_options *opt, void *d_work,
+                          size_t work_bytes, double *d_Y, double *d_ttheta, double *d_rnorm, int *d_count, int *d_nfold, int *d_ifold,
+                          int *d_status, int *d_nreject, double *d_hlast, double *d_zgoal)
+{
+    if (!c) return SOCP_ERR_ARG;
+    BranchArgs A;
+    const int rc = branch_args(c, "branch_batch", B, dir_kind, dir_index, opt, &A);
+    if (rc != SOCP_OK) return rc;
+    if (B > 0 && (!d_Z || !d_work || !d_Y || !d_ttheta || !d_rnorm || !d_count || !d_nfold || !d_ifold || !d_status || !d_nreject || !d_hlast))
+        return fail(c, SOCP_ERR_ARG, "branch_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    if (work_bytes < socp_branch_work_bytes(c, B)) return fail(c, SOCP_ERR_ARG, "branch_batch: the workspace is smaller than socp_branch_work_bytes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const BranchOut O{d_Y, d_ttheta, d_rnorm, d_count, d_nfold, d_ifold, d_status, d_nreject, d_hlast, d_zgoal};
+    return branch_rounds(c, B, d_Z, A, opt->epsfcn, opt->jac, d_work, O, 0, opt->rounds, nullptr);
+}
+
+int socp_branch_batch(socp_ctx *c, int B, const double *Z, int dir_kind, int dir_index, const socp_branch_options *opt, double *Y,
+                      double *ttheta, double *rnorm, int *count, int *nfold, int *ifold, int *status, int *nreject, double *hlast, double *zgoal)
+{
+    if (!c) return SOCP_ERR_ARG;
+    BranchArgs A;
+    const int rc0 = branch_args(c, "branch_batch", B, dir_kind, dir_index, opt, &A);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B > 0 && (!Z || !Y || !ttheta || !rnorm || !count || !nfold || !ifold || !status || !nreject || !hlast))
+        return fail(c, SOCP_ERR_ARG, "branch_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = c->n, nZ = (size_t)B * n, nC = (size_t)B * opt->cap, nY = nC * (n + 1), nG = zgoal ? nZ : 0;
+    const size_t bytes = socp_branch_work_bytes(c, B);
+    double *d_Z;
+    HIP_TRY(c, c->s_var.reserve(bytes));
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (nY + 2 * nC + (size_t)B + nG) + sizeof(int) * 5 * (size_t)B));
+    double *dY = c->s_out.as<double>(), *dT = dY + nY, *dR = dT + nC, *dH = dR + nC, *dG = dH + B;
+    int *dI = reinterpret_cast<int *>(dG + nG);                   // count, nfold, ifold, status, nreject: B each
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, d_Z));
+    const BranchOut O{dY, dT, dR, dI, dI + B, dI + 2 * (size_t)B, dI + 3 * (size_t)B, dI + 4 * (size_t)B, dH, zgoal ? dG : nullptr};
+    // chunks of rounds; between two chunks the number of unfinished rows comes back: 0 ends the call (a finished row changes nothing)
+    for (int from = 0; from < opt->rounds; from += kBranchChunk) {
+        const int to = from + kBranchChunk < opt->rounds ? from + kBranchChunk : opt->rounds;
+        const int *d_live = nullptr;
+        const int rc = branch_rounds(c, B, d_Z, A, opt->epsfcn, opt->jac, c->s_var.p, O, from, to, &d_live);
+        if (rc != SOCP_OK) return rc;
+        if (to == opt->rounds) break;
+        int live = 0;
+        HIP_TRY(c, copy_down(c, &live, d_live, 1));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (live == 0) break;
+    }
+    HIP_TRY(c, copy_down(c, Y, dY, nY));
+    HIP_TRY(c, copy_down(c, ttheta, dT, nC));
+    HIP_TRY(c, copy_down(c, rnorm, dR, nC));
+    HIP_TRY(c, copy_down(c, hlast, dH, (size_t)B));
+    if (zgoal) HIP_TRY(c, copy_down(c, zgoal, dG, nG));
+    HIP_TRY(c, copy_down(c, count, O.count, (size_t)B));
+    HIP_TRY(c, copy_down(c, nfold, O.nfold, (size_t)B));
+    HIP_TRY(c, copy_down(c, ifold, O.ifold, (size_t)B));
+    HIP_TRY(c, copy_down(c, status, O.status, (size_t)B));
+    HIP_TRY(c, copy_down(c, nreject, O.nreject, (size_t)B));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_branch_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time, const double *xnode,
+                             int dir_kind, int dir_index, const socp_branch_options *opt, double *Y, double *ttheta, double *rnorm,
+                             int *count, int *nfold, int *ifold, int *status, int *nreject, double *hlast, double *zgoal)
+{
+    if (!c) return SOCP_ERR_ARG;
+    BranchArgs A;
+    const int rc0 = branch_args(c, "branch_batch_blocks", B, dir_kind, dir_index, opt, &A);
+    if (rc0 != SOCP_OK) return rc0;
+    if (const int rc = blocks_stride(c, "branch_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !Y || !ttheta || !rnorm || !count || !nfold || !ifold || !status || !nreject || !hlast))
+        return fail(c, SOCP_ERR_ARG, "branch_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode, [&] {
+        return socp_branch_batch(c, B, Z, dir_kind, dir_index, opt, Y, ttheta, rnorm, count, nfold, ifold, status, nreject, hlast, zgoal);
+    });
 }
 
 /* ---- row grouping --------------------------------------------------------------------------- */

@@ -104,6 +104,35 @@ hipError_t tangent_diff_fast(hipStream_t st, int B, int K, int n, const double *
 // A[B][n*n] column-major, Y[B][K][n] -> the solutions in Y, info[B]; hipErrorInvalidValue unless linsolve_fits(n, K)
 hipError_t linsolve(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
 hipError_t linsolve_fast(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
+// socp_branch_batch (kernels_branch.hip: one object without contraction, for both flavours).  The direction and the options travel as
+// a kernel argument; the row state lives in the caller's workspace.
+struct BranchArgs {
+    int kind, index, dir, kfast, max_corr, have_goal, cap;
+    double e, wtheta, h0, hmin, hmax, grow, ftol, goal;          // e = sqrt(max(epsfcn, DBL_EPSILON))
+};
+// per row: the evaluation point v, the last accepted point y and the unit tangent t there ([B][n+1]: z then lambda), the step
+// length h, the parameter step h_theta and ||F0||inf of this round, the corrector count k, this round's case and the elimination's
+// info; live: the number of unfinished rows after the last update
+struct BranchState {
+    double *v, *y, *t, *h, *hth, *rn;
+    int *k, *kase, *info, *live;
+};
+struct BranchOut {
+    double *Y, *ttheta, *rnorm;
+    int *count, *nfold, *ifold, *status, *nreject;
+    double *hlast, *zgoal;                                       // zgoal may be null
+};
+// block rows r = kk B + b (kk = 0: theta = fl(lambda wtheta) of row b's evaluation point, kk = 1: theta + h_theta) into wP / wT / wX
+// [2B][..], the evaluation point's z into wZ[2B][n], h_theta into the state, live = 0; first: the state and the outputs are set
+// from Z and the row's blocks first
+hipError_t branch_expand(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int nparams, int B, const BranchArgs &A, int first,
+                         const double *Z, const BranchState &S, const BranchOut &O, double *wP, double *wT, double *wX, double *wZ);
+// from the residual rows F[2B][n] and J[B][n*n]: ||F0||inf and the row's case into the state, the bordered matrix Mx[B][(n+1)^2]
+// column-major, the right-hand side rhs[B][n+1]
+hipError_t branch_assemble(hipStream_t st, int B, int n, const BranchArgs &A, int first, const double *F, const double *J,
+                           const BranchState &S, const int *status, double *Mx, double *rhs);
+// the transitions of every unfinished row from the solutions X[B][n+1]
+hipError_t branch_update(hipStream_t st, int B, int n, const BranchArgs &A, const BranchState &S, const BranchOut &O, const double *X);
 // socp_svd_batch_dev / socp_singular_batch (kernels_svd.hip, built once per flavour like kernels_tangent.hip).  One matrix per team
 // of L lanes, a lane per pair of rows; T teams per workgroup; the matrix, its n row norms and kSvdFlags doubles of flags in LDS
 constexpr int kSvdLdsBytes = 160 * 1024;             // the LDS of a CU: the most one workgroup can take

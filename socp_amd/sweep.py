@@ -401,6 +401,29 @@ def singular_local(ctx, args, local, lo, rank, params=None):
             "file": path}
 
 
+def branch_local(ctx, args, local, lo, rank, params=None):
+    """--branch-out: pseudo-arclength continuation (socp_branch_batch) of this rank's CONVERGED chains along the packed parameter
+    --branch-param towards --branch-goal, each chain from its own parameter block when the chains have one: the branch is followed by
+    its arclength, past folds, until the parameter crosses the goal.  Written to PATH.rank<r>.npz: index [k] = position of the chain
+    in the sweep's start table, y [k][cap][n+1] (z then the parameter of every accepted point, unused slots NaN), ttheta, rnorm
+    [k][cap], count, nfold, ifold, status [k], zgoal [k][n] (the root at the goal; NaN unless the goal was reached).  Runs after the
+    timed solve.  Returns the record entry of this rank: how many branches reach the goal, and how many turn back on the way."""
+    from . import capi
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.branch_out)
+    slot = capi.GODDARD_PARAM_NAMES.index(args.branch_param)
+    theta = np.full(len(conv), ctx.get_params()[slot]) if own is None else own[:, slot].copy()
+    # one orientation per call: towards the goal from where most chains stand
+    direction = 1 if len(conv) == 0 or args.branch_goal >= float(np.median(theta)) else -1
+    r = ctx.branch_batch(z, (capi.DIR_PARAM, slot), params=own, wtheta=args.branch_wtheta, dir=direction, h0=args.branch_h, hmin=1e-6 * args.branch_h,
+                         hmax=8.0 * args.branch_h, goal=args.branch_goal, cap=args.branch_points, rounds=args.branch_rounds)
+    np.savez(path, index=index, y=r["y"], ttheta=r["ttheta"], rnorm=r["rnorm"], count=r["count"], nfold=r["nfold"], ifold=r["ifold"],
+             status=r["status"], zgoal=r["zgoal"])
+    status = r["status"]
+    return {"rows": int(len(conv)), "reached": int(np.sum(status == capi.BRANCH_REACHED)), "with_fold": int(np.sum(r["nfold"] > 0)),
+            "step_too_small": int(np.sum(status == capi.BRANCH_STEP_TOO_SMALL)), "singular": int(np.sum(status == capi.BRANCH_SINGULAR)),
+            "points_median": float(np.median(r["count"])) if len(conv) else None}
+
+
 def roots_global(ctx, args, table, n, with_cost=False, leader_blocks=None):
     """--roots-out: the distinct roots of the WHOLE sweep (socp_group_batch), on rank 0 from the gathered table [P][n+3] as it is:
     ld = n + 3, mask = (info == 1), grouping on the unknown vectors z only, greedy in start order.  Written to PATH.npz: label [P]
@@ -601,6 +624,20 @@ def main():
     ap.add_argument("--sing-scale", type=int, default=1, metavar="0|1",
                     help="with --sing-out: 1 brings the Jacobian's columns to unit norm first (MINPACK's mode 1 scaling), 0 takes it as it is")
     ap.add_argument("--sing-sweeps", type=int, default=60, metavar="N", help="with --sing-out: at most N Jacobi sweeps, 1 .. 1000")
+    ap.add_argument("--branch-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank follows the solution branch of the converged chains of its own block along one "
+                         "packed parameter by pseudo-arclength continuation in one batch (socp_branch_batch: past folds, where restarting "
+                         "the solver at the next parameter value stalls), with the chains' own parameter blocks, until --branch-goal is "
+                         "crossed; writes PATH.rank<r>.npz (index, y, ttheta, rnorm, count, nfold, ifold, status, zgoal) and adds branch "
+                         "{rows, reached, with_fold, step_too_small, singular, points_median} to the record.  Needs --branch-goal.  Not "
+                         "with --model interceptor.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--branch-param", default="KD", metavar="NAME", help="with --branch-out: the parameter, by its name in the packed block")
+    ap.add_argument("--branch-goal", type=float, default=None, metavar="V", help="with --branch-out: follow until the parameter crosses V")
+    ap.add_argument("--branch-wtheta", type=float, default=1.0, metavar="W",
+                    help="with --branch-out: the scale of the parameter in the arclength (lambda = theta / W; for KD ~ 310 take 310)")
+    ap.add_argument("--branch-h", type=float, default=0.1, metavar="H", help="with --branch-out: the first arclength step (the largest is 8 H)")
+    ap.add_argument("--branch-points", type=int, default=64, metavar="C", help="with --branch-out: points kept per row, >= 2")
+    ap.add_argument("--branch-rounds", type=int, default=400, metavar="R", help="with --branch-out: rounds, >= 1")
     ap.add_argument("--events-refine", type=int, default=2, metavar="R",
                     help="with --events-out: false-position steps per event, 0 .. 8 (0: linear interpolation over the step)")
     args = ap.parse_args()
@@ -624,6 +661,18 @@ def main():
         from .capi import GODDARD_PARAM_NAMES            # (the module only: the library is loaded by the first context)
         if args.tangent_param not in GODDARD_PARAM_NAMES:
             ap.error("--tangent-param: not a name of the packed parameter block (%s)" % ", ".join(GODDARD_PARAM_NAMES))
+    if args.branch_out and args.model == "interceptor":
+        ap.error("--branch-out is implemented for the Goddard sweeps")
+    if args.branch_out:
+        from .capi import GODDARD_PARAM_NAMES
+        if args.branch_param not in GODDARD_PARAM_NAMES:
+            ap.error("--branch-param: not a name of the packed parameter block (%s)" % ", ".join(GODDARD_PARAM_NAMES))
+        if args.branch_goal is None or not np.isfinite(args.branch_goal):
+            ap.error("--branch-out needs a finite --branch-goal")
+        if not (args.branch_wtheta > 0 and np.isfinite(args.branch_wtheta) and args.branch_h > 0 and np.isfinite(args.branch_h)):
+            ap.error("--branch-wtheta and --branch-h must be positive and finite")
+        if args.branch_points < 2 or args.branch_rounds < 1:
+            ap.error("--branch-points must be >= 2 and --branch-rounds >= 1")
     if args.sing_out and args.model == "interceptor":
         ap.error("--sing-out is implemented for the Goddard sweeps")
     if args.sing_scale not in (0, 1):
@@ -736,6 +785,8 @@ def main():
         extra["jacobi" if rank == 0 else "jacobi_rank%d" % rank] = jacobi_local(ctx, args, local, lo_w, rank, blocks)
     if args.sing_out:
         extra["singular" if rank == 0 else "singular_rank%d" % rank] = singular_local(ctx, args, local, lo_w, rank, blocks)
+    if args.branch_out:
+        extra["branch" if rank == 0 else "branch_rank%d" % rank] = branch_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
