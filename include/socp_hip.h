@@ -396,6 +396,63 @@ int socp_jacobi_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
                              const double *xnode, double epsfcn, int stride, int skip, int cap, double *tq, double *det, int *count,
                              int *nchange, double *tconj, double *Jend);
 
+/* The same test with EXACT Jacobi fields: J(t) = dx(t)/dp(t0) by forward-mode differentiation of the residual's own RK4 steps, and
+ * the transition matrix Phi = dX(t_{i+1})/dX(t_i) of every segment as a by-product.  [ext] HamPath's expdhvfun provides this; the
+ * reference does not.  For an explicit Runge-Kutta method, carrying the derivative through the steps is precisely the derivative
+ * of the DISCRETE flow the residual integrates; there is no epsfcn and no step rule.  socp_jacobi_batch's forward difference is
+ * wrong in the fourth digit on the nominal Goddard extremal (it starts at |v| = 1.7e-10, where vx / v is violently nonlinear).
+ * Measured on the CPU restatement against the same recurrence in 240 bits, nominal Goddard start, one segment [0, 0.2640825],
+ * N = 50 (error of Jend / max |J|;  det truth;  det forward difference with epsfcn 0 / 4 DBL_EPSILON;  det by this call):
+ *   mu2 = 1                      1.5e-4 -> 3.5e-13    -1.26348e-8    -1.199e-8 / -1.135e-8     -1.26348027522e-8
+ *   mu2 = 0.2                    7.7e-5 -> 3.7e-14    0 (singular)   -5.0e-24 / -6.7e-25       -2.4e-43
+ *   mu2 = 0, sw = (0.05, 0.15)   3.7e-4 -> 2.5e-13    0              0.0 / 0.0                 0.0
+ * Z[B][n] -> tq[B][M][cap], det[B][M][cap], count[B][M], nchange[B][M], tconj[B][M], Phi[B][M][s][C] (may be NULL; row-major: row r of
+ * X, column c).  cols = SOCP_FIELDS_COSTATE: C = d columns, the unit vectors of p(t_i);  SOCP_FIELDS_ALL: C = s = 2d columns, the
+ * unit vectors of X(t_i), x first.
+ * SETUP, timeline, switching times, per-row blocks, STEPS, SAMPLES, the slab / cap rule and DETECTION (with skip) are word for word
+ * those of socp_jacobi_batch.  There is no epsfcn.
+ * DUAL NUMBERS.  A dual number is (v, d).  Every operation is one IEEE rounding per listed step, never contracted:
+ *   a +- b = (a.v +- b.v, a.d +- b.d);   a b = (a.v b.v, (a.d b.v) + (a.v b.d));   a / b: q = a.v / b.v, (q, (a.d - q b.d) / b.v);
+ *   -a and |a| act on both parts, |a| flips d when v < 0;
+ *   sqrt a: s = sqrt(a.v), (s, a.d / (s + s)), the derivative +0.0 when s == 0 (Goddard's norm_u with the thrust off);
+ *   exp a: e = the model's exp (exp_glibc for Goddard), (e, e a.d);
+ *   comparisons read v; a branch's derivative is that of the branch taken;
+ *   a plain double c (a parameter, a literal, t, h, and a control or penalty that the law makes a constant: thrust off or full, a
+ *   clamped control, an inactive penalty) takes part with its zero derivative terms DROPPED, not computed:
+ *   c a = (c v, c d);  a / c = (v / c, d / c);  c / a: q = c / v, (q, (-(q d)) / v);  c +- a = (c +- v, +-d);  a - c = (v - c, d).
+ *   A component of the right-hand side that is a constant has the derivative +0.0.
+ * The model's right-hand side is its rhs_t trait (plugin_impl.hpp): the reference-order text on plain IEEE operations.
+ * COLUMNS.  Column c starts from (X0, e_k): k = d + c (COSTATE), k = c (ALL).  All columns take the residual's RK4 steps in the
+ * association order of odeTools.cpp:89-98 on dual numbers, t and the step plain doubles; the value part of every column is the
+ * reference-order residual's trajectory, bit for bit.
+ * DETERMINANT.  J[r][c'] = the derivative part of component r < d in the column of p_c'(t_i); det by the elimination of
+ * socp_jacobi_batch, unchanged.
+ * Phi holds the derivative parts of all s components after the last step.  A zero-length or backward segment takes no step:
+ * count = 0, nchange = 0, tconj = NaN, Phi = the unit columns it started from.
+ * ONE OBJECT, NO CONTRACTION: the kernels are built once, without contraction, and serve both variants -- a throughput-flavour
+ * context returns the same bits, and the value trajectories are the reference-order ones, not the fast residual's.
+ * WHAT IT IS AND IS NOT.  The caveats of the Jacobi test stand: the classical statement is for M = 1 with a fixed initial state, and
+ * with a free final time the plain determinant is not the right test (use Phi).  The result is exact for the DISCRETE flow, to
+ * rounding -- not for the differential equation.  A determinant that is zero to rounding (table above) has no sign to read.  A
+ * state-dependent kink (Switch < 0, a saturation) differentiates the branch taken.  Out of scope: the adaptive integrator, the
+ * interceptor, vtolUAV, a jac = 2 for socp_tangent_batch / socp_singular_batch / socp_branch_batch, hybrj for Goddard
+ * (socp_ctx_has_variational stays 0 for it), more than one GPU.
+ * socp_ctx_has_fields: 1 when the context's model has the entry, else 0.
+ * SOCP_ERR_ARG: as socp_jacobi_batch, and cols outside 0 .. 1; B == 0: SOCP_OK without a launch; SOCP_ERR_UNSUPPORTED (the message
+ * says which): the context's integrator is SOCP_INT_DOPRI5, or the model's launch table has no fields entry (the interceptor,
+ * vtolUAV, a plugin without the rhs_t trait).  An error writes nothing and leaves the context unchanged.
+ * One launch; socp_ctx_counters advances by B M C trajectories.  The _dev, host and _blocks forms as for socp_jacobi_batch. */
+#define SOCP_FIELDS_COSTATE 0   /* C = d columns: the unit vectors of p(t_i)                 */
+#define SOCP_FIELDS_ALL     1   /* C = s = 2d columns: the unit vectors of X(t_i), x first    */
+int socp_ctx_has_fields(const socp_ctx *ctx);          /* 1 / 0 */
+int socp_fields_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int cols, int stride, int skip, int cap, double *d_tq,
+                          double *d_det, int *d_count, int *d_nchange, double *d_tconj, double *d_Phi);
+int socp_fields_batch(socp_ctx *ctx, int B, const double *Z, int cols, int stride, int skip, int cap, double *tq, double *det,
+                      int *count, int *nchange, double *tconj, double *Phi);
+int socp_fields_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                             const double *xnode, int cols, int stride, int skip, int cap, double *tq, double *det, int *count,
+                             int *nchange, double *tconj, double *Phi);
+
 /* replaces: shooting::Move(tf) (shooting.cpp:383-437) for a whole batch: the state ON a stored solution at a query time, and the
  * re-grid the reference's multi-stage flows build from it (testGoddard.cpp:115-145: vX[i] = Move(vt[i]), then InitShooting(vt, vX)
  * on a new structure).  Z[B][n], tq[B][K] -> Xq[B][K][s]; tout[B][K] (may be NULL) = the time actually reached.

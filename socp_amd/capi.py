@@ -23,6 +23,7 @@ INTERCEPTOR_PARAM_NAMES = ["c0", "hr", "d0", "eta", "propellant_mass", "empty_ma
 FIXED, FREE, CONTINUOUS = 0, 1, 2
 VARIANT_AUTO, VARIANT_LANE_EXACT, VARIANT_LANE_FAST = 0, 1, 2
 EVAL_RHS, EVAL_CONTROL, EVAL_HAMILTONIAN = 0, 1, 2
+FIELDS_COSTATE, FIELDS_ALL = 0, 1          # socp_fields_batch: the d costate columns / all s columns
 REQ_DONE, REQ_FVEC, REQ_JAC = 0, 1, 2
 INT_RK4, INT_DOPRI5 = 0, 1
 GODDARD_PARAM_NAMES = ["C", "b", "KD", "kr", "u_max", "mu1", "mu2", "singularControl"]
@@ -160,6 +161,11 @@ def lib():
         L.socp_ctx_has_jacobi.argtypes = [_vp]
         L.socp_jacobi_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
         L.socp_jacobi_batch.argtypes = [_vp, C.c_int, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp]
+        L.socp_ctx_has_fields.argtypes = [_vp]
+        L.socp_fields_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.socp_fields_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp]
+        L.socp_fields_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip,
+                                               _ip, _dp, _dp]
         L.socp_jacobi_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip,
                                                _ip, _dp, _dp]
         L.socp_move_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
@@ -726,6 +732,58 @@ class Context:
                 self.jacobi_batch_dev(B, Zd.data_ptr(), epsfcn, stride, skip, c, out["tq"].data_ptr(), out["det"].data_ptr(), out["count"].data_ptr(),
                                       out["nchange"].data_ptr(), out["tconj"].data_ptr(), out["jend"].data_ptr() if jend else None)
             self.synchronize()
+            return out["count"].cpu().numpy(), out
+
+        if not held:
+            return _call_with_enough_cap(call, cap)
+        pp, tt, xx = held
+        self._chk(self.L.socp_problem_set_blocks_dev(self.h, ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx)))
+        try:
+            return _call_with_enough_cap(call, cap)
+        finally:
+            self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
+
+    # -- batched exact fields
+    def has_fields(self):
+        """Whether this model has an exact-fields kernel (socp_ctx_has_fields): the in-tree Goddard, double integrator and covid19,
+        and a plugin with the rhs_t trait; not the interceptor, not vtolUAV."""
+        return self.L.socp_ctx_has_fields(self.h) == 1
+
+    def fields_batch_dev(self, B, d_Z, cols, stride, skip, cap, d_tq, d_det, d_count, d_nchange, d_tconj, d_Phi=None):
+        """Device pointers (ints; d_Phi may be None); enqueue only, no copy, no synchronise (socp_fields_batch_dev)."""
+        self._chk(self.L.socp_fields_batch_dev(self.h, int(B), _vp(d_Z), int(cols), int(stride), int(skip), int(cap), _vp(d_tq), _vp(d_det),
+                                               _vp(d_count), _vp(d_nchange), _vp(d_tconj), _vp(d_Phi)))
+
+    def fields_batch(self, Z, cols=0, stride=1, skip=0, cap=64, phi=False, blocks=None):
+        """The conjugate-time test of jacobi_batch with EXACT Jacobi fields (include/socp_hip.h): J(t) = dx(t)/dp(t0) carried through the
+        residual's fixed RK4 steps on dual numbers -- the derivative of the discrete flow, no epsfcn.  cols = FIELDS_COSTATE (0): the
+        d costate columns; FIELDS_ALL (1): all s columns, the whole transition matrix.  Returns a dict of DEVICE tensors like
+        jacobi_batch: tq, det [B][M][cap], count, nchange, tconj [B][M] and, with phi=True, phi[B][M][s][C] and jend[B][M][d][d] = the
+        x-rows of the costate columns of phi (a view).  Repeated with the largest count when a segment has more than `cap` samples.
+        blocks = (params, time, xnode) as in jacobi_batch.  The same bits on a throughput-flavour context."""
+        import torch
+        dev = torch.device("cuda")
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        Zd = up(Z).reshape(-1, self.n)
+        B, M, d = Zd.shape[0], self.M, self.dim
+        ncol = 2 * d if int(cols) == FIELDS_ALL else d
+        held = [up(a).reshape(B, -1) if a is not None else None for a in (blocks if blocks is not None else ())]
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+
+        def call(c):
+            out = dict(tq=torch.full((B, M, c), float("nan"), dtype=torch.float64, device=dev),
+                       det=torch.full((B, M, c), float("nan"), dtype=torch.float64, device=dev),
+                       count=torch.zeros((B, M), dtype=torch.int32, device=dev), nchange=torch.zeros((B, M), dtype=torch.int32, device=dev),
+                       tconj=torch.full((B, M), float("nan"), dtype=torch.float64, device=dev))
+            if phi:
+                out["phi"] = torch.zeros((B, M, 2 * d, ncol), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()
+            if B:
+                self.fields_batch_dev(B, Zd.data_ptr(), cols, stride, skip, c, out["tq"].data_ptr(), out["det"].data_ptr(), out["count"].data_ptr(),
+                                      out["nchange"].data_ptr(), out["tconj"].data_ptr(), out["phi"].data_ptr() if phi else None)
+            self.synchronize()
+            if phi:
+                out["jend"] = out["phi"][:, :, :d, ncol - d:]
             return out["count"].cpu().numpy(), out
 
         if not held:

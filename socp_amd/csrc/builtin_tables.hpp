@@ -40,7 +40,8 @@ const ModelLaunchers *builtin_tables(int model_id)
 {
     // goddard.cpp:23-40 defaults.  Dense output always takes the general law.
     static const ModelLaunchers goddard = [] {
-        ModelLaunchers t = plugin::table<God>(SOCP_GODDARD_NPARAMS, 10, {3.5, 7.0, 310.0, 500.0, 1.0, 1.0, 0.0, -1.0});
+        ModelLaunchers t = plugin::table<God, false>(SOCP_GODDARD_NPARAMS, 10, {3.5, 7.0, 310.0, 500.0, 1.0, 1.0, 0.0, -1.0});
+        t.fields = &fields_goddard;                  // kernels_fields.hip: the same reference-order object in both flavours
         t.traj = &goddard_by_params<&plugin::traj<GodSmooth>, &plugin::traj<God>>;
         t.eval = &goddard_by_params<&plugin::eval<GodSmooth>, &plugin::eval<God>>;
         t.residual = &goddard_by_problem<&plugin::residual<GodSmooth>, &plugin::residual<God>>;
@@ -55,9 +56,17 @@ const ModelLaunchers *builtin_tables(int model_id)
         return t;
     }();
     // doubleIntegrator.cpp:26-34 defaults
-    static const ModelLaunchers dint = plugin::table<DInt>(SOCP_DINT_NPARAMS, 30, {1.0, 1.0, 0.01});
+    static const ModelLaunchers dint = [] {
+        ModelLaunchers t = plugin::table<DInt, false>(SOCP_DINT_NPARAMS, 30, {1.0, 1.0, 0.01});
+        t.fields = &fields_dint;
+        return t;
+    }();
     // covid19.cpp:25-38 defaults; its ModelInt integrates with its own stepNbr = 1000
-    static const ModelLaunchers covid = plugin::table<Covid>(SOCP_COVID_NPARAMS, 1000, {4, 10, 5, 1, 0.1, 1, -10, 20});
+    static const ModelLaunchers covid = [] {
+        ModelLaunchers t = plugin::table<Covid, false>(SOCP_COVID_NPARAMS, 1000, {4, 10, 5, 1, 0.1, 1, -10, 20});
+        t.fields = &fields_covid;
+        return t;
+    }();
     switch (model_id) {
     case SOCP_MODEL_GODDARD: return &goddard;
     case SOCP_MODEL_DOUBLE_INTEGRATOR: return &dint;

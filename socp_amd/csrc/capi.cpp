@@ -1222,6 +1222,82 @@ int socp_jacobi_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
                        [&] { return socp_jacobi_batch(c, B, Z, epsfcn, stride, skip, cap, tq, det, count, nchange, tconj, Jend); });
 }
 
+/* ---- batched exact fields ------------------------------------------------------------------ */
+
+int socp_ctx_has_fields(const socp_ctx *c) { return c ? (table_of(c)->fields ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+int fields_args(socp_ctx *c, const char *who, int B, int cols, int stride, int skip, int cap)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (cols != SOCP_FIELDS_COSTATE && cols != SOCP_FIELDS_ALL) return fail(c, SOCP_ERR_ARG, w + ": cols is SOCP_FIELDS_COSTATE or SOCP_FIELDS_ALL");
+    if (stride < 1) return fail(c, SOCP_ERR_ARG, w + ": stride >= 1 is required");
+    if (skip < 0) return fail(c, SOCP_ERR_ARG, w + ": skip >= 0 is required");
+    if (cap < 1) return fail(c, SOCP_ERR_ARG, w + ": cap >= 1 is required");
+    return args_tail(c, w, table_of(c)->fields != nullptr,
+                     "fields entry (a model with its own ComputeTraj, or one without the rhs_t trait)", "the exact fields follow");
+}
+}  // namespace
+
+int socp_fields_batch_dev(socp_ctx *c, int B, const double *d_Z, int cols, int stride, int skip, int cap, double *d_tq, double *d_det,
+                          int *d_count, int *d_nchange, double *d_tconj, double *d_Phi)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = fields_args(c, "fields_batch", B, cols, stride, skip, cap)) return rc;
+    if (B > 0 && (!d_Z || !d_tq || !d_det || !d_count || !d_nchange || !d_tconj)) return fail(c, SOCP_ERR_ARG, "fields_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_traj += (long long)B * c->M * (cols == SOCP_FIELDS_ALL ? c->S : c->S / 2); c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->fields(c->stream, c->P, c->pb, B, d_Z, cols, stride, skip, cap, d_tq, d_det, d_count, d_nchange, d_tconj, d_Phi));
+    return SOCP_OK;
+}
+
+int socp_fields_batch(socp_ctx *c, int B, const double *Z, int cols, int stride, int skip, int cap, double *tq, double *det, int *count,
+                      int *nchange, double *tconj, double *Phi)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = fields_args(c, "fields_batch", B, cols, stride, skip, cap)) return rc;
+    if (B > 0 && (!Z || !tq || !det || !count || !nchange || !tconj)) return fail(c, SOCP_ERR_ARG, "fields_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t s = (size_t)c->S, C = cols == SOCP_FIELDS_ALL ? s : s / 2, segs = (size_t)B * c->M, slots = segs * cap, nZ = (size_t)B * c->n,
+                 nP = Phi ? segs * s * C : 0;
+    double *dZ, *dT;
+    int *dC;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, dZ));
+    // tq and det travel both ways: what the kernel leaves untouched (entries at or beyond min(count, cap)) comes back as it went
+    HIP_TRY(c, stage_up(c, c->s_out, tq, slots, dT, 2 * slots + segs + nP));
+    double *dD = dT + slots, *dTc = dD + slots, *dP = dTc + segs;
+    HIP_TRY(c, copy_up(c, dD, det, slots));
+    HIP_TRY(c, c->s_var.reserve(sizeof(int) * 2 * segs));
+    dC = c->s_var.as<int>();
+    int *dN = dC + segs;
+    const int rc = socp_fields_batch_dev(c, B, dZ, cols, stride, skip, cap, dT, dD, dC, dN, dTc, Phi ? dP : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, tq, dT, slots));
+    HIP_TRY(c, copy_down(c, det, dD, slots));
+    HIP_TRY(c, copy_down(c, count, dC, segs));
+    HIP_TRY(c, copy_down(c, nchange, dN, segs));
+    HIP_TRY(c, copy_down(c, tconj, dTc, segs));
+    if (Phi) HIP_TRY(c, copy_down(c, Phi, dP, nP));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_fields_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                             const double *xnode, int cols, int stride, int skip, int cap, double *tq, double *det, int *count,
+                             int *nchange, double *tconj, double *Phi)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = fields_args(c, "fields_batch_blocks", B, cols, stride, skip, cap)) return rc;
+    if (const int rc = blocks_stride(c, "fields_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !tq || !det || !count || !nchange || !tconj)) return fail(c, SOCP_ERR_ARG, "fields_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_fields_batch(c, B, Z, cols, stride, skip, cap, tq, det, count, nchange, tconj, Phi); });
+}
+
 int socp_regrid_num_param(const socp_ctx *c, int M2, const int *mode_t2)
 {
     unsigned long long bits[4];

@@ -36,19 +36,21 @@ __device__ __forceinline__ double jacobi_pick(const double (&a)[D], int r)
     return __longlong_as_double(v);
 }
 
-// The determinant of the D x D matrix whose column c - 1 is in registers a[0 .. D) of lane base + c (c = 1 .. D; lane base
-// holds anything finite or not, it is not read).  Called by all 64 lanes; the result is the same in every lane of a group.
+// The determinant of the D x D matrix whose column c - OFF is in registers a[0 .. D) of lane base + c (c = OFF .. OFF + D - 1) of a
+// group of G lanes; the group's other lanes hold anything finite or not, they are not read.  OFF = 1, G = D + 1: the groups of
+// jacobi_group_kernel (lane base is the extremal); fields.hpp has OFF = 0 or D.  Called by all 64 lanes; the result is the
+// same in every lane of a group.
 // Gaussian elimination with partial pivoting in the operation order of include/socp_hip.h.  `a` is destroyed.
-template <int D>
+template <int D, int OFF = 1, int G = D + 1>
 __device__ __forceinline__ double jacobi_det(double (&a)[D], int base, int c)
 {
-    constexpr int G = D + 1;
+    static_assert(OFF >= 0 && OFF + D <= G && G <= 64, "the columns lie inside the group");
     // not finite anywhere in the group's columns -> NaN
     bool fin = true;
 #pragma unroll
     for (int r = 0; r < D; r++) fin = fin && (fabs(a[r]) <= 1.7976931348623157e308);
-    const unsigned long long bad = __ballot(c >= 1 && !fin);
-    const unsigned long long gmask = ((1ull << G) - 1ull) << base;
+    const unsigned long long bad = __ballot(c >= OFF && c < OFF + D && !fin);
+    const unsigned long long gmask = (G >= 64 ? ~0ull : ((1ull << (G & 63)) - 1ull)) << base;
     const bool nonfinite = (bad & gmask) != 0ull;
 
     double det = 0.0;
@@ -64,7 +66,7 @@ __device__ __forceinline__ double jacobi_det(double (&a)[D], int base, int c)
             best = gt ? fabs(a[r]) : best;
             p = gt ? r : p;
         }
-        const int owner = (base + k + 1) & 63;                      // (& 63: an idle lane behind the last group reads a lane that exists)
+        const int owner = (base + k + OFF) & 63;                      // (& 63: an idle lane behind the last group reads a lane that exists)
         p = __shfl(p, owner);
         // swap rows k and p (columns < k are finished: swapping them too changes nothing that is read again)
         const double ap = jacobi_pick<D>(a, p);
@@ -75,7 +77,7 @@ __device__ __forceinline__ double jacobi_det(double (&a)[D], int base, int c)
         const double v = __shfl(a[k], owner);
         zero = zero || (v == 0.0);
         det = (k == 0) ? v : det * v;
-        const bool mine = (c - 1) > k;
+        const bool mine = (c - OFF) > k;
 #pragma unroll
         for (int r = k + 1; r < D; r++) {
             const double l = __shfl(a[r] / v, owner);

@@ -39,9 +39,10 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 10;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 11;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
-                                   // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher
+                                   // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
+                                   // kPluginAbi = 11: batched exact-fields launcher
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -73,6 +74,12 @@ struct ModelLaunchers {
     // nchange[B][M], tconj[B][M] and, unless null, Jend[B][M][d][d]; fixed-step integrator only.  Null: the model has its own
     // ComputeTraj, or the entry is not offered for it
     hipError_t (*jacobi)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double, int, int, int, double *, double *,
+                         int *, int *, double *, double *);
+    // batched exact fields (socp_fields_batch): Z[B][n], cols (0: the d costate columns, 1: all s), stride, skip, cap ->
+    // tq[B][M][cap], det[B][M][cap], count[B][M], nchange[B][M], tconj[B][M] and, unless null, Phi[B][M][s][C]; fixed-step integrator
+    // only.  Null: the model has its own ComputeTraj, or no rhs_t trait (plugin_impl.hpp).  The in-tree models' entries live in
+    // kernels_fields.hip, one object without contraction that both flavours' tables point to
+    hipError_t (*fields)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, int, int, int, double *, double *,
                          int *, int *, double *, double *);
 };
 
@@ -181,6 +188,15 @@ hipError_t cost_total(hipStream_t st, int B, int M, const double *cost, double *
 // Xm[B][M2+1][S] and the target times T2[B][M2+1]; free_bits: bit j of word j / 64 = node j of the target is FREE (M2 <= 255)
 hipError_t regrid_pack(hipStream_t st, int B, int S, int M2, int n2, const unsigned long long (&free_bits)[4], const double *Xm,
                        const double *T2, double *Z2);
+
+// socp_fields_batch of the in-tree models (kernels_fields.hip: one object without contraction, for both flavours -- a throughput
+// context returns the same bits); Goddard's picks the law per launch like its other entries
+hipError_t fields_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int cols, int stride, int skip,
+                          int cap, double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi);
+hipError_t fields_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int cols, int stride, int skip,
+                       int cap, double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi);
+hipError_t fields_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int cols, int stride, int skip,
+                        int cap, double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi);
 
 // the in-tree models' tables, one translation unit each
 // Goddard, double integrator, covid19 by SOCP_MODEL_* id (builtin_tables.hpp); null for any other id

@@ -9,6 +9,7 @@
 // ocml's exp.  Citations: file:line into bherisse/socp.
 #pragma once
 #include "dev_common.hpp"
+#include "dual.hpp"
 #include "exp_glibc.hpp"
 
 namespace socp {
@@ -246,6 +247,117 @@ struct GoddardExactT {
         control(P, c, sw0, sw1, t, X, u);
     }
 
+    // ---- the right-hand side over a number type T (socp_fields_batch: T = Dual, dual.hpp) --------------------------------------
+    // goddard.cpp:48-253 restated expression by expression on PLAIN IEEE operations (no Den, no sqrt_in_range: their bits are
+    // those of plain division and sqrt in range, see above), in the reference's association order; tests/fast_reference.py
+    // (goddard_ref) is the same text in Python.  With T = double it gives the bits of rhs.  The thrust magnitude is a plain
+    // double where the law makes it a constant (off, full, a given singular value) and a T where it depends on the state; the
+    // text from there on is written once (`thrust`) and instantiated for both.
+    template <class T>
+    __device__ static __forceinline__ void costate_dots_t(const ModelParams &P, const T (&X)[S], const T &r, const T &v, const T &g,
+                                                         const T &E, const T &pvdotv, T (&pd)[6])
+    {
+        const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
+        const T p_x = X[7], p_y = X[8], p_z = X[9], p_vx = X[10], p_vy = X[11], p_vz = X[12];
+        const double KD = P.p[GP_KD], kr = P.p[GP_KR];
+        const T A = -kr*KD / mass*v*E;
+        const T Q = KD / mass*E;
+        pd[0] = A*x / r*pvdotv + g*(p_vx*(1 - 3 * x*x / r / r) / r - p_vy * 3 * x*y / r / r / r - p_vz * 3 * x*z / r / r / r);
+        pd[1] = A*y / r*pvdotv + g*(-p_vx * 3 * y*x / r / r / r + p_vy*(1 - 3 * y*y / r / r) / r - p_vz * 3 * y*z / r / r / r);
+        pd[2] = A*z / r*pvdotv + g*(-p_vx * 3 * z*x / r / r / r - p_vy * 3 * z*y / r / r / r + p_vz*(1 - 3 * z*z / r / r) / r);
+        pd[3] = -p_x + Q*(pvdotv*vx / v + p_vx*v);
+        pd[4] = -p_y + Q*(pvdotv*vy / v + p_vy*v);
+        pd[5] = -p_z + Q*(pvdotv*vz / v + p_vz*v);
+    }
+
+    // goddard.cpp:188-253 on T
+    template <class T>
+    __device__ static __forceinline__ T singular_control_t(const ModelParams &P, const T (&X)[S], const T &r, const T &v, const T &g,
+                                                          const T &norm_pv, const T &E, const T &pvdotv, const T (&pd)[6])
+    {
+        const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
+        const T p_x = X[7], p_y = X[8], p_z = X[9], p_vx = X[10], p_vy = X[11], p_vz = X[12];
+        const double b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
+        const T rdotv = x*vx + y*vy + z*vz;
+        const T D = KD*E;
+        const T prdotdotpv = pd[0]*p_vx + pd[1]*p_vy + pd[2]*p_vz;
+        const T prdotpvdot = p_x*pd[3] + p_y*pd[4] + p_z*pd[5];
+        const T prdotpv = p_x*p_vx + p_y*p_vy + p_z*p_vz;
+        const T pvdotdotv = pd[3]*vx + pd[4]*vy + pd[5]*vz;
+        const T pvdotdotpv = pd[3]*p_vx + pd[4]*p_vy + pd[5]*p_vz;
+        const T vdotg = vx*g*x / r + vy*g*y / r + vz*g*z / r;
+        const T pvdotg = p_vx*g*x / r + p_vy*g*y / r + p_vz*g*z / r;
+
+        const T au = 2 * norm_pv*C / mass*pvdotv
+            + 2 * pvdotv*C / mass*norm_pv
+            - b / mass*(2 * pvdotv*pvdotv + norm_pv*norm_pv*v*v)
+            - b / D*v*prdotpv - C / D*prdotpv / v*pvdotv / norm_pv;
+
+        const T bu = -2 * norm_pv*norm_pv*(vdotg + D / mass*v*v*v) + 2 * v*v*pvdotdotpv
+            - 2 * pvdotv*(pvdotg + D / mass*v*pvdotv - pvdotdotv)
+            + b / C*(2 * norm_pv*pvdotv*(vdotg + D / mass*v*v*v) + norm_pv*v*v*(pvdotg + D / mass*v*pvdotv - pvdotdotv) - v*v*pvdotv / norm_pv*pvdotdotpv)
+            - mass / D*kr*rdotv / r*v*prdotpv + mass / D*prdotpv / v*(vdotg + D / mass*v*v*v) - mass / D*v*(prdotdotpv + prdotpvdot);
+
+        return bu / au;
+    }
+
+    template <class T>
+    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S])
+    {
+        const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
+        const T p_vx = X[10], p_vy = X[11], p_vz = X[12], p_mass = X[13];
+        const double b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR], u_max = P.p[GP_UMAX];
+        const T r = d_sqrt(x*x + y*y + z*z);
+        const T v = d_sqrt(vx*vx + vy*vy + vz*vz);
+        const T pvdotv = p_vx*vx + p_vy*vy + p_vz*vz;
+        const T g = 1 / r / r;
+        const T norm_pv = d_sqrt(p_vx*p_vx + p_vy*p_vy + p_vz*p_vz);
+        const T Switch = P.p[GP_MU1] - b*p_mass - C / mass*norm_pv;
+        const T E = d_exp(-kr*(r - 1));
+        T pd[6];
+        costate_dots_t<T>(P, X, r, v, g, E, pvdotv, pd);
+
+        T u[3];
+        // goddard.cpp:147-185 from the thrust magnitude on; A = double or T
+        auto thrust = [&](const auto &alpha_u) {
+            u[0] = -p_vx*alpha_u / norm_pv;
+            u[1] = -p_vy*alpha_u / norm_pv;
+            u[2] = -p_vz*alpha_u / norm_pv;
+            const auto norm_a = d_abs(alpha_u);
+            if (d_val(norm_a) > u_max) {
+                u[0] = u[0] / norm_a*u_max;
+                u[1] = u[1] / norm_a*u_max;
+                u[2] = u[2] / norm_a*u_max;
+            }
+        };
+        if (SMOOTH || P.p[GP_MU2] > 0) {
+            if (d_val(Switch) < 0) thrust(-Switch / 2 / P.p[GP_MU2]);
+            else thrust(0.0);
+        } else if constexpr (!SMOOTH) {
+            if (t <= sw0) thrust(1.0);
+            else if (t > sw0 && t <= sw1) {
+                if (P.p[GP_SING] < 0) thrust(singular_control_t<T>(P, X, r, v, g, norm_pv, E, pvdotv, pd));
+                else thrust(P.p[GP_SING]);
+            } else thrust(0.0);
+        }
+        const T norm_u = d_sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        const T pvdotu = p_vx*u[0] + p_vy*u[1] + p_vz*u[2];
+        dX[0] = vx;
+        dX[1] = vy;
+        dX[2] = vz;
+        dX[3] = -KD*v*vx*E / mass - g*x / r + C*u[0] / mass;
+        dX[4] = -KD*v*vy*E / mass - g*y / r + C*u[1] / mass;
+        dX[5] = -KD*v*vz*E / mass - g*z / r + C*u[2] / mass;
+        dX[6] = -b*norm_u;
+        dX[7] = pd[0];
+        dX[8] = pd[1];
+        dX[9] = pd[2];
+        dX[10] = pd[3];
+        dX[11] = pd[4];
+        dX[12] = pd[5];
+        dX[13] = -KD*E / mass / mass*v*pvdotv + C / mass / mass*pvdotu;
+    }
+
     // goddard.cpp:256-295
     __device__ static double hamiltonian(const ModelParams &P, double sw0, double sw1, double t, const double (&X)[S])
     {
@@ -320,6 +432,28 @@ struct DIntExact {
         dX[0] = X[3];  dX[1] = X[4];  dX[2] = X[5];
         dX[3] = a_max * u[0];  dX[4] = a_max * u[1];  dX[5] = a_max * u[2];
         dX[6] = 0;  dX[7] = 0;  dX[8] = 0;
+        dX[9] = -X[6];  dX[10] = -X[7];  dX[11] = -X[8];
+    }
+
+    // the right-hand side over a number type T (socp_fields_batch: T = Dual, dual.hpp): doubleIntegrator.cpp:67-108, 218-259 on
+    // plain IEEE operations; with T = double the bits of rhs
+    template <class T>
+    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double, double, double, const T (&X)[S], T (&dX)[S])
+    {
+        const double a_max = P.p[DP_AMAX], u_max = P.p[DP_UMAX];
+        T u[3];
+        u[0] = -X[9] / a_max;
+        u[1] = -X[10] / a_max;
+        u[2] = -X[11] / a_max;
+        const T norm_u = d_sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
+        if (d_val(norm_u) > u_max) {
+            u[0] = u[0] / norm_u*u_max;
+            u[1] = u[1] / norm_u*u_max;
+            u[2] = u[2] / norm_u*u_max;
+        }
+        dX[0] = X[3];  dX[1] = X[4];  dX[2] = X[5];
+        dX[3] = a_max * u[0];  dX[4] = a_max * u[1];  dX[5] = a_max * u[2];
+        dX[6] = T(0.0);  dX[7] = T(0.0);  dX[8] = T(0.0);
         dX[9] = -X[6];  dX[10] = -X[7];  dX[11] = -X[8];
     }
 
@@ -411,6 +545,36 @@ struct CovidExact {
         dX[5] = (pE - pI) / Tinc;
         dX[6] = (pS - pE)*R*Sx / Tinf / N + (pI - pR) / Tinf + Ipen;
         dX[7] = 0;
+    }
+
+    // the right-hand side over a number type T (socp_fields_batch: T = Dual, dual.hpp): covid19.cpp:53-126 on plain IEEE
+    // operations; with T = double the bits of rhs.  A clamped control and an inactive penalty are plain doubles, as the
+    // definition has them: the text from the control on is written once (`rest`) and instantiated for both.
+    template <class T>
+    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double, double, double, const T (&X)[S], T (&dX)[S])
+    {
+        const T Sx = X[0], E = X[1], I = X[2], R = X[3], pS = X[4], pE = X[5], pI = X[6], pR = X[7];
+        const double R0 = P.p[CP_R0], Tinf = P.p[CP_TINF], Tinc = P.p[CP_TINC], N = P.p[CP_N];
+        auto rest = [&](const auto &u) {
+            const auto Rt = R0 * (1 - u);
+            dX[0] = -Rt / Tinf / N*Sx*I;
+            dX[1] = Rt / Tinf / N*Sx*I - E / Tinc;
+        };
+        const T u = (pE - pS)*Sx*I / Tinf / N * R0;
+        double uc = 0.0;
+        bool clamped = false;
+        if (d_val(u) <= P.p[CP_UMIN]) { uc = P.p[CP_UMIN]; clamped = true; }
+        if ((clamped ? uc : d_val(u)) >= P.p[CP_UMAX]) { uc = P.p[CP_UMAX]; clamped = true; }
+        if (clamped) rest(uc);
+        else rest(u);
+        dX[2] = E / Tinc - I / Tinf;
+        dX[3] = I / Tinf;
+        dX[4] = (pS - pE)*R*I / Tinf / N;
+        dX[5] = (pE - pI) / Tinc;
+        const T d6 = (pS - pE)*R*Sx / Tinf / N + (pI - pR) / Tinf;
+        if (d_val(I) >= P.p[CP_IMAX]) dX[6] = d6 + -P.p[CP_MUI]*(I - P.p[CP_IMAX]);
+        else dX[6] = d6 + 0.0;
+        dX[7] = T(0.0);
     }
 
     // covid19.cpp:128-165

@@ -37,6 +37,11 @@
 //                 // element e of Model(t, Y, isJac = 1), Y = [X(S) ; R(S x S)], R[k][i] at Y[S (k+1) + i]  
 //       __device__ static void dhamiltonian(const socp::ModelParams &P, double t, const double *X, double (&dH)[S + 1]);
 //                 // Hamiltonian(t, X, isJac = 1): dH/dX (S entries), then dH/dt
+//       // OPTIONAL -- the right-hand side over a number type (socp_fields_batch: exact Jacobi fields and transition matrices on
+//       // dual numbers, dual.hpp).  The text of rhs on plain IEEE operations, d_sqrt / d_abs / d_exp for the functions and d_val
+//       // where a comparison reads a value; a quantity that is a constant stays a plain double.  With T = double: the bits of rhs.
+//       template <class T> __device__ static void rhs_t(const socp::ModelParams &P, double sw0, double sw1, double t,
+//                                                       const T (&X)[S], T (&dX)[S]);
 //   };
 //   SOCP_DEFINE_MODEL_PLUGIN(1001, MyModel, 3 /*nparams*/, 30 /*stepNbr*/, {1.0, 2.0, 3.0})
 //
@@ -44,9 +49,10 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
+#include "fields.hpp"
 #include "jacobi.hpp"
 #include "launch.hpp"
 #include "variational.hpp"
@@ -211,6 +217,40 @@ hipError_t jacobi(hipStream_t st, const ModelParams &P, const ProblemDev &pb, in
     return hipGetLastError();
 }
 
+// optional trait rhs_t: the right-hand side over a number type -> the model has exact fields (socp_fields_batch)
+template <class M, class = void> struct has_fields : std::false_type {};
+template <class M>
+struct has_fields<M, std::void_t<decltype(M::template rhs_t<Dual>(std::declval<const ModelParams &>(), 0.0, 0.0, 0.0,
+                                                                   std::declval<const Dual (&)[M::S]>(), std::declval<Dual (&)[M::S]>()))>>
+    : std::true_type {};
+
+// batched exact fields: fixed-step integrator only.  One group of C neighbouring lanes per (row, segment), 64 / C groups per
+// single-wave workgroup (fields.hpp); always one wave per SIMD.  The translation unit must be built without contraction
+template <class Mdl, bool ALL>
+hipError_t fields_cols(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int skip, int cap,
+                       double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi)
+{
+    constexpr int gpw = 64 / (ALL ? Mdl::S : Mdl::D);
+    const long slabs = (long)B * pb.M;
+    const unsigned grid = (unsigned)((slabs + gpw - 1) / gpw);
+    if (pb.pp_params || pb.pp_time || pb.pp_xnode)
+        hipLaunchKernelGGL((fields_group_kernel<Mdl, ALL, true>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, stride, skip, cap, tq, det, count,
+                           nchange, tconj, Phi);
+    else
+        hipLaunchKernelGGL((fields_group_kernel<Mdl, ALL, false>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, stride, skip, cap, tq, det, count,
+                           nchange, tconj, Phi);
+    return hipGetLastError();
+}
+template <class Mdl>
+hipError_t fields(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int cols, int stride, int skip, int cap,
+                  double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0 || cols < 0 || cols > 1 || stride < 1 || skip < 0 || cap < 1) return hipErrorInvalidValue;
+    return cols ? fields_cols<Mdl, true>(st, P, pb, B, Z, stride, skip, cap, tq, det, count, nchange, tconj, Phi)
+                : fields_cols<Mdl, false>(st, P, pb, B, Z, stride, skip, cap, tq, det, count, nchange, tconj, Phi);
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -218,7 +258,8 @@ struct has_variational<M, std::void_t<decltype(M::aug_rhs(std::declval<const Mod
                                       decltype(M::dhamiltonian(std::declval<const ModelParams &>(), 0.0, (const double *)nullptr,
                                                                std::declval<double (&)[M::S + 1]>()))>> : std::true_type {};
 
-template <class Mdl>
+// FIELDS = false: leave the fields entry to the caller (the in-tree models' entries live in kernels_fields.hip, builtin_tables.hpp)
+template <class Mdl, bool FIELDS = true>
 ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> defaults)
 {
     static_assert(Mdl::S == 2 * Mdl::D, "state vector is [state ; costate]");
@@ -236,6 +277,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
         t.event_channels = event_channels<Mdl>::value; t.events = &events<Mdl>;
     }
     if constexpr (!has_custom_traj<Mdl>::value && !no_jacobi<Mdl>::value) t.jacobi = &jacobi<Mdl>;   // nor Jacobi fields (their chart changes rewrite the costate)
+    if constexpr (FIELDS && has_fields<Mdl>::value && !has_custom_traj<Mdl>::value) t.fields = &fields<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

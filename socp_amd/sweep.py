@@ -359,6 +359,31 @@ def jacobi_local(ctx, args, local, lo, rank, params=None):
             "wall_s": wall, "file": path}
 
 
+def fields_local(ctx, args, local, lo, rank, params=None):
+    """--fields-out: the conjugate-time test with EXACT Jacobi fields (socp_fields_batch) of this rank's CONVERGED chains, each with
+    its own parameter block when the chains have one: det of J(t) = dx(t)/dp(t0), carried through the residual's RK4 steps on dual
+    numbers, sampled every --fields-stride steps of every segment, its sign changes from sample --fields-skip on.  Written to
+    PATH.rank<r>.npz: index [k], tq [k][M][cap], det [k][M][cap], count [k][M], nchange [k][M], tconj [k][M] (NaN: none) and, with
+    --fields-phi, phi [k][M][s][s] = the transition matrix dX(t_{i+1})/dX(t_i) of every segment.  Runs after the timed solve.
+    Returns the record entry of this rank; a measuring instrument like --jacobi-out, not a verdict."""
+    from . import capi
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.fields_out)
+    t0 = time.perf_counter()
+    r = ctx.fields_batch(z, cols=capi.FIELDS_ALL if args.fields_phi else capi.FIELDS_COSTATE, stride=args.fields_stride, skip=args.fields_skip,
+                         phi=args.fields_phi, blocks=None if own is None else (own, None, None))
+    r = {k: v.cpu().numpy() for k, v in r.items()}
+    wall = time.perf_counter() - t0
+    arrays = dict(index=index, tq=r["tq"], det=r["det"], count=r["count"], nchange=r["nchange"], tconj=r["tconj"])
+    if args.fields_phi:
+        arrays["phi"] = r["phi"]
+    np.savez(path, **arrays)
+    changed = r["nchange"].sum(axis=1) > 0 if len(conv) else np.zeros(0, dtype=bool)
+    first = np.array([np.nanmin(row) for row in r["tconj"][changed]]) if changed.any() else np.zeros(0)
+    return {"rows": int(len(conv)), "with_change": int(changed.sum()), "tconj_min": float(first.min()) if len(first) else None,
+            "tconj_median": float(np.median(first)) if len(first) else None, "stride": args.fields_stride, "skip": args.fields_skip,
+            "phi": bool(args.fields_phi), "wall_s": wall, "file": path}
+
+
 def tangent_local(ctx, args, local, lo, rank, params=None):
     """--tangent-out: the sensitivity dz/dtheta (socp_tangent_batch) of this rank's CONVERGED chains to the packed parameter
     --tangent-param, each chain with its own parameter block when the chains have one, written to PATH.rank<r>.npz: index [k] =
@@ -612,6 +637,15 @@ def main():
                          "chains' own parameter blocks; writes PATH.rank<r>.npz (index, tq, det, count, nchange, tconj) and adds jacobi "
                          "{rows, with_change, tconj_min, tconj_median, stride, skip, wall_s, file} to the record.  Not with --model "
                          "interceptor.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--fields-out", default=None, metavar="PATH",
+                    help="after the solve, run the conjugate-time test with EXACT Jacobi fields on this rank's converged chains as one "
+                         "batch (socp_fields_batch): dx(t)/dp(t0) carried through the RK4 steps on dual numbers, no forward "
+                         "difference; writes PATH.rank<r>.npz (index, tq, det, count, nchange, tconj; phi with --fields-phi) and adds "
+                         "fields {rows, with_change, tconj_min, tconj_median} to the record.  Not for the interceptor")
+    ap.add_argument("--fields-stride", type=int, default=100, metavar="K", help="with --fields-out: sample every K-th step (and the last)")
+    ap.add_argument("--fields-skip", type=int, default=0, metavar="S", help="with --fields-out: compare the samples from the S-th on")
+    ap.add_argument("--fields-phi", action="store_true",
+                    help="with --fields-out: all 2d columns, and the transition matrix of every segment in the file")
     ap.add_argument("--jacobi-stride", type=int, default=100, metavar="K", help="with --jacobi-out: sample every K-th step (and the last)")
     ap.add_argument("--jacobi-skip", type=int, default=1, metavar="S",
                     help="with --jacobi-out: compare the samples from the S-th on (near t0 the difference matrix is singular to rounding)")
@@ -647,6 +681,10 @@ def main():
         ap.error("--events-out: the interceptor has no event channels (its own ComputeTraj rewrites the costate in mid-trajectory)")
     if args.jacobi_out and args.model == "interceptor":
         ap.error("--jacobi-out: the interceptor has no Jacobi-field kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
+    if args.fields_out and args.model == "interceptor":
+        ap.error("--fields-out: the interceptor has no exact-fields kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
+    if args.fields_stride < 1 or args.fields_skip < 0:
+        ap.error("--fields-stride must be >= 1 and --fields-skip >= 0")
     if args.jacobi_stride < 1 or args.jacobi_skip < 0:
         ap.error("--jacobi-stride must be >= 1 and --jacobi-skip >= 0")
     if bool(args.regrid_out) != (args.regrid_segments > 0) or not 0 <= args.regrid_segments <= 255:
@@ -783,6 +821,8 @@ def main():
         extra["tangent_rank%d" % rank] = tangent_local(ctx, args, local, lo_w, rank, blocks)
     if args.jacobi_out:
         extra["jacobi" if rank == 0 else "jacobi_rank%d" % rank] = jacobi_local(ctx, args, local, lo_w, rank, blocks)
+    if args.fields_out:
+        extra["fields" if rank == 0 else "fields_rank%d" % rank] = fields_local(ctx, args, local, lo_w, rank, blocks)
     if args.sing_out:
         extra["singular" if rank == 0 else "singular_rank%d" % rank] = singular_local(ctx, args, local, lo_w, rank, blocks)
     if args.branch_out:
