@@ -17,11 +17,12 @@
 // device library's, so -- unlike Goddard's exp -- rows 6..8 of the RHS and the Hamiltonian are NOT bit-identical
 // to the CPU path (every other row is).  Pinned to reference-generated vectors (tests/test_gpu_vtol.py).
 // VtolFast: restructured; one exponential per box and axis serves 1 - tanh h and 1 - tanh^2 h.
+// Both are held per component to a 240-bit evaluation within a derived bound (tests/test_gpu_vtol_pin.py).
 //
 // Upstream quirks kept on purpose: the ellipsoid gradient's `rad` omits the z term and its z component is zero;
 // only the obstacle part of the map is live (the waypoint part is commented out upstream: psiWP multiplies zero);
 // a position exactly on a box's centre plane makes the term NaN and the isnan reset then zeroes the WHOLE
-// component; normV = 0 gives a NaN right-hand side.
+// component; normV = 0 gives NaN in rows 9..11 (0 / 0) and nowhere else, in both flavours.
 #pragma once
 #include "integrator.hpp"
 
@@ -224,7 +225,8 @@ struct VtolT {
         if constexpr (FAST) {
             const double v2 = vx*vx + vy*vy + vz*vz;
             const double inv = vfast::rsqrt(v2);
-            const double normV = v2 * inv;
+            // rsqrt(0) is NaN: at rest normV is v2 itself, so rows 3..5 stay finite as upstream (rows 9..11 are NaN there, as upstream)
+            const double normV = v2 > 0 ? v2 * inv : v2;
             dX[3] = a_max*u[0] - ca*vx*normV;
             dX[4] = a_max*u[1] - ca*vy*normV;
             dX[5] = a_max*u[2] - ca*vz*normV;

@@ -16,6 +16,9 @@ Error model of Tracked (u = 2^-53, res the exact result, ea / eb the operands' b
     a +- b   ea + eb + u|res|                          a * b    |a| eb + |b| ea + u|res|
     a / b    (ea + |res| eb)/|b| + u|res|              sqrt a   ea / (2 sqrt a) + u|res|
     exp a    |res| ea + C_EXP u|res|                   1/a, 1/sqrt a as the fast flavour forms them: same propagation, C_RCP, C_RSQ
+    tanh a   (1 - res^2) ea + C_TANH u|res|            (a kit built with c_exp = C_EXP_LIB charges the library's exp that budget)
+Within second_order_products() a product also carries ea eb: where BOTH factors vanish to the working precision (vtolUAV's 1 - tanh h
+far from a box) the first-order terms are zero and that term is all that is left.  Goddard and covid19 do not use it.
 Inputs and parameters carry err = 0.  C_EXP = C_RCP = C_RSQ = 2: the budget the comments of models_fast.hpp claim, doubled.  A fused
 multiply-add is counted as a product and a sum (two roundings): an upper bound of what contraction does.  Gradual underflow is in
 the model the standard way (Higham 2.8): a product, quotient, root or exp whose result is subnormal adds 2^-1075 absolute; an exp
@@ -25,6 +28,8 @@ Every branch decision is taken on the exact value and recorded with the Tracked 
 margin exceeds 4x its error (a margin whose error is zero, e.g. t == sw0 compared exactly, is decidable: both flavours compare the
 same two doubles).  Near a kink the flavours may take different branches; `flip` forces the other branch of named decisions.
 """
+import contextlib
+
 import numpy as np
 
 try:
@@ -39,6 +44,10 @@ except ImportError:                                   # the GPU tests read the f
 
 F64 = np.float64
 C_EXP = C_RCP = C_RSQ = 2
+# library calls whose accuracy the project does not control (vtolUAV: the device library's tanh and exp): the published OpenCL
+# full-profile limits the device library is built to, tanh <= 5 ulp and exp <= 3 ulp, with ulp = 2u.  Taken from the specification,
+# not measured.
+C_TANH, C_EXP_LIB = 10, 6
 DECIDE_FACTOR = 4
 
 if HAVE_MPMATH:
@@ -51,6 +60,7 @@ if HAVE_MPMATH:
 class Tracked:
     """value (mpf, the exact result of the expression so far) and err (mpf, first-order bound of |computed - value|)."""
     __slots__ = ("v", "e")
+    second_order = False                              # second_order_products() sets it
 
     def __init__(self, v, e=0):
         self.v = v if isinstance(v, mpf) else mpf(float(v))
@@ -89,7 +99,10 @@ class Tracked:
 
     def __mul__(self, o):
         o = Tracked.lift(o)
-        return Tracked._rounded(self.v * o.v, abs(self.v) * o.e + abs(o.v) * self.e)
+        prop = abs(self.v) * o.e + abs(o.v) * self.e
+        if Tracked.second_order:
+            prop += self.e * o.e
+        return Tracked._rounded(self.v * o.v, prop)
 
     __rmul__ = __mul__
 
@@ -100,6 +113,16 @@ class Tracked:
 
     def __rtruediv__(self, o):
         return Tracked.lift(o) / self
+
+
+@contextlib.contextmanager
+def second_order_products():
+    """Tracked products carry |a| eb + |b| ea + ea eb (the exact bound of a product of two perturbed factors) while this is open."""
+    before, Tracked.second_order = Tracked.second_order, True
+    try:
+        yield
+    finally:
+        Tracked.second_order = before
 
 
 class _Kit:
@@ -115,6 +138,13 @@ class _Kit:
         self.margins[name] = m
         return (not d) if name in self.flip else bool(d)
 
+    def cmp_exact(self, name, a, b, op):
+        """a op b for two INPUTS (doubles, no error): both flavours compare the same two doubles, so the margin's error is zero."""
+        m = self.exact_diff(a, b)
+        v = self.value(m)
+        self.margins[name] = m
+        return bool({"<": v < 0, ">": v > 0, "==": v == 0}[op])
+
 
 class MpfKit(_Kit):
     def lift(self, x):
@@ -123,31 +153,47 @@ class MpfKit(_Kit):
     def value(self, x):
         return x
 
+    def exact_diff(self, a, b):
+        return a - b
+
     sqrt = staticmethod(lambda x: mpmath.sqrt(x))
     exp = staticmethod(lambda x: mpmath.exp(x))
+    tanh = staticmethod(lambda x: mpmath.tanh(x))
     rcp = staticmethod(lambda x: 1 / x)
     rsqrt = staticmethod(lambda x: 1 / mpmath.sqrt(x))
 
 
 class TrackedKit(_Kit):
+    def __init__(self, flip=(), c_exp=C_EXP):
+        super().__init__(flip)
+        self.c_exp = c_exp
+
     def lift(self, x):
         return Tracked(x)
 
     def value(self, x):
         return x.v
 
+    def exact_diff(self, a, b):
+        assert a.e == 0 and b.e == 0
+        return Tracked(a.v - b.v, 0)
+
     @staticmethod
     def sqrt(a):
         res = mpmath.sqrt(a.v)
         return Tracked._rounded(res, a.e / (2 * res) if a.e else mpf(0))
 
-    @staticmethod
-    def exp(a):
+    def exp(self, a):
         res = mpmath.exp(a.v)
-        e = res * a.e + C_EXP * U * res
+        e = res * a.e + self.c_exp * U * res
         if res < TINY:
             e += EXP_FLOOR
         return Tracked(res, e)
+
+    @staticmethod
+    def tanh(a):
+        res = mpmath.tanh(a.v)
+        return Tracked(res, (1 - res * res) * a.e + C_TANH * U * abs(res))
 
     @staticmethod
     def rcp(a):
@@ -170,18 +216,23 @@ class F64Kit(_Kit):
     """numpy.float64, one rounding per operation; 1/x, 1/sqrt x and exp from numpy unless replaced (the mutation checks replace
     them); flip_gravity_gradient negates the p_v / r^3 term of the fast structure's dX[7]."""
 
-    def __init__(self, flip=(), rcp=None, rsqrt=None, exp=None, flip_gravity_gradient=False):
+    def __init__(self, flip=(), rcp=None, rsqrt=None, exp=None, tanh=None, flip_gravity_gradient=False, mutation=None):
         super().__init__(flip)
         self.rcp = rcp or (lambda x: F64(1.0) / x)
         self.rsqrt = rsqrt or (lambda x: F64(1.0) / np.sqrt(x))
         self.exp = exp or np.exp
+        self.tanh = tanh or np.tanh
         self.flip_gravity_gradient = flip_gravity_gradient
+        self.mutation = mutation                      # vtol_reference.vtol_fast: a named structural defect of the mutation checks
 
     def lift(self, x):
         return F64(x)
 
     def value(self, x):
         return x
+
+    def exact_diff(self, a, b):
+        return a - b
 
     sqrt = staticmethod(np.sqrt)
 
