@@ -1,17 +1,18 @@
 /*
  * interceptor_oracle.c -- CPU ORACLE for the interceptor model (test infrastructure, NOT product code).
  *
- * PARITY UNPINNED: the reference's interceptor.cpp includes "Eigen/Dense" (interceptor.cpp:15), which
- * this image lacks, so that translation unit cannot be compiled here and the reference ships no
- * output of it (no golden trace, no asserting test).  This file is therefore a
- * restatement from the source text alone.  What stands in for a pin (tests/test_oracle_interceptor.py):
- *   - the costate equations are checked against -dH/dx of the restated Hamiltonian by central
- *     differences in both charts (a transcription slip in either breaks it);
- *   - chart 1 -> 2 -> 1 is the identity and H is invariant under the chart change;
- *   - the 6x6 solve is checked against numpy.
- * The two Eigen calls (Jac.lu().solve(p), Jac*p; interceptor.cpp:715-716, :829-830) are restated as
- * textbook partial-pivot LU and row-times-vector sums; Eigen's internal summation order is not
- * reproducible without Eigen, so chart switches agree with the reference only to rounding.
+ * PINNED to the reference's own object code: oracle/Makefile compiles the reference's interceptor.cpp as it lies against
+ * oracle/eigen_shim (a stand-in of this repository's for the three things that file uses of Eigen) into
+ * oracle/_ref/libsocp_ref_interceptor.so, and tests/test_interceptor_pin_cpu.py holds this file to its doubles BIT FOR BIT
+ * (tests/golden/interceptor_pin.npz): right-hand side, control and Hamiltonian in both charts and both stages, the stage
+ * and chart logic of ComputeTraj, the final rows, the analytical guess.  Through a chart change the pin holds up to Eigen's
+ * summation order: the two Eigen calls (Jac.lu().solve(p), Jac*p; interceptor.cpp:715-716, :829-830) are a partial-pivot LU
+ * and row-times-vector sums here AND in the shim, operation for operation; Eigen's internal order is not reproduced.
+ * Bit equality is a property of the two texts when sin() and cos() are libm's: the compiler otherwise fuses some pairs into
+ * glibc's sincos(), which differs from them in the last place for ~0.07 % of arguments (oracle/Makefile: NOFUSE).
+ * The adaptive interceptor (orc_interceptor_compute_traj_adaptive) remains an extension with no upstream counterpart.
+ * Independent of the pin (tests/test_oracle_interceptor.py): the costate equations against -dH/dx of the Hamiltonian by
+ * central differences in both charts; chart 1 -> 2 -> 1 is the identity and H is invariant; the 6x6 solve against numpy.
  *
  * Citations are file:line into /root/reference/src/models/interceptor/interceptor.cpp.
  * Arithmetic order follows the cited expressions term by term (trigonometric values are named once

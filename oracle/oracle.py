@@ -16,6 +16,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "_build", "libsocp_oracle.so")
+ORACLE_PIN_SO = os.path.join(HERE, "_build", "libsocp_oracle_pin.so")      # the same text, sin/cos not fused into sincos (oracle/Makefile)
 REF_SO = os.path.join(HERE, "_ref", "libsocp_ref.so")
 
 MODEL_GODDARD, MODEL_DINT, MODEL_COVID, MODEL_INTERCEPTOR = 1, 2, 3, 4
@@ -68,10 +69,11 @@ class Problem:
 
 
 class Oracle:
-    def __init__(self, model_id, step_nbr=None, params=None):
-        if not os.path.exists(ORACLE_SO):
+    def __init__(self, model_id, step_nbr=None, params=None, pin_build=False):
+        so = ORACLE_PIN_SO if pin_build else ORACLE_SO
+        if not os.path.exists(so):
             build(ref=False)
-        self.lib = C.CDLL(ORACLE_SO)
+        self.lib = C.CDLL(so)
         self.lib.orc_goddard_singular_control.restype = C.c_double
         self.lib.orc_integrate.restype = C.c_long
         self.lib.orc_model_int.restype = C.c_long
@@ -200,6 +202,14 @@ class Oracle:
         Xf = np.ascontiguousarray(Xf, dtype=np.float64)
         self.lib.orc_interceptor_init_analytical(C.byref(self.m), C.c_double(ti), _d(Xi), C.c_double(tf), _d(Xf))
         return Xi
+
+    def final_rows(self, Xtf, Xf, mode_x):
+        """interceptor FinalFunction rows (FinalHFunction's seventh row is hamiltonian(tf, Xtf) + muT at the flags in force)."""
+        mode = np.ascontiguousarray(mode_x, dtype=np.int32)
+        out = np.empty(6)
+        self.lib.orc_interceptor_final_rows(C.byref(self.m), _d(np.ascontiguousarray(Xtf, dtype=np.float64)),
+                                            _d(np.ascontiguousarray(Xf, dtype=np.float64)), mode.ctypes.data_as(_ip), _d(out))
+        return out
 
     def traj_dopri5(self, t0, X0, tf, tol, is_jac=0):
         """Adaptive Dormand-Prince segment, initial step (tf - t0)/stepNbr; is_jac = 1: on the augmented state [X ; dX/dX0].
@@ -386,3 +396,86 @@ class Ref:
         else:
             sec = self.lib.ref_goddard_traj_batch(int(threads), int(step_nbr), _d(params), B, _d(t0), _d(tf), _d(X0), _d(Xf))
         return Xf, sec
+
+
+REF_INTERCEPTOR_SO = os.path.join(HERE, "_ref", "libsocp_ref_interceptor.so")
+
+
+def have_ref_interceptor():
+    return os.path.exists(REF_INTERCEPTOR_SO)
+
+
+class RefInterceptor:
+    """The reference's own interceptor object behind oracle/ref_interceptor_driver.cpp (its interceptor.cpp compiled
+    against oracle/eigen_shim).  Same calls as ``Oracle(MODEL_INTERCEPTOR)``; authoring machine only."""
+
+    def __init__(self, params=None, step_nbr=None):
+        self.lib = L = C.CDLL(REF_INTERCEPTOR_SO)
+        L.ref_icpt_new.restype = C.c_void_p
+        L.ref_icpt_hamiltonian.restype = C.c_double
+        L.ref_icpt_mass.restype = C.c_double
+        self.h = C.c_void_p(L.ref_icpt_new())
+        if params is not None or step_nbr is not None:
+            p, n = self.params()
+            self.set_params(p if params is None else params, n if step_nbr is None else step_nbr)
+
+    def __del__(self):
+        try:
+            self.lib.ref_icpt_free(self.h)
+        except Exception:
+            pass
+
+    def params(self):
+        p = np.empty(18)
+        n = C.c_int(0)
+        self.lib.ref_icpt_get_params(self.h, _d(p), C.byref(n))
+        return p, n.value
+
+    def set_params(self, params, step_nbr):
+        p = np.ascontiguousarray(params, dtype=np.float64)[:18].copy()
+        self.lib.ref_icpt_set_params(self.h, _d(p), int(step_nbr))
+
+    def set_flags(self, chart, stage):
+        self.lib.ref_icpt_set_flags(self.h, int(chart), int(stage))
+
+    def flags(self):
+        c, s = C.c_int(0), C.c_int(0)
+        self.lib.ref_icpt_get_flags(self.h, C.byref(c), C.byref(s))
+        return c.value, s.value
+
+    def _vec(self, fn, n, *args):
+        out = np.empty(n)
+        fn(self.h, *args, _d(out))
+        return out
+
+    def rhs(self, t, X):
+        return self._vec(self.lib.ref_icpt_rhs, 12, C.c_double(t), _d(np.ascontiguousarray(X, dtype=np.float64)))
+
+    def control(self, t, X):
+        return self._vec(self.lib.ref_icpt_control, 2, C.c_double(t), _d(np.ascontiguousarray(X, dtype=np.float64)))
+
+    def hamiltonian(self, t, X):
+        return np.array([self.lib.ref_icpt_hamiltonian(self.h, C.c_double(t), _d(np.ascontiguousarray(X, dtype=np.float64)))])
+
+    def mass(self, t, X):
+        return self.lib.ref_icpt_mass(self.h, C.c_double(t), _d(np.ascontiguousarray(X, dtype=np.float64)))
+
+    def chart12(self, X1):
+        return self._vec(self.lib.ref_icpt_chart12, 12, _d(np.ascontiguousarray(X1, dtype=np.float64)))
+
+    def chart21(self, X2):
+        return self._vec(self.lib.ref_icpt_chart21, 12, _d(np.ascontiguousarray(X2, dtype=np.float64)))
+
+    def traj(self, t0, X0, tf):
+        return self._vec(self.lib.ref_icpt_traj, 12, C.c_double(t0), _d(np.ascontiguousarray(X0, dtype=np.float64)), C.c_double(tf))
+
+    def final_rows(self, with_h, tf, Xtf, Xf, mode_x):
+        mode = np.ascontiguousarray(mode_x, dtype=np.int32)
+        return self._vec(self.lib.ref_icpt_final, 7 if with_h else 6, int(with_h), C.c_double(tf),
+                         _d(np.ascontiguousarray(Xtf, dtype=np.float64)), _d(np.ascontiguousarray(Xf, dtype=np.float64)),
+                         mode.ctypes.data_as(_ip))
+
+    def init_analytical(self, ti, Xi, tf, Xf):
+        Xi = np.array(Xi, dtype=np.float64)
+        self.lib.ref_icpt_init_analytical(self.h, C.c_double(ti), _d(Xi), C.c_double(tf), _d(np.ascontiguousarray(Xf, dtype=np.float64)))
+        return Xi

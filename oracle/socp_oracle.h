@@ -102,7 +102,7 @@ void orc_integrate_batch(const orc_model *m, int B, const double *t0, const doub
  * (two stages + chart switching, interceptor.cpp:162-218) and leaves m->chart / m->stage behind */
 void orc_compute_traj(orc_model *m, double t0, const double *X0, double tf, int is_jac, double *Xf);
 
-/* ---- interceptor (interceptor_oracle.c; PARITY UNPINNED, see that file's header) ---- */
+/* ---- interceptor (interceptor_oracle.c; pinned to the reference's interceptor.cpp built against oracle/eigen_shim, see that file's header) ---- */
 typedef void (*orc_interceptor_observer)(void *ctx, double t, const double *X, int chart, int stage);
 void orc_interceptor_init(orc_model *m);
 void orc_interceptor_rhs(const orc_model *m, double t, const double *X, double *Xdot);

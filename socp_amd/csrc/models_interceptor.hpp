@@ -238,9 +238,19 @@ struct InterceptorT {
         const double tL = sL * icL;
         // control (:338-385 / :506-552): cos/sin(beta) straight from the atan2 arguments
         const double by = chart1 ? p_a2 : -p_a2, bx = p_a1 * c1;
-        const double b2 = bx * bx + by * by;
+        double nx = bx, ny = by;                            // the pair that is normalised; by itself enters num below
+        double b2 = nx * nx + ny * ny;
+        // costates beyond ~1e+-135 would square to inf (cb = sb = 0: the whole control term lost) or into the subnormals:
+        // the pair rescaled by an exact power of two, towards 1.  Never taken on physical states; other rows keep their bits.
+        // A mixed pair (one entry huge, the other tiny) flushes the tiny one to 0 in the scaling: its sine or cosine, of the
+        // order 1e-330, is below the smallest double anyway.
+        if (!(b2 > 0x1p-900 && b2 < 0x1p900)) {
+            const double k = (fabs(nx) > 1.0 || fabs(ny) > 1.0) ? 0x1p-600 : 0x1p600;
+            nx *= k; ny *= k;
+            b2 = nx * nx + ny * ny;
+        }
         double cb = 1.0, sb = 0.0;                          // atan2(0, 0) = 0
-        if (b2 > 0) { const double ib = ifast::rsqrt(b2); cb = bx * ib; sb = by * ib; }
+        if (b2 > 0) { const double ib = ifast::rsqrt(b2); cb = nx * ib; sb = ny * ib; }
         const double W = v * c_max + ft * alpha_max * im * iv;
         const double num = p_a1 * cb * W + by * sb * ic1 * W;      // chart 2: - p_phi (...) = by (...)
         const double den = p_v * (2 * eta * c_max * v * v + ft * alpha_max * alpha_max * im) - P.p[MUC];

@@ -17,6 +17,12 @@ Error model of Tracked (u = 2^-53, res the exact result, ea / eb the operands' b
     a / b    (ea + |res| eb)/|b| + u|res|              sqrt a   ea / (2 sqrt a) + u|res|
     exp a    |res| ea + C_EXP u|res|                   1/a, 1/sqrt a as the fast flavour forms them: same propagation, C_RCP, C_RSQ
     tanh a   (1 - res^2) ea + C_TANH u|res|            (a kit built with c_exp = C_EXP_LIB charges the library's exp that budget)
+    sin a    |cos a| ea + C_SIN u|res|                 cos a    |sin a| ea + C_COS u|res|
+    tan a    (1 + res^2) ea + C_TAN u|res|             atan2(y, x)   (|x| ey + |y| ex)/(x^2 + y^2) + C_ATAN2 u|res|
+    acos a   the enclosure max |acos(a -+ ea) - acos a| (arguments clamped to [-1, 1]) + C_ACOS u|res|: to first order that is
+             ea / sqrt(1 - a^2), and like it it grows without limit relative to ea as |a| -> 1 (sqrt(2 ea) at |a| = 1), but it stays
+             a bound there, which the first-order term is not
+    copysign(a, b)   |a| with the sign of b's exact value; a's error (the caller records the sign of b as a decision where it matters)
 Within second_order_products() a product also carries ea eb: where BOTH factors vanish to the working precision (vtolUAV's 1 - tanh h
 far from a box) the first-order terms are zero and that term is all that is left.  Goddard and covid19 do not use it.
 Inputs and parameters carry err = 0.  C_EXP = C_RCP = C_RSQ = 2: the budget the comments of models_fast.hpp claim, doubled.  A fused
@@ -48,6 +54,11 @@ C_EXP = C_RCP = C_RSQ = 2
 # full-profile limits the device library is built to, tanh <= 5 ulp and exp <= 3 ulp, with ulp = 2u.  Taken from the specification,
 # not measured.
 C_TANH, C_EXP_LIB = 10, 6
+# the interceptor's library calls, same source (OpenCL full profile: sin, cos, acos <= 4 ulp, tan <= 5 ulp, atan2 <= 6 ulp; ulp = 2u).
+# Taken from the specification, not measured.
+C_SIN = C_COS = C_ACOS = 8
+C_TAN = 10
+C_ATAN2 = 12
 DECIDE_FACTOR = 4
 
 if HAVE_MPMATH:
@@ -161,6 +172,28 @@ class MpfKit(_Kit):
     tanh = staticmethod(lambda x: mpmath.tanh(x))
     rcp = staticmethod(lambda x: 1 / x)
     rsqrt = staticmethod(lambda x: 1 / mpmath.sqrt(x))
+    sin = staticmethod(lambda x: mpmath.sin(x))
+    cos = staticmethod(lambda x: mpmath.cos(x))
+    tan = staticmethod(lambda x: mpmath.tan(x))
+    acos = staticmethod(lambda x: mpmath.acos(_clamp1(x)))
+    copysign = staticmethod(lambda a, b: abs(a) if b >= 0 else -abs(a))
+
+    @staticmethod
+    def atan2(y, x, y_negative_zero=False):
+        return _atan2_mpf(y, x, y_negative_zero)
+
+
+def _clamp1(x):
+    return max(mpf(-1), min(mpf(1), x))
+
+
+def _atan2_mpf(y, x, y_negative_zero):
+    """atan2 with the sign of a zero y, which mpf does not carry: atan2(-0.0, x < 0) = -pi."""
+    if y == 0 and x == 0:
+        return mpf(0)
+    if y == 0 and x < 0:
+        return -mpmath.pi if y_negative_zero else +mpmath.pi
+    return mpmath.atan2(y, x)
 
 
 class TrackedKit(_Kit):
@@ -205,6 +238,39 @@ class TrackedKit(_Kit):
         res = 1 / mpmath.sqrt(a.v)
         return Tracked._rounded(res, a.e * abs(res) / (2 * abs(a.v)) if a.e else mpf(0), c=C_RSQ)
 
+    @staticmethod
+    def sin(a):
+        res = mpmath.sin(a.v)
+        return Tracked(res, abs(mpmath.cos(a.v)) * a.e + C_SIN * U * abs(res))
+
+    @staticmethod
+    def cos(a):
+        res = mpmath.cos(a.v)
+        return Tracked(res, abs(mpmath.sin(a.v)) * a.e + C_COS * U * abs(res))
+
+    @staticmethod
+    def tan(a):
+        res = mpmath.tan(a.v)
+        return Tracked(res, (1 + res * res) * a.e + C_TAN * U * abs(res))
+
+    @staticmethod
+    def atan2(y, x, y_negative_zero=False):
+        res = _atan2_mpf(y.v, x.v, y_negative_zero)
+        n2 = x.v * x.v + y.v * y.v
+        prop = (abs(x.v) * y.e + abs(y.v) * x.e) / n2 if n2 else mpf(0)
+        return Tracked(res, prop + C_ATAN2 * U * abs(res))
+
+    @staticmethod
+    def acos(a):
+        v = _clamp1(a.v)
+        res = mpmath.acos(v)
+        prop = max(mpmath.acos(_clamp1(v - a.e)) - res, res - mpmath.acos(_clamp1(v + a.e))) if a.e else mpf(0)
+        return Tracked(res, prop + C_ACOS * U * abs(res))
+
+    @staticmethod
+    def copysign(a, b):
+        return Tracked(abs(a.v) if b.v >= 0 else -abs(a.v), a.e)
+
     def decidable(self):
         return all(m.e == 0 or abs(m.v) > DECIDE_FACTOR * m.e for m in self.margins.values())
 
@@ -235,6 +301,15 @@ class F64Kit(_Kit):
         return a - b
 
     sqrt = staticmethod(np.sqrt)
+    sin = staticmethod(np.sin)
+    cos = staticmethod(np.cos)
+    tan = staticmethod(np.tan)
+    acos = staticmethod(np.arccos)
+    copysign = staticmethod(np.copysign)
+
+    @staticmethod
+    def atan2(y, x, y_negative_zero=False):
+        return np.arctan2(y, x)                       # a float64 carries the sign of its zero itself
 
 
 # ---- Goddard ----------------------------------------------------------------------------------------------------------------

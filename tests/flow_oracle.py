@@ -386,7 +386,7 @@ def covid_flow(solver="scipy", xtol=1e-8, stages=3, step_nbr=1000):
 
 
 def interceptor_flow(solver="scipy", xtol=1e-8, scenario=1):
-    """tests/testInterceptor.cpp on the oracle (PARITY UNPINNED, oracle/interceptor_oracle.c): analytical guess
+    """tests/testInterceptor.cpp on the oracle (oracle/interceptor_oracle.c, pinned by tests/test_interceptor_pin_cpu.py): analytical guess
     at mu_gft = 0 -> Newton solve -> continuation of mu_gft to 1 (step 0.1) -> continuation of the boundary data
     to the scenario (step 0.1).  M = 1, final time and final velocity free: n = 13."""
     from oracle.oracle import MODEL_INTERCEPTOR

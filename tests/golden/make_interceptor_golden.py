@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Frozen outputs of the interceptor restatement (oracle/interceptor_oracle.c).
 
-PARITY UNPINNED: the reference's interceptor.cpp cannot be compiled in this image (it includes Eigen/Dense) and
-the reference ships no output of it, so these vectors come from the CPU restatement, not from the reference.
+These vectors come from the CPU restatement in its default build, not from the reference; the restatement itself is pinned bit
+for bit to the reference's interceptor.cpp, compiled against oracle/eigen_shim, by tests/test_interceptor_pin_cpu.py
+(tests/golden/make_interceptor_pin_golden.py writes that fixture).
 They freeze the restatement (a later edit that changes its results fails tests/test_oracle_interceptor.py) and
 give the GPU flow test its expected solutions.  What ties them to the reference: the restated test program
 (tests/flow_oracle.py: interceptor_flow = tests/testInterceptor.cpp) converges with info = 1 in all three

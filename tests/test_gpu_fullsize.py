@@ -200,7 +200,8 @@ def test_config5_sweep_at_256_starts(variant):
     """BASELINE config 5 as a solve sweep at the size DESIGN quotes: interceptor, adaptive Dormand-Prince, M = 21, n = 253,
     256 starts around the converged scenario-1 trajectory: all converge, to one root (spread < 1e-8).  256 x 253^2 doubles per
     Jacobian refresh go through the engine's threaded host side and its chunked read-back.  Parity of this configuration is
-    unpinned (no Boost, no Eigen; tests/test_gpu_interceptor.py has the comparison with the restatement)."""
+    unpinned because of its adaptive integrator alone (no Boost, and the reference's interceptor is RK4-only); the model is pinned
+    (tests/test_interceptor_pin_cpu.py, tests/test_gpu_interceptor_pin.py)."""
     from socp_amd import capi, sweep
     ctx = capi.Context(capi.MODEL_INTERCEPTOR)
     ctx.set_variant(capi.VARIANT_LANE_FAST if variant == "fast" else capi.VARIANT_LANE_EXACT)

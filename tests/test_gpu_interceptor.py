@@ -1,5 +1,6 @@
 """GPU: interceptor device model (models_interceptor.hpp) against the CPU restatement
-(oracle/interceptor_oracle.c -- PARITY UNPINNED, see its header: the reference TU needs Eigen).
+(oracle/interceptor_oracle.c -- pinned to the reference's own interceptor.cpp, see its header; tests/test_gpu_interceptor_pin.py
+holds both flavours to a 240-bit evaluation within derived bounds).
 
 The model calls sin/cos/tan/atan2/acos/exp, which differ between the device library and libm in the last
 place, so nothing here is bit-exact.  Tolerances: 1e-12 relative on single evaluations, 1e-10 on

@@ -1,6 +1,7 @@
-"""CPU: the interceptor restatement (oracle/interceptor_oracle.c).  PARITY UNPINNED -- the reference's
-interceptor.cpp needs Eigen, which the image lacks, and the reference ships no output of it.  These tests are
-what stands in for a pin: internal consistency that a transcription slip would break (the costate equations
+"""CPU: the interceptor restatement (oracle/interceptor_oracle.c).  It is pinned bit for bit to the reference's own
+interceptor.cpp, compiled against oracle/eigen_shim, by tests/test_interceptor_pin_cpu.py (up to Eigen's summation order
+through a chart change; the adaptive interceptor remains an extension with no upstream counterpart).  These tests are
+independent of that pin: internal consistency that a transcription slip would break (the costate equations
 are -dH/dx of the separately restated Hamiltonian in BOTH charts; a chart change is invertible and leaves H
 unchanged), the stage/chart logic of ComputeTraj, the overridden final rows, the restated test program
 converging from the reference's own analytical guess, and the frozen vectors under tests/golden/."""
