@@ -344,6 +344,49 @@ int socp_events_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
                              const double *xnode, int E, const int *chan, const double *levels, int refine, int cap, double *tev,
                              int *id, int *count, double *Xev);
 
+/* Per-segment extrema along a whole batch of unknown vectors: how constant the Hamiltonian is, how large states and controls get,
+ * how close the switching function comes to a switch -- without the rows of a trace ever being stored.  [ext] The reference
+ * plots its trace files.
+ * Z[B][n] -> vmin, vmax, tmin, tmax [B][M][C], count[B][M], nbad[B][M];  tmin, tmax and nbad may be NULL.
+ * CHANNELS, in this order (C = socp_extrema_width = 2d + NU + 1 + EC):  X[0 .. 2d), u[0 .. NU), H, g[0 .. EC) -- g the model's event
+ * channels, the channels of socp_events_batch, EC = socp_ctx_event_channels (0 when the model has none).
+ * WHAT.  The state channels are always reduced; SOCP_EXTREMA_CONTROL, SOCP_EXTREMA_HAMILTONIAN and SOCP_EXTREMA_EVENTS select u, H
+ * and g.  Columns of a group that is not selected keep what the buffer held; the events bit on a model with EC = 0 selects nothing.
+ * ROWS.  Segment i of row b is integrated exactly as socp_trace_batch integrates it (same timeline, switching times, start state
+ * z[s i .. s i + s), integrator -- the fixed-step RK4 loop or the adaptive Dormand-Prince one --, per-problem blocks of
+ * socp_problem_set_blocks_dev: row b reads block b), and the rows k = 0 .. R-1 reduced are exactly the rows socp_trace_batch keeps
+ * with stride = 1: t, X and the aux pair of row k.  count[b][i] = R.  A model with its own ComputeTraj (the interceptor) reports its
+ * traced rows and the extra final row, each in the RAW coordinates of the chart the row is in: an extremum of such a state channel
+ * mixes charts, as the trace's column does.  A zero-length or backward segment has R = 1.
+ * VALUES.  u and H of a row are what socp_eval_batch(SOCP_EVAL_CONTROL / SOCP_EVAL_HAMILTONIAN) returns at the row's (t, X) with the
+ * row's aux pair as sw; g_c = event_fn(P, aux0, aux1, t, X, c), the channel value socp_events_batch watches.
+ * REDUCTION, per selected channel, sequential in row order, v the channel's value and t the time of the row:
+ *   row 0:            vmin = vmax = v;  tmin = tmax = t
+ *   every later row:  if (v < vmin) { vmin = v; tmin = t; }   if (v > vmax) { vmax = v; tmax = t; }
+ * The comparisons are strict, so: the FIRST attainment of an extremum wins; -0.0 never displaces +0.0 (nor +0.0 -0.0); a NaN never
+ * displaces anything, and a NaN in row 0 stays (no later row compares below or above it).
+ * nbad[b][i] = the number of rows in which at least one selected channel is not finite (the state is always selected).
+ * The result is over the ROWS, like the trace: an extremum inside a step is not interpolated.
+ * SOCP_ERR_ARG: no problem set, B < 0, what outside 0 .. 7, B > 0 with Z, vmin, vmax or count NULL, _blocks with params and
+ * param_stride != nparams + 2; B == 0: SOCP_OK without a launch; SOCP_ERR_UNSUPPORTED: the model's launch table has no extrema
+ * entry (socp_ctx_has_extrema says 0).  An error writes nothing and leaves the context unchanged.
+ * One launch, which writes nothing but these arrays; socp_ctx_counters advances by B M trajectories and one launch.  The _dev form
+ * takes device pointers, enqueues on the context's stream and neither copies nor synchronises; the host forms stage through that
+ * stream (vmin, vmax, tmin and tmax travel both ways) and return when the results are in the caller's arrays.  _blocks: per-row
+ * blocks like socp_trace_batch_blocks (any of params / time / xnode may be NULL); the context's own blocks are restored afterwards. */
+#define SOCP_EXTREMA_CONTROL      1
+#define SOCP_EXTREMA_HAMILTONIAN  2
+#define SOCP_EXTREMA_EVENTS       4
+int socp_extrema_width(const socp_ctx *ctx);                 /* C = 2d + NU + 1 + EC  (< 0: error) */
+int socp_ctx_has_extrema(const socp_ctx *ctx);               /* 1 / 0 */
+int socp_extrema_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int what,
+                           double *d_vmin, double *d_vmax, double *d_tmin, double *d_tmax, int *d_count, int *d_nbad);
+int socp_extrema_batch(socp_ctx *ctx, int B, const double *Z, int what,
+                       double *vmin, double *vmax, double *tmin, double *tmax, int *count, int *nbad);
+int socp_extrema_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
+                              const double *time, const double *xnode, int what,
+                              double *vmin, double *vmax, double *tmin, double *tmax, int *count, int *nbad);
+
 /* Conjugate-time test of a whole batch of unknown vectors: the Jacobi fields along every extremal.  [ext] The reference never
  * computes this; indirect shooting finds extremals, not minima, and the standard instrument for telling them apart (cotcot, HamPath)
  * is J(t) = dx(t)/dp(t0), a d x d matrix with J(t0) = 0: the first time det J(t) changes sign is the first conjugate time, and a

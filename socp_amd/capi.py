@@ -154,6 +154,11 @@ def lib():
         L.socp_cost_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
         L.socp_cost_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]
         L.socp_ctx_event_channels.argtypes = [_vp]
+        L.socp_extrema_width.argtypes = [_vp]
+        L.socp_ctx_has_extrema.argtypes = [_vp]
+        L.socp_extrema_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.socp_extrema_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip]
+        L.socp_extrema_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip]
         L.socp_events_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_events_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _ip, _ip, _dp]
         L.socp_events_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -288,6 +293,16 @@ def trace_kept_rows(R, stride):
     if kept[-1] != R - 1:
         kept.append(R - 1)
     return kept
+
+
+EXTREMA_CONTROL, EXTREMA_HAMILTONIAN, EXTREMA_EVENTS = 1, 2, 4
+
+
+def extrema_channel_names(dim, control_dim, event_channels=0):
+    """Names of the C = 2 dim + control_dim + 1 + event_channels channels of extrema_batch, in their order: x0.., p0.. (the state
+    and the costate), u0.., H, g0.. (the model's event channels)."""
+    return (["x%d" % k for k in range(dim)] + ["p%d" % k for k in range(dim)] + ["u%d" % k for k in range(control_dim)] + ["H"]
+            + ["g%d" % k for k in range(event_channels)])
 
 
 def merge_events(t, id, count):
@@ -656,6 +671,43 @@ class Context:
         xe = np.empty((B, self.M, self.s)) if xend else None
         self._chk(self.L.socp_cost_batch_blocks(self.h, B, _d(Z), *blocks, _d(cost), _d(tot), _d(xe)))
         return dict(cost=cost, total=tot, xend=xe)
+
+    # -- batched extrema
+    def has_extrema(self):
+        """Whether this model's launch table has an extrema entry (socp_ctx_has_extrema): every model with a trace entry."""
+        return self.L.socp_ctx_has_extrema(self.h) == 1
+
+    def extrema_width(self):
+        """Channels of extrema_batch: X[2d], u[NU], H, g[event channels] (socp_extrema_width)."""
+        return self.L.socp_extrema_width(self.h)
+
+    def extrema_channels(self):
+        """The channels' names, in their order (extrema_channel_names)."""
+        return extrema_channel_names(self.dim, self.nu, self.event_channels())
+
+    def extrema_batch_dev(self, B, d_Z, what, d_vmin, d_vmax, d_tmin, d_tmax, d_count, d_nbad=None):
+        """Device pointers (ints; d_tmin / d_tmax / d_nbad may be None); enqueue only, no copy, no synchronise
+        (socp_extrema_batch_dev)."""
+        self._chk(self.L.socp_extrema_batch_dev(self.h, int(B), _vp(d_Z), int(what), _vp(d_vmin), _vp(d_vmax), _vp(d_tmin), _vp(d_tmax),
+                                                _vp(d_count), _vp(d_nbad)))
+
+    def extrema_batch(self, Z, what=7, blocks=None):
+        """Per-segment extrema over the rows trace_batch keeps with stride = 1, in one launch that stores no row (include/socp_hip.h):
+        returns dict(vmin, vmax, tmin, tmax [B][M][C], count[B][M], nbad[B][M], channels) -- the smallest and the largest value of
+        every channel (extrema_channels), the time of the row that first attains it, the number of rows and the number of rows with
+        a value that is not finite.  what: EXTREMA_CONTROL | EXTREMA_HAMILTONIAN | EXTREMA_EVENTS select u, H and the event channels
+        beside the state; the columns of a group that is not selected hold NaN.  blocks = (params, time, xnode): per-row blocks as in
+        residual_batch_blocks, host arrays or None."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B, Cw = Z.shape[0], self.extrema_width()
+        out = {k: np.full((B, self.M, Cw), np.nan) for k in ("vmin", "vmax", "tmin", "tmax")}
+        count = np.zeros((B, self.M), dtype=np.int32)
+        nbad = np.zeros((B, self.M), dtype=np.int32)
+        self._chk(self.L.socp_extrema_batch_blocks(self.h, B, _d(Z), *_block_args(B, *(blocks if blocks is not None else (None, None, None))),
+                                                   int(what), _d(out["vmin"]), _d(out["vmax"]), _d(out["tmin"]), _d(out["tmax"]),
+                                                   count.ctypes.data_as(_ip), nbad.ctypes.data_as(_ip)))
+        out.update(count=count, nbad=nbad, channels=self.extrema_channels())
+        return out
 
     # -- batched events
     def event_channels(self):

@@ -972,6 +972,78 @@ int socp_cost_batch_blocks(socp_ctx *c, int B, const double *Z, const double *pa
     return with_blocks(c, B, params, pstride, time, xnode, [&] { return socp_cost_batch(c, B, Z, cost, total, Xend); });
 }
 
+/* ---- batched extrema ----------------------------------------------------------------------- */
+
+int socp_ctx_has_extrema(const socp_ctx *c) { return c ? (table_of(c)->extrema ? 1 : 0) : SOCP_ERR_ARG; }
+
+int socp_extrema_width(const socp_ctx *c) { return c ? c->S + c->nu + 1 + socp_ctx_event_channels(c) : SOCP_ERR_ARG; }
+
+namespace {
+int extrema_args(socp_ctx *c, const char *who, int B, int what, const void *Z, const void *vmin, const void *vmax, const void *count)
+{
+    if (const int rc = args_head(c, who, B >= 0 && what >= 0 && what <= 7, "B >= 0 and 0 <= what <= 7 are required")) return rc;
+    if (B > 0 && (!Z || !vmin || !vmax || !count)) return fail(c, SOCP_ERR_ARG, std::string(who) + ": null argument");
+    return args_tail(c, who, table_of(c)->extrema != nullptr, "extrema entry", nullptr);
+}
+}  // namespace
+
+int socp_extrema_batch_dev(socp_ctx *c, int B, const double *d_Z, int what, double *d_vmin, double *d_vmax, double *d_tmin,
+                           double *d_tmax, int *d_count, int *d_nbad)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc = extrema_args(c, "extrema_batch", B, what, d_Z, d_vmin, d_vmax, d_count);
+    if (rc != SOCP_OK) return rc;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_traj += (long long)B * c->M; c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->extrema(c->stream, c->P, c->pb, B, d_Z, what, d_vmin, d_vmax, d_tmin, d_tmax, d_count, d_nbad));
+    return SOCP_OK;
+}
+
+int socp_extrema_batch(socp_ctx *c, int B, const double *Z, int what, double *vmin, double *vmax, double *tmin, double *tmax,
+                       int *count, int *nbad)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = extrema_args(c, "extrema_batch", B, what, Z, vmin, vmax, count);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t segs = (size_t)B * c->M, nV = segs * socp_extrema_width(c);
+    double *d_Z;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, (size_t)B * c->n, d_Z));
+    // the caller's arrays travel both ways: the columns of a group `what` does not select come back as they went
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * 4 * nV));
+    HIP_TRY(c, c->s_var.reserve(sizeof(int) * 2 * segs));
+    double *dLo = c->s_out.as<double>(), *dHi = dLo + nV, *dTa = dHi + nV, *dTb = dTa + nV;
+    int *dC = c->s_var.as<int>(), *dN = dC + segs;
+    HIP_TRY(c, copy_up(c, dLo, vmin, nV));
+    HIP_TRY(c, copy_up(c, dHi, vmax, nV));
+    if (tmin) HIP_TRY(c, copy_up(c, dTa, tmin, nV));
+    if (tmax) HIP_TRY(c, copy_up(c, dTb, tmax, nV));
+    const int rc = socp_extrema_batch_dev(c, B, d_Z, what, dLo, dHi, tmin ? dTa : nullptr, tmax ? dTb : nullptr, dC, nbad ? dN : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, vmin, dLo, nV));
+    HIP_TRY(c, copy_down(c, vmax, dHi, nV));
+    if (tmin) HIP_TRY(c, copy_down(c, tmin, dTa, nV));
+    if (tmax) HIP_TRY(c, copy_down(c, tmax, dTb, nV));
+    HIP_TRY(c, copy_down(c, count, dC, segs));
+    if (nbad) HIP_TRY(c, copy_down(c, nbad, dN, segs));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_extrema_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                              const double *xnode, int what, double *vmin, double *vmax, double *tmin, double *tmax, int *count,
+                              int *nbad)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = extrema_args(c, "extrema_batch_blocks", B, what, Z, vmin, vmax, count)) return rc;
+    if (const int rc = blocks_stride(c, "extrema_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_extrema_batch(c, B, Z, what, vmin, vmax, tmin, tmax, count, nbad); });
+}
+
 /* ---- batched Move(tf) / re-grid ------------------------------------------------------------- */
 
 namespace {

@@ -905,6 +905,163 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) vo
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// K_extrema: per-segment extrema over the rows K_trace keeps with stride = 1 (socp_extrema_batch), without the rows ever
+// leaving the lane.  Z[B][n] -> vmin, vmax, tmin, tmax [B][M][C], count[B][M], nbad[B][M];  C = S + NU + 1 + EC:  X[S], u[NU],
+// H, g[EC] (EC = the model's event channels when its table has an events entry, else 0).  One lane = (row, segment),
+// T = b M + i, the lane mapping of K_trace and K_cost.  Segment i starts from the shared prologue (Timeline / segment_start)
+// and runs through the SAME loops with the SAME step hooks as segment_trace, so the rows reduced are the rows traced.  On
+// every row the hook evaluates control_only / hamiltonian / event_fn at the row's (t, X) with the row's aux pair -- what
+// K_trace_fill evaluates -- and updates the running (value, time) pairs, which live in registers beside the state:
+//     row 0:  vmin = vmax = v, tmin = tmax = t;   later:  if (v < vmin) { vmin = v; tmin = t; }  if (v > vmax) { vmax = v; tmax = t; }
+// (strict comparisons: the first attainment wins, -0.0 never displaces +0.0, a NaN never displaces anything and a NaN in row 0
+// stays).  nbad = rows in which a selected channel is not finite.
+// FULL = false: the state channels only -- the lane carries neither u, H, g nor their 4 (NU + 1 + EC) running doubles.
+// FULL = true: every channel is reduced; the bits of `what` (1: u, 2: H, 4: g) select which groups count for nbad and are stored.
+// The C-wide results leave once, at the end; a lane's C doubles are consecutive and consecutive lanes own adjacent spans.
+// Every store site is ONE block under ONE computed predicate (see the note in segment_residual).
+// ---------------------------------------------------------------------------------------------
+template <class Mdl>
+constexpr int extrema_event_channels() { return has_custom_traj<Mdl>::value ? 0 : event_channels<Mdl>::value; }
+template <class Mdl>
+constexpr int extrema_width() { return Mdl::S + Mdl::NU + 1 + extrema_event_channels<Mdl>(); }
+
+template <class Mdl, int INTEG, bool FULL, class ZRead>
+__device__ __forceinline__ void segment_extrema(const ModelParams &P, const ProblemDev &pb, const ZRead &z, int i, int what,
+                                                double *__restrict__ vmin, double *__restrict__ vmax, double *__restrict__ tmin,
+                                                double *__restrict__ tmax, int *__restrict__ count, int *__restrict__ nbad)
+{
+    constexpr int S = Mdl::S, NU = Mdl::NU, EC = extrema_event_channels<Mdl>();
+    constexpr int L = FULL ? extrema_width<Mdl>() : S;          // channels this instantiation carries
+    const Timeline<ZRead> tl{pb, z};
+    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
+    double sw0 = tl.template switching_time<Mdl>(P.sw0, pb.sw_node0), sw1 = tl.template switching_time<Mdl>(P.sw1, pb.sw_node1);
+    double X[S];
+    segment_start(z, S * i, X);
+
+    const bool wu = (what & 1) != 0, wh = (what & 2) != 0, wg = (what & 4) != 0;
+    double lo[L], hi[L], tlo[L], thi[L];
+#pragma unroll
+    for (int c = 0; c < L; c++) lo[c] = hi[c] = tlo[c] = thi[c] = 0.0;     // row 0 overwrites them
+    int rows = 0, bad = 0;
+    auto finite = [](double v) { return fabs(v) <= 1.7976931348623157e308; };      // false for NaN and the infinities
+    auto row = [&](double t, const double (&Xr)[S], double b0, double b1) {
+        double v[L];
+#pragma unroll
+        for (int k = 0; k < S; k++) v[k] = Xr[k];
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < S; k++) ok = ok && finite(v[k]);
+        if constexpr (FULL) {
+            double u[3];
+            Mdl::control_only(P, b0, b1, t, Xr, u);
+#pragma unroll
+            for (int k = 0; k < NU; k++) { v[S + k] = u[k]; ok = ok && (!wu || finite(u[k])); }
+            v[S + NU] = Mdl::hamiltonian(P, b0, b1, t, Xr);
+            ok = ok && (!wh || finite(v[S + NU]));
+            if constexpr (EC > 0) {
+#pragma unroll
+                for (int c = 0; c < EC; c++) {
+                    v[S + NU + 1 + c] = Mdl::event_fn(P, b0, b1, t, Xr, c);
+                    ok = ok && (!wg || finite(v[S + NU + 1 + c]));
+                }
+            }
+        }
+        const bool first = rows == 0;
+#pragma unroll
+        for (int c = 0; c < L; c++) {
+            const bool dn = first || v[c] < lo[c], up = first || v[c] > hi[c];
+            lo[c] = dn ? v[c] : lo[c];
+            tlo[c] = dn ? t : tlo[c];
+            hi[c] = up ? v[c] : hi[c];
+            thi[c] = up ? t : thi[c];
+        }
+        bad += ok ? 0 : 1;
+        rows++;
+    };
+
+    if constexpr (has_custom_traj<Mdl>::value) {
+        Mdl::template compute_traj<INTEG>(P, sw0, sw1, t1, t2, X, row);
+        row(t2, X, sw0, sw1);            // the extra row of traj_dense_kernel: the state as ComputeTraj returns it and the flags it leaves
+    } else {
+        row(t1, X, sw0, sw1);                                            // row 0 = (t1, X_start)
+        auto after = [&](double t, const double (&Xr)[S]) { row(t, Xr, sw0, sw1); };
+        if constexpr (INTEG == 1) Lane<Mdl>::integrate_dopri5(P, sw0, sw1, t1, t2, X, NoStepHook(), after);
+        else Lane<Mdl>::integrate(P, sw0, sw1, t1, t2, X, after);
+    }
+
+    // channels [c0, c1) of the four arrays, each under its own predicate
+    // (compile-time bounds: the running pairs are registers, never indexed by a variable)
+    auto store = [&](bool sel, auto c0, auto c1) {
+        if (sel) {
+#pragma unroll
+            for (int c = c0(); c < c1(); c++) { vmin[c] = lo[c]; vmax[c] = hi[c]; }
+        }
+        const bool sa = sel && tmin != nullptr;
+        if (sa) {
+#pragma unroll
+            for (int c = c0(); c < c1(); c++) tmin[c] = tlo[c];
+        }
+        const bool sb = sel && tmax != nullptr;
+        if (sb) {
+#pragma unroll
+            for (int c = c0(); c < c1(); c++) tmax[c] = thi[c];
+        }
+    };
+    using std::integral_constant;
+    store(true, integral_constant<int, 0>(), integral_constant<int, S>());
+    if constexpr (FULL) {
+        store(wu, integral_constant<int, S>(), integral_constant<int, S + NU>());
+        store(wh, integral_constant<int, S + NU>(), integral_constant<int, S + NU + 1>());
+        if constexpr (EC > 0) store(wg, integral_constant<int, S + NU + 1>(), integral_constant<int, S + NU + 1 + EC>());
+    }
+    *count = rows;
+    const bool sn = nbad != nullptr;
+    if (sn) *nbad = bad;
+}
+
+template <class Mdl, int INTEG, bool PERPROB, bool FULL>
+__device__ __forceinline__ void extrema_lane(const ModelParams &P, const ProblemDev &pb, int B, const double *__restrict__ Z, int what,
+                                             double *__restrict__ vmin, double *__restrict__ vmax, double *__restrict__ tmin,
+                                             double *__restrict__ tmax, int *__restrict__ count, int *__restrict__ nbad)
+{
+    constexpr int C = extrema_width<Mdl>();
+    const long T = (long)blockIdx.x * 64 + threadIdx.x;              // = b * M + i: index into count / nbad, span of the four arrays
+    if (T >= (long)B * pb.M) return;
+    const long b = T / pb.M;
+    const int i = (int)(T - b * pb.M);
+    const double *zr = Z + b * pb.n;
+    auto z = [=](int k) -> double { return zr[k]; };
+    double *ta = tmin ? tmin + T * C : nullptr, *tb = tmax ? tmax + T * C : nullptr;
+    int *nb = nbad ? nbad + T : nullptr;
+    if constexpr (PERPROB) {
+        ModelParams Pq = P;
+        ProblemDev pq = pb;
+        load_problem_block(pb, b, Pq, pq);
+        segment_extrema<Mdl, INTEG, FULL>(Pq, pq, z, i, what, vmin + T * C, vmax + T * C, ta, tb, count + T, nb);
+    } else {
+        segment_extrema<Mdl, INTEG, FULL>(P, pb, z, i, what, vmin + T * C, vmax + T * C, ta, tb, count + T, nb);
+    }
+}
+
+// every channel (what != 0) and the state channels only (what == 0): two kernels of one launch-macro shape
+template <class Mdl, int WPE, int INTEG = 0, bool PERPROB = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) void extrema_lane_kernel(ModelParams P, ProblemDev pb, int B,
+                                                             const double *__restrict__ Z, int what, double *__restrict__ vmin,
+                                                             double *__restrict__ vmax, double *__restrict__ tmin,
+                                                             double *__restrict__ tmax, int *__restrict__ count, int *__restrict__ nbad)
+{
+    extrema_lane<Mdl, INTEG, PERPROB, true>(P, pb, B, Z, what, vmin, vmax, tmin, tmax, count, nbad);
+}
+template <class Mdl, int WPE, int INTEG = 0, bool PERPROB = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) void extrema_state_lane_kernel(ModelParams P, ProblemDev pb, int B,
+                                                             const double *__restrict__ Z, double *__restrict__ vmin,
+                                                             double *__restrict__ vmax, double *__restrict__ tmin,
+                                                             double *__restrict__ tmax, int *__restrict__ count, int *__restrict__ nbad)
+{
+    extrema_lane<Mdl, INTEG, PERPROB, false>(P, pb, B, Z, 0, vmin, vmax, tmin, tmax, count, nbad);
+}
+
 // K_trace_fill: u and H of every stored row, in place; one lane = (row b, segment i, kept row k), the rows at or beyond
 // min(count, cap) untouched.  Evaluated like eval_lane_kernel evaluates them: at the row's (t, X) with the row's aux pair.
 template <class Mdl, bool PERPROB>

@@ -39,10 +39,11 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 11;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 12;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
+                                   // kPluginAbi = 12: batched extrema launcher
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -81,6 +82,11 @@ struct ModelLaunchers {
     // kernels_fields.hip, one object without contraction that both flavours' tables point to
     hipError_t (*fields)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, int, int, int, double *, double *,
                          int *, int *, double *, double *);
+    // batched extrema (socp_extrema_batch): Z[B][n], what (bit 0: u, 1: H, 2: the event channels; the state always) -> vmin, vmax,
+    // tmin, tmax [B][M][C] (tmin, tmax may be null), count[B][M], nbad[B][M] (may be null), C = 2d + NU + 1 + event_channels; both
+    // integrators, one launch.  Every model with a trace entry has it
+    hipError_t (*extrema)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, double *, double *, double *,
+                          double *, int *, int *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)

@@ -49,7 +49,7 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, batched extrema, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
 #include "fields.hpp"
@@ -164,6 +164,19 @@ hipError_t trace_fill(hipStream_t st, const ModelParams &P, const ProblemDev &pb
     return pb.pp_params ? trace_fill_pp<Mdl, true>(st, P, pb, B, cap, rows, count) : trace_fill_pp<Mdl, false>(st, P, pb, B, cap, rows, count);
 }
 
+// batched extrema: one lane per (row, segment) like the trace, both integrators; what == 0 launches the state-only kernel, which
+// carries neither u, H, the event channels nor their running pairs
+template <class Mdl>
+hipError_t extrema(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int what, double *vmin, double *vmax,
+                   double *tmin, double *tmax, int *count, int *nbad)
+{
+    if (B <= 0) return hipSuccess;
+    if (what < 0 || what > 7) return hipErrorInvalidValue;
+    if (what == 0) SOCP_PLUGIN_LAUNCH_PB(extrema_state_lane_kernel, blocks_for((long)B * pb.M), st, P, pb, B, Z, vmin, vmax, tmin, tmax, count, nbad);
+    else SOCP_PLUGIN_LAUNCH_PB(extrema_lane_kernel, blocks_for((long)B * pb.M), st, P, pb, B, Z, what, vmin, vmax, tmin, tmax, count, nbad);
+    return hipGetLastError();
+}
+
 // batched cost: fixed-step integrator only, so no adaptive instantiation (the C-ABI layer refuses the adaptive integrator)
 template <class Mdl>
 hipError_t cost(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *out, double *Xend)
@@ -270,7 +283,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     for (double v : defaults) if (i < kMaxParams) t.default_params[i++] = v;
     t.traj = &traj<Mdl>; t.residual = &residual<Mdl>; t.fdjac = &fdjac<Mdl>; t.fdrows = &fdrows<Mdl>;
     t.dense = &dense<Mdl>; t.eval = &eval<Mdl>; t.trace = &trace<Mdl>; t.trace_fill = &trace_fill<Mdl>;
-    t.move = &move<Mdl>;
+    t.move = &move<Mdl>; t.extrema = &extrema<Mdl>;
     if constexpr (!has_custom_traj<Mdl>::value) t.cost = &cost<Mdl>;     // a model with its own ComputeTraj has no cost kernel
     if constexpr (event_channels<Mdl>::value > 0 && !has_custom_traj<Mdl>::value) {
         static_assert(event_channels<Mdl>::value <= 16, "a watch's channel travels in four bits");

@@ -384,6 +384,28 @@ def fields_local(ctx, args, local, lo, rank, params=None):
             "phi": bool(args.fields_phi), "wall_s": wall, "file": path}
 
 
+def extrema_local(ctx, args, local, lo, rank, params=None):
+    """--extrema-out: the per-segment extrema (socp_extrema_batch) of this rank's CONVERGED chains, each with its own parameter block
+    when the chains have one: over every row of every segment (the rows of a trace with stride 1, none of them stored) the smallest
+    and the largest value of each state, and by --extrema-what of the controls, the Hamiltonian and the switching function, with the
+    times of their first attainment.  Written to PATH.rank<r>.npz: index [k] = position of the chain in the sweep's start table,
+    vmin / vmax / tmin / tmax [k][M][C], count [k][M], nbad [k][M].  Runs after the timed solve.  Returns the record entry of this
+    rank: the spread of the Hamiltonian along a row, max_i(Hmax) - min_i(Hmin) -- the integration-quality figure of an autonomous
+    problem (NaN figures when H is not selected) -- and the number of rows with a value that is not finite."""
+    from . import capi
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.extrema_out)
+    t0 = time.perf_counter()
+    r = ctx.extrema_batch(z, what=args.extrema_what, blocks=None if own is None else (own, None, None))
+    wall = time.perf_counter() - t0
+    np.savez(path, index=index, vmin=r["vmin"], vmax=r["vmax"], tmin=r["tmin"], tmax=r["tmax"], count=r["count"], nbad=r["nbad"])
+    h = r["channels"].index("H")
+    some = len(conv) > 0 and bool(args.extrema_what & capi.EXTREMA_HAMILTONIAN)
+    spread = r["vmax"][:, :, h].max(axis=1) - r["vmin"][:, :, h].min(axis=1) if some else np.zeros(0)
+    return {"rows": int(len(conv)), "h_spread_max": float(spread.max()) if some else None,
+            "h_spread_median": float(np.median(spread)) if some else None, "nbad_rows": int(np.sum(r["nbad"].sum(axis=1) > 0)),
+            "what": args.extrema_what, "wall_s": wall, "file": path}
+
+
 def tangent_local(ctx, args, local, lo, rank, params=None):
     """--tangent-out: the sensitivity dz/dtheta (socp_tangent_batch) of this rank's CONVERGED chains to the packed parameter
     --tangent-param, each chain with its own parameter block when the chains have one, written to PATH.rank<r>.npz: index [k] =
@@ -642,6 +664,15 @@ def main():
                          "batch (socp_fields_batch): dx(t)/dp(t0) carried through the RK4 steps on dual numbers, no forward "
                          "difference; writes PATH.rank<r>.npz (index, tq, det, count, nchange, tconj; phi with --fields-phi) and adds "
                          "fields {rows, with_change, tconj_min, tconj_median} to the record.  Not for the interceptor")
+    ap.add_argument("--extrema-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank reduces the trajectories of the converged chains of its own block in one launch "
+                         "that stores no row (socp_extrema_batch): the smallest and the largest value of every state and, by "
+                         "--extrema-what, control, the Hamiltonian and the switching function over all rows of every segment, with the "
+                         "chains' own parameter blocks; writes PATH.rank<r>.npz (index, vmin, vmax, tmin, tmax, count, nbad) and adds "
+                         "extrema {rows, h_spread_max, h_spread_median, nbad_rows} to the record.  Not with --model interceptor.  "
+                         "Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--extrema-what", type=int, default=7, metavar="N",
+                    help="with --extrema-out: 0 .. 7, the sum of 1 (controls), 2 (Hamiltonian), 4 (event channels); the states always")
     ap.add_argument("--fields-stride", type=int, default=100, metavar="K", help="with --fields-out: sample every K-th step (and the last)")
     ap.add_argument("--fields-skip", type=int, default=0, metavar="S", help="with --fields-out: compare the samples from the S-th on")
     ap.add_argument("--fields-phi", action="store_true",
@@ -683,6 +714,10 @@ def main():
         ap.error("--jacobi-out: the interceptor has no Jacobi-field kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
     if args.fields_out and args.model == "interceptor":
         ap.error("--fields-out: the interceptor has no exact-fields kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
+    if args.extrema_out and args.model == "interceptor":
+        ap.error("--extrema-out is implemented for the Goddard sweeps")
+    if not 0 <= args.extrema_what <= 7:
+        ap.error("--extrema-what must be 0 .. 7")
     if args.fields_stride < 1 or args.fields_skip < 0:
         ap.error("--fields-stride must be >= 1 and --fields-skip >= 0")
     if args.jacobi_stride < 1 or args.jacobi_skip < 0:
@@ -823,6 +858,8 @@ def main():
         extra["jacobi" if rank == 0 else "jacobi_rank%d" % rank] = jacobi_local(ctx, args, local, lo_w, rank, blocks)
     if args.fields_out:
         extra["fields" if rank == 0 else "fields_rank%d" % rank] = fields_local(ctx, args, local, lo_w, rank, blocks)
+    if args.extrema_out:
+        extra["extrema" if rank == 0 else "extrema_rank%d" % rank] = extrema_local(ctx, args, local, lo_w, rank, blocks)
     if args.sing_out:
         extra["singular" if rank == 0 else "singular_rank%d" % rank] = singular_local(ctx, args, local, lo_w, rank, blocks)
     if args.branch_out:
