@@ -496,6 +496,72 @@ int socp_fields_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
                              const double *xnode, int cols, int stride, int skip, int cap, double *tq, double *det, int *count,
                              int *nchange, double *tconj, double *Phi);
 
+/* The EXACT Jacobian dF/dz of the shooting function itself, for a whole batch of unknown vectors: dual numbers carried through the
+ * residual's own RK4 steps AND through the boundary, continuity, Hamiltonian and switching rows, with a column for every free time.
+ * [ext] The reference differences (hybrd) or integrates variational equations the model must bring (hybrj); Goddard brings none.
+ * Every other consumer of the Jacobian here reads a forward difference, which on the nominal Goddard extremal is wrong in the fourth
+ * digit (table above).  Z[B][n] -> Fjac[B][n*n], COLUMN-major with leading dimension n -- the layout of socp_fd_jacobian_multi_dev, so
+ * the result goes unchanged into socp_linsolve_batch_dev and socp_svd_batch_dev -- and, unless NULL, F[B][n], the residual.
+ * SETUP, timeline, switching times and per-row blocks are those of socp_residual_batch; the rows and the unknowns are its rows and
+ * unknowns (state unknowns z[S i + c] of node i < M, S = 2d, then the free times in node order).  DUAL NUMBERS as in socp_fields_batch.
+ * COLUMNS AND LANES.  Segment i of row b carries S + 1 columns.  Column c < S starts from (X0, e_c), X0 = z[S i ..): the unknown
+ * z[S i + c].  Column S starts from (X0, +0.0) and is the segment's LENGTH L = t2 - t1.  One lane per column, G = S + 1 neighbouring
+ * lanes of one wavefront, 64 / G groups per wave (Goddard 15 lanes, 4 groups; double integrator 13, 4; covid19 9, 7).
+ * STEPS.  ONE text for every lane.  t1 = (t1, +0.0), t2 = (t2, delta), delta = 1.0 in the length column and +0.0 in the state
+ * columns; dt = (t2 - t1) / N (dual - dual, then / the plain N); t = t1; while t.v < (t2.v - dt.v / 2) [and the step guard of the
+ * residual]: step = (t.v + dt.v > t2.v) ? (t2 - t) : dt; one RK4 step; t = t + dt -- all by the dual rules, conditions on value
+ * parts.  The RK4 step is that of odeTools.cpp:89-98 in its association order with a DUAL step:
+ *   h2 = step / 2.0; th = t + step / 2.0; F1 = f(t.v, X); Y = X + h2 F1; F2 = f(th.v, Y); Y = X + h2 F2; F3 = f(th.v, Y);
+ *   Y = X + step F3; Fs = F2 + F3; F4 = f((t + step).v, Y); h6 = step / 6.0; X = X + h6 (F1 + (F4 + 2.0 Fs))
+ * where every product h F is the full dual x dual rule: the term h.d F.v IS computed, also where h.d is zero.  f is the model's
+ * rhs_t and receives the VALUE part of the stage time.  Consequences: the value trajectory of every column is the reference-order
+ * residual's, bit for bit; the derivative parts of the state columns equal Phi of socp_fields_batch (SOCP_FIELDS_ALL) as numbers,
+ * though not in the sign of a zero (there h is plain and its zero term dropped).
+ * WHAT IS NOT DIFFERENTIATED.  An explicit dependence of the right-hand side, the Hamiltonian or the switching row on t: the in-tree
+ * models use t only in comparisons.  The dependence on a switching time through the control law's comparisons (Goddard with
+ * mu2 = 0: t <= sw0, t <= sw1): the discrete flow is piecewise constant in it.  A state-dependent kink differentiates the branch
+ * taken.  So column k of a free time holds the derivative through the LENGTHS of the segments alone.
+ * ROWS.  segment_residual on duals: each lane evaluates the rows its segment owns and stores the derivative part at (row, its
+ * column); value parts go to F.
+ *   segment 0, on the START state: rows j < d: X[j + d] where component j of node 0 is FREE, else X[j] - xd[j]; row ft_row[0] (t0
+ *   FREE): hamiltonian_t(t1, X).  The length column has no part in these rows.
+ *   segment i < M - 1, on the END state X, with Xp = z[S (i + 1) ..) as constants: row ft_row[i + 1] (that time FREE):
+ *   switching_fn_t(t2, X, (Xp, +0.0)); rows S (i + 1) + j and S (i + 1) + d + j: FIXED: X[j] - xd[j] and the value Xp[j] - xd[j]
+ *   (no derivative stored from this side); CONTINUOUS: X[j] - Xp[j] and X[j + d] - Xp[j + d].
+ *   segment M - 1, on the END state: rows d + j: X[j + d] where component j of node M is FREE, else X[j] - xd[j]; row ft_row[M] (tf
+ *   FREE): hamiltonian_t(t2, X).
+ *   The part of node i's rows (1 <= i < M) that depends on segment i's START state belongs to the state lanes of segment i, which
+ *   own those columns: -1.0 at (S i + c, S i + c) where component (c mod d) is CONTINUOUS; 1.0 at (S i + d + c, S i + c), c < d, where
+ *   it is FIXED; and, where the model's free-time row is H(t, X) - H(t, Xp) (trait kSwitchingReadsXp: the double integrator,
+ *   covid19; not Goddard, whose row is H(t, X)), the derivative part of -hamiltonian_t(t1, (X0, e_c)) at (ft_row[i], S i + c).
+ *   Every entry then has exactly one writer.
+ * FREE-TIME COLUMNS.  The segment lies between the junctions A <= i and Bn >= i + 1 (A = i or lo[i], Bn = i + 1 or hi[i + 1]).  For
+ * f in {A, Bn} with node f FREE and unknown index k, the length lane stores w (d row / d L) -- one product -- at (row, k) for every
+ * END-state row above, w = c(i + 1, f) - c(i, f), where c(j, f) is 1.0 for j == f, (double)(j - a) / (double)(b - a) for a node j
+ * interpolated between the junctions a and b = f, 1.0 minus that for a = f, and 0.0 otherwise.  Nothing is stored when w == 0.0.
+ * The matrix is zero-filled first, on the call's stream; then ONE launch stores every entry listed above (zeros included) directly.
+ * A zero-length or backward segment takes no step: its continuity block is the unit matrix, its length column zero.
+ * ONE OBJECT, NO CONTRACTION, as socp_fields_batch: a throughput-flavour context returns the same bits, and F is
+ * socp_residual_batch of a reference-order context, bit for bit.
+ * WHAT IT IS AND IS NOT.  Exact for the DISCRETE flow, to rounding, apart from what is listed as not differentiated; the forward
+ * difference sees those dependences (and noise).  tests/exact_jacobian_reference.py restates the definition; the tests compare whole
+ * buffers to it.  Out of scope: jac = 2 in socp_tangent_batch / socp_singular_batch / socp_branch_batch (they keep 0 .. 1), hybrj
+ * for Goddard inside socp_chains_solve, the adaptive integrator, the interceptor, vtolUAV, derivatives with respect to parameters,
+ * more than one GPU.
+ * socp_ctx_has_exact_jacobian: 1 when the context's model has the entry -- the traits rhs_t, hamiltonian_t and switching_fn_t, no
+ * switching_state hook, no custom final rows, no ComputeTraj of its own -- else 0; SOCP_ERR_ARG for a NULL context (as
+ * socp_ctx_has_fields).
+ * SOCP_ERR_ARG: no problem set, B < 0, a NULL Z or Fjac with B > 0, a wrong parameter stride (_blocks); B == 0: SOCP_OK without a
+ * launch; SOCP_ERR_UNSUPPORTED (the message says which): the context's integrator is SOCP_INT_DOPRI5, the model's launch table has no
+ * exact_jacobian entry (the interceptor, vtolUAV, a plugin without the traits), or the problem has a FREE state component on an
+ * interior node (its rows are the model's SwitchingStateFunction).  An error writes nothing and leaves the context unchanged.
+ * socp_ctx_counters advances by B M (S + 1) trajectories and one launch.  The _dev, host and _blocks forms as for socp_fields_batch. */
+int socp_ctx_has_exact_jacobian(const socp_ctx *ctx);   /* 1 / 0; SOCP_ERR_ARG for a NULL context */
+int socp_exact_jacobian_batch_dev(socp_ctx *ctx, int B, const double *d_Z, double *d_Fjac, double *d_F /* or NULL */);
+int socp_exact_jacobian_batch(socp_ctx *ctx, int B, const double *Z, double *Fjac, double *F);
+int socp_exact_jacobian_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
+                                     const double *time, const double *xnode, double *Fjac, double *F);
+
 /* replaces: shooting::Move(tf) (shooting.cpp:383-437) for a whole batch: the state ON a stored solution at a query time, and the
  * re-grid the reference's multi-stage flows build from it (testGoddard.cpp:115-145: vX[i] = Move(vt[i]), then InitShooting(vt, vX)
  * on a new structure).  Z[B][n], tq[B][K] -> Xq[B][K][s]; tout[B][K] (may be NULL) = the time actually reached.

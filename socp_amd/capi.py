@@ -173,6 +173,10 @@ def lib():
                                                _ip, _dp, _dp]
         L.socp_jacobi_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip,
                                                _ip, _dp, _dp]
+        L.socp_ctx_has_exact_jacobian.argtypes = [_vp]
+        L.socp_exact_jacobian_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp]
+        L.socp_exact_jacobian_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp]
+        L.socp_exact_jacobian_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]
         L.socp_move_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
         L.socp_move_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]
         L.socp_move_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp]
@@ -846,6 +850,43 @@ class Context:
             return _call_with_enough_cap(call, cap)
         finally:
             self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
+
+    # -- batched exact shooting Jacobian
+    def has_exact_jacobian(self):
+        """Whether this model has the exact shooting-Jacobian kernel (socp_ctx_has_exact_jacobian): the in-tree Goddard, double integrator
+        and covid19, and a plugin with the rhs_t, hamiltonian_t and switching_fn_t traits; not the interceptor, not vtolUAV."""
+        return self.L.socp_ctx_has_exact_jacobian(self.h) == 1
+
+    def exact_jacobian_batch_dev(self, B, d_Z, d_Fjac, d_F=None):
+        """Device pointers (ints; d_F may be None); enqueue only, no copy, no synchronise (socp_exact_jacobian_batch_dev)."""
+        self._chk(self.L.socp_exact_jacobian_batch_dev(self.h, int(B), _vp(d_Z), _vp(d_Fjac), _vp(d_F)))
+
+    def exact_jacobian_batch(self, Z, residual=False, blocks=None):
+        """The exact Jacobian dF/dz of the shooting function for every row of Z (include/socp_hip.h): dual numbers carried through the
+        residual's RK4 steps and its boundary, continuity, Hamiltonian and switching rows, with the free-time columns.  Returns the
+        DEVICE tensor J[B][n][n] holding each matrix COLUMN-major (J[b][j][r] = dF_r/dz_j: J[b].T is the matrix), the layout
+        socp_linsolve_batch_dev and socp_svd_batch_dev take; with residual=True (J, F[B][n]).  blocks = (params, time, xnode) as in
+        fields_batch.  The same bits on a throughput-flavour context."""
+        import torch
+        dev = torch.device("cuda")
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        Zd = up(Z).reshape(-1, self.n)
+        B, n = Zd.shape[0], self.n
+        held = [up(a).reshape(B, -1) if a is not None else None for a in (blocks if blocks is not None else ())]
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        J = torch.empty((B, n, n), dtype=torch.float64, device=dev)
+        F = torch.empty((B, n), dtype=torch.float64, device=dev) if residual else None
+        torch.cuda.synchronize()
+        if held:
+            pp, tt, xx = held
+            self._chk(self.L.socp_problem_set_blocks_dev(self.h, ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx)))
+        try:
+            self.exact_jacobian_batch_dev(B, Zd.data_ptr(), J.data_ptr(), ptr(F))
+            self.synchronize()
+        finally:
+            if held:
+                self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
+        return (J, F) if residual else J
 
     # -- batched Move(tf) / re-grid
     def move_batch_dev(self, B, d_Z, K, d_tq, d_Xq, d_tout=None):

@@ -1370,6 +1370,82 @@ int socp_fields_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
                        [&] { return socp_fields_batch(c, B, Z, cols, stride, skip, cap, tq, det, count, nchange, tconj, Phi); });
 }
 
+/* ---- batched exact shooting Jacobian ------------------------------------------------------- */
+
+int socp_ctx_has_exact_jacobian(const socp_ctx *c) { return c ? (table_of(c)->exact_jacobian ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+int exact_jacobian_args(socp_ctx *c, const char *who, int B)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (const int rc = args_tail(c, w, table_of(c)->exact_jacobian != nullptr,
+                                 "exact_jacobian entry (a model without the rhs_t, hamiltonian_t and switching_fn_t traits, or one with a "
+                                 "switching_state hook, custom final rows or its own ComputeTraj)",
+                                 "the exact Jacobian follows"))
+        return rc;
+    // a FREE state component of an interior node: its rows are the model's SwitchingStateFunction, which the definition does not cover
+    for (int k = 1; k < c->M; k++)
+        for (int j = 0; j < c->dim; j++)
+            if (c->mode_x[(size_t)k * c->dim + j] == SOCP_FREE)
+                return fail(c, SOCP_ERR_UNSUPPORTED, w + ": a FREE state component on an interior node (node " + std::to_string(k) +
+                                                         ", component " + std::to_string(j) + ") is not covered");
+    return SOCP_OK;
+}
+}  // namespace
+
+namespace {
+// the zero-fill and the launch of a batch that is checked and not empty
+int exact_jacobian_launch(socp_ctx *c, int B, const double *d_Z, double *d_Fjac, double *d_F)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_traj += (long long)B * c->M * (c->S + 1); c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->exact_jacobian(c->stream, c->P, c->pb, B, d_Z, d_Fjac, d_F));
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_exact_jacobian_batch_dev(socp_ctx *c, int B, const double *d_Z, double *d_Fjac, double *d_F)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = exact_jacobian_args(c, "exact_jacobian_batch", B)) return rc;
+    if (B > 0 && (!d_Z || !d_Fjac)) return fail(c, SOCP_ERR_ARG, "exact_jacobian_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    return exact_jacobian_launch(c, B, d_Z, d_Fjac, d_F);
+}
+
+int socp_exact_jacobian_batch(socp_ctx *c, int B, const double *Z, double *Fjac, double *F)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = exact_jacobian_args(c, "exact_jacobian_batch", B)) return rc;
+    if (B > 0 && (!Z || !Fjac)) return fail(c, SOCP_ERR_ARG, "exact_jacobian_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nZ = (size_t)B * c->n, nJ = nZ * c->n;
+    double *dZ, *dJ;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, dZ));
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (nJ + nZ)));
+    dJ = c->s_out.as<double>();
+    double *dF = dJ + nJ;
+    const int rc = exact_jacobian_launch(c, B, dZ, dJ, F ? dF : nullptr);      // the arguments are checked above, once
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, Fjac, dJ, nJ));
+    if (F) HIP_TRY(c, copy_down(c, F, dF, nZ));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_exact_jacobian_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                                     const double *xnode, double *Fjac, double *F)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = exact_jacobian_args(c, "exact_jacobian_batch_blocks", B)) return rc;
+    if (const int rc = blocks_stride(c, "exact_jacobian_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !Fjac)) return fail(c, SOCP_ERR_ARG, "exact_jacobian_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode, [&] { return socp_exact_jacobian_batch(c, B, Z, Fjac, F); });
+}
+
 int socp_regrid_num_param(const socp_ctx *c, int M2, const int *mode_t2)
 {
     unsigned long long bits[4];

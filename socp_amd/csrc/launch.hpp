@@ -39,11 +39,12 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 12;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 13;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
                                    // kPluginAbi = 12: batched extrema launcher
+                                   // kPluginAbi = 13: batched exact shooting-Jacobian launcher
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -87,6 +88,11 @@ struct ModelLaunchers {
     // integrators, one launch.  Every model with a trace entry has it
     hipError_t (*extrema)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, double *, double *, double *,
                           double *, int *, int *);
+    // batched exact shooting Jacobian (socp_exact_jacobian_batch): Z[B][n] -> Fjac[B][n*n] column-major (zero-filled on the stream,
+    // then ONE launch) and, unless null, F[B][n]; fixed-step integrator only.  Null: the model lacks one of the traits rhs_t,
+    // hamiltonian_t, switching_fn_t, or has a switching_state hook, custom final rows or its own ComputeTraj (plugin_impl.hpp).  The
+    // in-tree models' entries live in kernels_exact_jacobian.hip, one object without contraction that both flavours' tables point to
+    hipError_t (*exact_jacobian)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
@@ -203,6 +209,11 @@ hipError_t fields_dint(hipStream_t st, const ModelParams &P, const ProblemDev &p
                        int cap, double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi);
 hipError_t fields_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int cols, int stride, int skip,
                         int cap, double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi);
+
+// socp_exact_jacobian_batch of the in-tree models (kernels_exact_jacobian.hip: one object without contraction, for both flavours)
+hipError_t exact_jacobian_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
+hipError_t exact_jacobian_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
+hipError_t exact_jacobian_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
 
 // the in-tree models' tables, one translation unit each
 // Goddard, double integrator, covid19 by SOCP_MODEL_* id (builtin_tables.hpp); null for any other id

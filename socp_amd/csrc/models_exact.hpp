@@ -301,23 +301,16 @@ struct GoddardExactT {
         return bu / au;
     }
 
+    // goddard.cpp:104-185 on T: the control u of both laws, the closed-form singular control included, from the quantities Model() and
+    // Hamiltonian() both derive from the state.  ONE text for rhs_t and hamiltonian_t.
     template <class T>
-    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S])
+    __device__ static __forceinline__ void control_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T &r,
+                                                    const T &v, const T &g, const T &norm_pv, const T &E, const T &pvdotv, const T (&pd)[6],
+                                                    T (&u)[3])
     {
-        const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
-        const T p_vx = X[10], p_vy = X[11], p_vz = X[12], p_mass = X[13];
-        const double b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR], u_max = P.p[GP_UMAX];
-        const T r = d_sqrt(x*x + y*y + z*z);
-        const T v = d_sqrt(vx*vx + vy*vy + vz*vz);
-        const T pvdotv = p_vx*vx + p_vy*vy + p_vz*vz;
-        const T g = 1 / r / r;
-        const T norm_pv = d_sqrt(p_vx*p_vx + p_vy*p_vy + p_vz*p_vz);
+        const T mass = X[6], p_vx = X[10], p_vy = X[11], p_vz = X[12], p_mass = X[13];
+        const double b = P.p[GP_B], C = P.p[GP_C], u_max = P.p[GP_UMAX];
         const T Switch = P.p[GP_MU1] - b*p_mass - C / mass*norm_pv;
-        const T E = d_exp(-kr*(r - 1));
-        T pd[6];
-        costate_dots_t<T>(P, X, r, v, g, E, pvdotv, pd);
-
-        T u[3];
         // goddard.cpp:147-185 from the thrust magnitude on; A = double or T
         auto thrust = [&](const auto &alpha_u) {
             u[0] = -p_vx*alpha_u / norm_pv;
@@ -340,6 +333,24 @@ struct GoddardExactT {
                 else thrust(P.p[GP_SING]);
             } else thrust(0.0);
         }
+    }
+
+    template <class T>
+    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S])
+    {
+        const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
+        const T p_vx = X[10], p_vy = X[11], p_vz = X[12];
+        const double b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
+        const T r = d_sqrt(x*x + y*y + z*z);
+        const T v = d_sqrt(vx*vx + vy*vy + vz*vz);
+        const T pvdotv = p_vx*vx + p_vy*vy + p_vz*vz;
+        const T g = 1 / r / r;
+        const T norm_pv = d_sqrt(p_vx*p_vx + p_vy*p_vy + p_vz*p_vz);
+        const T E = d_exp(-kr*(r - 1));
+        T pd[6];
+        costate_dots_t<T>(P, X, r, v, g, E, pvdotv, pd);
+        T u[3];
+        control_t<T>(P, sw0, sw1, t, X, r, v, g, norm_pv, E, pvdotv, pd, u);
         const T norm_u = d_sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
         const T pvdotu = p_vx*u[0] + p_vy*u[1] + p_vz*u[2];
         dX[0] = vx;
@@ -383,6 +394,41 @@ struct GoddardExactT {
                                           const double (&X)[S], const double (&)[S])
     {
         return hamiltonian(P, sw0, sw1, t, X);
+    }
+
+    // the Hamiltonian and the free-interior-time row over a number type T (socp_exact_jacobian_batch: T = Dual): goddard.cpp:256-295 on
+    // plain IEEE operations in the reference's association order, the control from control_t -- the text rhs_t runs.  With T = double:
+    // the bits of hamiltonian / switching_fn.  tests/fast_reference.py (goddard_ref's H) is the same text in Python.
+    template <class T>
+    __device__ static __forceinline__ T hamiltonian_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S])
+    {
+        const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
+        const T p_x = X[7], p_y = X[8], p_z = X[9], p_vx = X[10], p_vy = X[11], p_vz = X[12], p_mass = X[13];
+        const double b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
+        const T r = d_sqrt(x*x + y*y + z*z);
+        const T v = d_sqrt(vx*vx + vy*vy + vz*vz);
+        const T pvdotv = p_vx*vx + p_vy*vy + p_vz*vz;
+        const T g = 1 / r / r;
+        const T norm_pv = d_sqrt(p_vx*p_vx + p_vy*p_vy + p_vz*p_vz);
+        const T E = d_exp(-kr*(r - 1));
+        T pd[6];
+        costate_dots_t<T>(P, X, r, v, g, E, pvdotv, pd);                 // read by the singular control only
+        T u[3];
+        control_t<T>(P, sw0, sw1, t, X, r, v, g, norm_pv, E, pvdotv, pd, u);
+        const T norm_u = d_sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        return P.p[GP_MU1]*norm_u + P.p[GP_MU2]*norm_u*norm_u
+            + p_x*vx + p_y*vy + p_z*vz
+            + p_vx*(-KD*v*vx*E / mass - g*x / r + C*u[0] / mass)
+            + p_vy*(-KD*v*vy*E / mass - g*y / r + C*u[1] / mass)
+            + p_vz*(-KD*v*vz*E / mass - g*z / r + C*u[2] / mass)
+            - p_mass*b*norm_u;
+    }
+    // the free interior-time row is H(t, X-): Xp is not read, so the lanes of the next segment have no part in it
+    static constexpr bool kSwitchingReadsXp = false;
+    template <class T>
+    __device__ static __forceinline__ T switching_fn_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T (&)[S])
+    {
+        return hamiltonian_t<T>(P, sw0, sw1, t, X);
     }
 
     // event channel 0 (socp_events_batch): the switching function of the control law, goddard.cpp:135 in its order, on plain IEEE
@@ -483,6 +529,34 @@ struct DIntExact {
                                           const double (&X)[S], const double (&Xp)[S])
     {
         return hamiltonian(P, sw0, sw1, t, X) - hamiltonian(P, sw0, sw1, t, Xp);
+    }
+
+    // the Hamiltonian and the free-interior-time row over a number type T (socp_exact_jacobian_batch: T = Dual):
+    // doubleIntegrator.cpp:218-300 on plain IEEE operations; with T = double the bits of hamiltonian / switching_fn
+    template <class T>
+    __device__ static __forceinline__ T hamiltonian_t(const ModelParams &P, double, double, double, const T (&X)[S])
+    {
+        const double a_max = P.p[DP_AMAX], u_max = P.p[DP_UMAX];
+        T u[3];
+        u[0] = -X[9] / a_max;
+        u[1] = -X[10] / a_max;
+        u[2] = -X[11] / a_max;
+        const T norm_c = d_sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
+        if (d_val(norm_c) > u_max) {
+            u[0] = u[0] / norm_c*u_max;
+            u[1] = u[1] / norm_c*u_max;
+            u[2] = u[2] / norm_c*u_max;
+        }
+        const T norm_u = d_sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
+        return P.p[DP_MUT] + a_max * a_max*norm_u*norm_u / 2 + X[6] * X[3] + X[7] * X[4] + X[8] * X[5]
+             + a_max * (X[9]*u[0] + X[10] * u[1] + X[11] * u[2]);
+    }
+    // model.hpp:299-304 default, H(t, X-) - H(t, X+): the lanes of the next segment own -grad H(X+)
+    static constexpr bool kSwitchingReadsXp = true;
+    template <class T>
+    __device__ static __forceinline__ T switching_fn_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T (&Xp)[S])
+    {
+        return hamiltonian_t<T>(P, sw0, sw1, t, X) - hamiltonian_t<T>(P, sw0, sw1, t, Xp);
     }
 };
 
@@ -598,6 +672,41 @@ struct CovidExact {
                                           const double (&X)[S], const double (&Xp)[S])
     {
         return hamiltonian(P, sw0, sw1, t, X) - hamiltonian(P, sw0, sw1, t, Xp);
+    }
+
+    // the Hamiltonian and the free-interior-time row over a number type T (socp_exact_jacobian_batch: T = Dual): covid19.cpp:97-165 on
+    // plain IEEE operations; with T = double the bits of hamiltonian / switching_fn.  As in rhs_t a clamped control and an inactive
+    // penalty are plain doubles: the sum is written once (`rest`) and instantiated for the four combinations.
+    template <class T>
+    __device__ static __forceinline__ T hamiltonian_t(const ModelParams &P, double, double, double, const T (&X)[S])
+    {
+        const T Sx = X[0], E = X[1], I = X[2], pS = X[4], pE = X[5], pI = X[6], pR = X[7];
+        const double R0 = P.p[CP_R0], Tinf = P.p[CP_TINF], Tinc = P.p[CP_TINC], N = P.p[CP_N];
+        auto rest = [&](const auto &u, const auto &Ipen) -> T {
+            const auto Rt = R0 * (1 - u);
+            return u*u / 2 + Ipen
+                + pS * (-Rt / Tinf / N*Sx*I)
+                + pE * (Rt / Tinf / N*Sx*I - E / Tinc)
+                + pI * (E / Tinc - I / Tinf)
+                + pR * (I / Tinf);
+        };
+        const T u = (pE - pS)*Sx*I / Tinf / N * R0;
+        double uc = 0.0;
+        bool clamped = false;
+        if (d_val(u) <= P.p[CP_UMIN]) { uc = P.p[CP_UMIN]; clamped = true; }
+        if ((clamped ? uc : d_val(u)) >= P.p[CP_UMAX]) { uc = P.p[CP_UMAX]; clamped = true; }
+        if (d_val(I) >= P.p[CP_IMAX]) {
+            const T Ipen = P.p[CP_MUI]*(I - P.p[CP_IMAX])*(I - P.p[CP_IMAX]) / 2;
+            return clamped ? rest(uc, Ipen) : rest(u, Ipen);
+        }
+        return clamped ? rest(uc, 0.0) : rest(u, 0.0);
+    }
+    // model.hpp:299-304 default, H(t, X-) - H(t, X+): the lanes of the next segment own -grad H(X+)
+    static constexpr bool kSwitchingReadsXp = true;
+    template <class T>
+    __device__ static __forceinline__ T switching_fn_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T (&Xp)[S])
+    {
+        return hamiltonian_t<T>(P, sw0, sw1, t, X) - hamiltonian_t<T>(P, sw0, sw1, t, Xp);
     }
 };
 

@@ -42,6 +42,14 @@
 //       // where a comparison reads a value; a quantity that is a constant stays a plain double.  With T = double: the bits of rhs.
 //       template <class T> __device__ static void rhs_t(const socp::ModelParams &P, double sw0, double sw1, double t,
 //                                                       const T (&X)[S], T (&dX)[S]);
+//       // OPTIONAL -- with rhs_t, the Hamiltonian and the free-interior-time row over a number type (socp_exact_jacobian_batch: the
+//       // exact Jacobian of the shooting function).  With T = double: the bits of hamiltonian / switching_fn.  kSwitchingReadsXp says
+//       // whether the row is H(t, X) - H(t, Xp) (true: the library then takes -grad H(Xp) from hamiltonian_t) or does not read Xp
+//       // (false, the default).  A model with a switching_state hook, custom final rows or its own ComputeTraj does not get the entry.
+//       template <class T> __device__ static T hamiltonian_t(const socp::ModelParams &P, double sw0, double sw1, double t, const T (&X)[S]);
+//       template <class T> __device__ static T switching_fn_t(const socp::ModelParams &P, double sw0, double sw1, double t,
+//                                                             const T (&X)[S], const T (&Xp)[S]);
+//       static constexpr bool kSwitchingReadsXp = ...;
 //   };
 //   SOCP_DEFINE_MODEL_PLUGIN(1001, MyModel, 3 /*nparams*/, 30 /*stepNbr*/, {1.0, 2.0, 3.0})
 //
@@ -49,10 +57,11 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, batched extrema, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, batched exact shooting Jacobian when it has hamiltonian_t and switching_fn_t too, batched extrema, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
 #include "fields.hpp"
+#include "exact_jacobian.hpp"
 #include "jacobi.hpp"
 #include "launch.hpp"
 #include "variational.hpp"
@@ -264,6 +273,37 @@ hipError_t fields(hipStream_t st, const ModelParams &P, const ProblemDev &pb, in
                 : fields_cols<Mdl, false>(st, P, pb, B, Z, stride, skip, cap, tq, det, count, nchange, tconj, Phi);
 }
 
+// optional traits hamiltonian_t and switching_fn_t beside rhs_t, and none of the hooks the definition does not cover -> the model has
+// the exact shooting Jacobian (socp_exact_jacobian_batch)
+template <class M, class = void> struct has_exact_jacobian : std::false_type {};
+template <class M>
+struct has_exact_jacobian<M, std::void_t<decltype(M::template hamiltonian_t<Dual>(std::declval<const ModelParams &>(), 0.0, 0.0, 0.0,
+                                                                                   std::declval<const Dual (&)[M::S]>())),
+                                         decltype(M::template switching_fn_t<Dual>(std::declval<const ModelParams &>(), 0.0, 0.0, 0.0,
+                                                                                    std::declval<const Dual (&)[M::S]>(),
+                                                                                    std::declval<const Dual (&)[M::S]>()))>>
+    : std::bool_constant<has_fields<M>::value && !has_custom_traj<M>::value && !has_custom_final<M>::value && !has_switching_state<M>::value> {};
+
+// batched exact shooting Jacobian: fixed-step integrator only.  The matrices are zero-filled on the stream, then ONE launch: one group of
+// S + 1 neighbouring lanes per (row, segment), 64 / (S + 1) groups per single-wave workgroup (exact_jacobian.hpp); always one wave per
+// SIMD.  The translation unit must be built without contraction
+template <class Mdl>
+hipError_t exact_jacobian(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(Fjac, 0, sizeof(double) * (size_t)B * pb.n * pb.n, st);
+    if (e != hipSuccess) return e;
+    constexpr int gpw = 64 / (Mdl::S + 1);
+    const long slabs = (long)B * pb.M;
+    const unsigned grid = (unsigned)((slabs + gpw - 1) / gpw);
+    if (pb.pp_params || pb.pp_time || pb.pp_xnode)
+        hipLaunchKernelGGL((exact_jacobian_kernel<Mdl, true>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, Fjac, F);
+    else
+        hipLaunchKernelGGL((exact_jacobian_kernel<Mdl, false>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, Fjac, F);
+    return hipGetLastError();
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -271,7 +311,8 @@ struct has_variational<M, std::void_t<decltype(M::aug_rhs(std::declval<const Mod
                                       decltype(M::dhamiltonian(std::declval<const ModelParams &>(), 0.0, (const double *)nullptr,
                                                                std::declval<double (&)[M::S + 1]>()))>> : std::true_type {};
 
-// FIELDS = false: leave the fields entry to the caller (the in-tree models' entries live in kernels_fields.hip, builtin_tables.hpp)
+// FIELDS = false: leave the fields and exact_jacobian entries to the caller (the in-tree models' entries live in kernels_fields.hip and
+// kernels_exact_jacobian.hip, builtin_tables.hpp)
 template <class Mdl, bool FIELDS = true>
 ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> defaults)
 {
@@ -291,6 +332,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     }
     if constexpr (!has_custom_traj<Mdl>::value && !no_jacobi<Mdl>::value) t.jacobi = &jacobi<Mdl>;   // nor Jacobi fields (their chart changes rewrite the costate)
     if constexpr (FIELDS && has_fields<Mdl>::value && !has_custom_traj<Mdl>::value) t.fields = &fields<Mdl>;
+    if constexpr (FIELDS && has_exact_jacobian<Mdl>::value) t.exact_jacobian = &exact_jacobian<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

@@ -359,6 +359,52 @@ def jacobi_local(ctx, args, local, lo, rank, params=None):
             "wall_s": wall, "file": path}
 
 
+def exactjac_local(ctx, args, local, lo, rank, params=None):
+    """--exactjac-out: the exact shooting Jacobian (socp_exact_jacobian_batch) of this rank's CONVERGED chains, each with its own
+    parameter block when the chains have one, beside the forward difference the solver read: socp_fd_jacobian_multi_dev, epsfcn
+    1e-15, at (z, F(z)) with F from socp_residual_batch_dev of the context's OWN flavour -- not the F the exact call returns, which is
+    the reference-order residual whatever the flavour; differencing a throughput-flavour F(z + h) against it would divide the
+    flavours' difference by h.  Written to PATH.rank<r>.npz: index [k], fd_dev [k] = max|J_fd - J| / max|J| per row, and sigma [k][n] = the singular
+    values of the exact matrices (socp_svd_batch_dev, 60 sweeps) where n <= 142, else an empty array.  Runs after the timed solve.
+    Returns the record entry of this rank; a measuring instrument, not a verdict."""
+    import torch
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.exactjac_out)
+    k, n = len(conv), ctx.n
+    t0 = time.perf_counter()
+    fd_dev, sigma = np.zeros(k), np.zeros((k, 0))
+    if k:
+        dev = torch.device("cuda")
+        Zd = torch.from_numpy(np.ascontiguousarray(z, dtype=np.float64)).to(dev)
+        held = None if own is None else torch.from_numpy(np.ascontiguousarray(own, dtype=np.float64)).to(dev)
+        J = ctx.exact_jacobian_batch(Zd, blocks=None if held is None else (held, None, None))
+        Jfd = torch.empty_like(J)
+        Ffd = torch.empty((k, n), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        if held is not None:
+            ctx._chk(ctx.L.socp_problem_set_blocks_dev(ctx.h, held.data_ptr(), held.shape[1], None, None))
+        try:
+            ctx.residual_batch_dev(k, Zd.data_ptr(), Ffd.data_ptr())
+            ctx.fd_jacobian_multi_dev(k, Zd.data_ptr(), Ffd.data_ptr(), 1e-15, Jfd.data_ptr())
+            ctx.synchronize()
+        finally:
+            if held is not None:
+                ctx.L.socp_problem_set_blocks_dev(ctx.h, None, 0, None, None)
+        fd_dev = ((Jfd - J).abs().amax(dim=(1, 2)) / J.abs().amax(dim=(1, 2))).cpu().numpy()
+        if n <= 142:
+            sig = torch.empty((k, n), dtype=torch.float64, device=dev)
+            sweeps = torch.zeros(k, dtype=torch.int32, device=dev)
+            info = torch.zeros(k, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            ctx.svd_batch_dev(k, n, J.data_ptr(), 60, sig.data_ptr(), None, sweeps.data_ptr(), info.data_ptr())
+            ctx.synchronize()
+            sigma = sig.cpu().numpy()
+    wall = time.perf_counter() - t0
+    np.savez(path, index=index, fd_dev=fd_dev, sigma=sigma)
+    some = k > 0
+    return {"rows": int(k), "fd_dev_median": float(np.median(fd_dev)) if some else None, "fd_dev_max": float(fd_dev.max()) if some else None,
+            "sigma_min_min": float(sigma[:, -1].min()) if some and sigma.shape[1] else None, "wall_s": wall, "file": path}
+
+
 def fields_local(ctx, args, local, lo, rank, params=None):
     """--fields-out: the conjugate-time test with EXACT Jacobi fields (socp_fields_batch) of this rank's CONVERGED chains, each with
     its own parameter block when the chains have one: det of J(t) = dx(t)/dp(t0), carried through the residual's RK4 steps on dual
@@ -664,6 +710,12 @@ def main():
                          "batch (socp_fields_batch): dx(t)/dp(t0) carried through the RK4 steps on dual numbers, no forward "
                          "difference; writes PATH.rank<r>.npz (index, tq, det, count, nchange, tconj; phi with --fields-phi) and adds "
                          "fields {rows, with_change, tconj_min, tconj_median} to the record.  Not for the interceptor")
+    ap.add_argument("--exactjac-out", default=None, metavar="PATH",
+                    help="after the solve, take the EXACT shooting Jacobian of this rank's converged chains as one batch "
+                         "(socp_exact_jacobian_batch) beside the forward difference (socp_fd_jacobian_multi_dev); writes PATH.rank<r>.npz "
+                         "(index, fd_dev = max|J_fd - J| / max|J| per row, sigma = the singular values of the exact matrices where "
+                         "n <= 142) and adds exact_jacobian {rows, fd_dev_median, fd_dev_max, sigma_min_min} to the record.  Not for "
+                         "the interceptor")
     ap.add_argument("--extrema-out", default=None, metavar="PATH",
                     help="after the timed solve, each rank reduces the trajectories of the converged chains of its own block in one launch "
                          "that stores no row (socp_extrema_batch): the smallest and the largest value of every state and, by "
@@ -714,6 +766,8 @@ def main():
         ap.error("--jacobi-out: the interceptor has no Jacobi-field kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
     if args.fields_out and args.model == "interceptor":
         ap.error("--fields-out: the interceptor has no exact-fields kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
+    if args.exactjac_out and args.model == "interceptor":
+        ap.error("--exactjac-out: the interceptor has no exact-Jacobian kernel (its own ComputeTraj and final rows)")
     if args.extrema_out and args.model == "interceptor":
         ap.error("--extrema-out is implemented for the Goddard sweeps")
     if not 0 <= args.extrema_what <= 7:
@@ -858,6 +912,8 @@ def main():
         extra["jacobi" if rank == 0 else "jacobi_rank%d" % rank] = jacobi_local(ctx, args, local, lo_w, rank, blocks)
     if args.fields_out:
         extra["fields" if rank == 0 else "fields_rank%d" % rank] = fields_local(ctx, args, local, lo_w, rank, blocks)
+    if args.exactjac_out:
+        extra["exact_jacobian" if rank == 0 else "exact_jacobian_rank%d" % rank] = exactjac_local(ctx, args, local, lo_w, rank, blocks)
     if args.extrema_out:
         extra["extrema" if rank == 0 else "extrema_rank%d" % rank] = extrema_local(ctx, args, local, lo_w, rank, blocks)
     if args.sing_out:
