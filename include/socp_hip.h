@@ -844,6 +844,87 @@ int socp_branch_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
                              double *Y, double *ttheta, double *rnorm, int *count, int *nfold, int *ifold, int *status, int *nreject,
                              double *hlast, double *zgoal);
 
+/* Polishing a table of roots: damped Newton iteration on B rows at once, in lock step, with the exact shooting Jacobian.  [ext] A
+ * sweep ends in roots hybrd stopped on at xtol with a Broyden-updated, differenced Jacobian; this call drives them to rounding level
+ * and says per row how far it got -- the damped Newton corrector of the indirect-methods tools.  It stands beside socp_chains_solve
+ * and changes none of its iterates.  It is the first consumer of socp_exact_jacobian_batch (jac = 2). */
+typedef struct socp_newton_options {
+    int jac;          /* 0 forward difference, 1 variational, 2 exact (socp_exact_jacobian_batch) */
+    double epsfcn;    /* jac == 0 only: the step rule of socp_fd_jacobian_multi_dev */
+    double ftol;      /* > 0: CONVERGED when ||F||inf <= ftol */
+    double xtol;      /* >= 0: SMALL_STEP when the step taken is <= xtol ||z||inf; 0 disables */
+    int trials;       /* 1 .. 8: step lengths 1, 1/2, ... 2^-(trials-1) tried per round */
+    int rounds;       /* >= 1 */
+} socp_newton_options;
+#define SOCP_NEWTON_RUNNING    0   /* the rounds ran out; Zout is the last accepted point, call again from it to go on */
+#define SOCP_NEWTON_CONVERGED  1   /* ||F||inf <= ftol */
+#define SOCP_NEWTON_SMALL_STEP 2   /* the step taken was <= xtol ||z||inf */
+#define SOCP_NEWTON_STALLED    3   /* no trial step lowered ||F||inf enough: as good as this arithmetic (or this Jacobian) gets */
+#define SOCP_NEWTON_SINGULAR   4   /* the elimination found no pivot, or its solution is not finite */
+#define SOCP_NEWTON_BAD_START  5   /* F at the start is not finite */
+/* Z[B][n] -> per row: Zout[B][n] (the accepted point y), Fout[B][n] (F0 = F(y); may be NULL), rnorm[B] (rn = ||F0||inf), dnorm[B]
+ * (||delta||inf of the FULL Newton step of the last system solved for the row: an a-posteriori error estimate of the point it was
+ * solved at; NaN while no system was solved, and for SINGULAR and BAD_START), iters[B] (accepted steps), nhalf[B] (the sum of the
+ * accepted steps' k), status[B], rhist[B][rounds + 1] (may be NULL; rn after 0, 1, ... accepted steps, unused slots NaN).
+ * All norms are max-norms: max_i |x_i|, a NaN when an entry is one (an infinite entry makes it infinite).  They are maxima, so no
+ * reduction order enters a result.  Per row the state is y, F0, rn and the counters.
+ * Start: F0 = F(Z) from ONE residual launch of the B rows in the context's flavour, each row with its blocks; rhist[b][0] = rn.
+ *   rn not finite: BAD_START, Zout = Z, dnorm NaN.  rn <= ftol: CONVERGED with iters = 0.
+ * One ROUND, for every row that is not finished:
+ *   1. J at (y, F0): jac 0: socp_fd_jacobian_multi_dev with epsfcn and dedup on (step 4 of socp_tangent_batch); jac 1: the variational
+ *      Jacobian; jac 2: the exact Jacobian (socp_exact_jacobian_batch; its own F output is not requested -- F0 is always the residual
+ *      launch's, so one flavour's merit function is measured by one kernel)
+ *   2. J delta = -F0 (the negation is exact): step 6 of socp_tangent_batch with K = 1, in reference order in both flavours.
+ *      dn = max_i |delta_i|.  info != 0: SINGULAR, y stays, dnorm NaN.  Otherwise dnorm = dn
+ *   3. the trial points, k = 0 .. trials - 1: s_k = 2^-k, t_k,i = y_i + fl(s_k delta_i)
+ *   4. F_k = F(t_k) from ONE residual launch of (rows x trials) rows, the row's block rows replicated where rows have their own
+ *   5. c_k = 1 - s_k / 4 (exact).  The first k with max_i |F_k,i| < fl(c_k rn) wins; a NaN never passes.  None passes: STALLED, y stays
+ *      (with an ftol below rounding level this is how a row says "as good as this arithmetic gets").  Otherwise y <- t_k, F0 <- F_k,
+ *      rn <- max_i |F_k,i|, iters += 1, nhalf += k, rhist[iters] = rn
+ *   6. rn <= ftol: CONVERGED.  Else if xtol > 0 and fl(s_k dn) <= fl(xtol max_i |y_i|) (the new y): SMALL_STEP
+ *   7. a finished row (status != 0) changes nothing any more; after `rounds` rounds an unfinished row is RUNNING.
+ * In reference-order contexts every operation above is one IEEE rounding (no contraction, IEEE division): the call is a fixed
+ * sequence of roundings per row, independent of the other rows, of B and of which rows are still running
+ * (tests/newton_reference.py restates it in numpy).  SOCP_VARIANT_LANE_FAST contexts differ through the model's own launches only
+ * (residual, Jacobian); the exact Jacobian is the same object in both flavours.
+ * Finished rows cost nothing: a round begins with a stable compaction of the unfinished rows, in ascending row order, into a list
+ * (three launches -- count, scan, scatter -- none of which waits on another workgroup); a gather copies y, F0, -F0 and the rows' own
+ * block rows into compact slots; the Jacobian, the elimination, the trial build and the trial residual run on compact slots, and the
+ * update scatters back through the list.  Slots at or beyond the live count keep what an earlier round (or the start, which sets
+ * slot b to row b) left there: valid rows no output depends on.
+ * The _dev form takes device pointers (the options are host values that travel as kernel arguments), launches all B slots in every
+ * round, enqueues exactly `rounds` rounds on the context's stream with no host decision, and neither allocates, copies nor
+ * synchronises.  The host forms stage through that stream and the context's grow-only buffers; after every compaction they read the
+ * live count back (one word), run the round on that many slots and stop at 0.  Both give identical bits.  _blocks: per-row blocks
+ * like socp_residual_batch_blocks; the context's own blocks are restored afterwards.
+ * socp_newton_work_bytes: the bytes of d_work for B rows and opt->trials (0 without a problem, for B < 0, a NULL opt or trials
+ * outside 1 .. 8): F0, the compact slots (points, residuals, right-hand sides, block rows, J[B][n*n]), the B trials trial rows
+ * (points, residuals, block rows), the list, and on a model with variational equations what socp_var_jacobian_multi_dev integrates in.
+ * Launches: the start is 2 (residual, state).  A round on s slots is the compaction (3), the gather, the Jacobian (jac 0: 1, jac 1: 3,
+ * jac 2: 1), the elimination, the trial build, ONE residual launch, the update: 9 launches (jac 1: 11).  socp_ctx_counters advances
+ * by B M trajectories and 2 launches for the start and, per round on s slots, by the Jacobian's trajectories (jac 0: s T of the dedup
+ * list, jac 1: s M, jac 2: s M (S + 1)) plus s trials M, and by 9 (11) launches; s = B in the _dev form, the live count in the host
+ * forms, whose last compaction (live count 0) adds 3 launches and nothing else.
+ * jac 0 / 1: all models, plugins included, both variants, both integrators (entries residual, fdjac, var_jacobian); jac 2 adds the
+ * entry exact_jacobian and its limits.  No new launch-table entry.
+ * SOCP_ERR_ARG: no problem set, B < 0, a NULL options pointer, jac outside 0 .. 2, trials outside 1 .. 8, rounds < 1, !(ftol > 0),
+ * xtol < 0 or NaN, a NULL required pointer with B > 0 (all but Fout and rhist), work_bytes below socp_newton_work_bytes, _blocks with
+ * params and param_stride != nparams + 2;  SOCP_ERR_UNSUPPORTED: jac == 1 without variational equations, jac == 2 where
+ * socp_exact_jacobian_batch refuses (no entry, SOCP_INT_DOPRI5, a FREE interior state component), n beyond the elimination's bound;
+ * B == 0: SOCP_OK without a launch.  An error writes nothing and leaves the context unchanged.
+ * Not covered: no trust region (the only globalisation is the halving above); it does not replace hybrd -- it polishes rows that are
+ * already near a root; no change to socp_chains_solve; a state-dependent kink differentiates the branch taken; with jac = 2 Goddard's
+ * mu2 = 0 switching times are not differentiated (socp_exact_jacobian_batch); one GPU. */
+size_t socp_newton_work_bytes(const socp_ctx *ctx, int B, const socp_newton_options *opt);
+int socp_newton_batch_dev(socp_ctx *ctx, int B, const double *d_Z, const socp_newton_options *opt, void *d_work, size_t work_bytes,
+                          double *d_Zout, double *d_Fout, double *d_rnorm, double *d_dnorm, int *d_iters, int *d_nhalf, int *d_status,
+                          double *d_rhist);
+int socp_newton_batch(socp_ctx *ctx, int B, const double *Z, const socp_newton_options *opt, double *Zout, double *Fout,
+                      double *rnorm, double *dnorm, int *iters, int *nhalf, int *status, double *rhist);
+int socp_newton_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                             const double *xnode, const socp_newton_options *opt, double *Zout, double *Fout, double *rnorm,
+                             double *dnorm, int *iters, int *nhalf, int *status, double *rhist);
+
 /* The distinct roots of a whole sweep: which distinct rows does a table hold, how many rows went to each, and which row went where.
  * Model-independent (no problem has to be set, no launch table is used).
  * Rows V[B][ld]; the first n <= ld entries of a row are compared.  Greedy leader grouping IN ROW ORDER:

@@ -29,6 +29,7 @@ INT_RK4, INT_DOPRI5 = 0, 1
 GODDARD_PARAM_NAMES = ["C", "b", "KD", "kr", "u_max", "mu1", "mu2", "singularControl"]
 DIR_PARAM, DIR_TIME, DIR_XNODE = 0, 1, 2      # what a direction of tangent_batch addresses (SOCP_DIR_*)
 BRANCH_RUNNING, BRANCH_REACHED, BRANCH_FULL, BRANCH_STEP_TOO_SMALL, BRANCH_SINGULAR, BRANCH_BAD_START = range(6)      # status of branch_batch (SOCP_BRANCH_*)
+NEWTON_RUNNING, NEWTON_CONVERGED, NEWTON_SMALL_STEP, NEWTON_STALLED, NEWTON_SINGULAR, NEWTON_BAD_START = range(6)      # status of newton_batch (SOCP_NEWTON_*)
 GROUP_OVERFLOW, GROUP_NOTFINITE, GROUP_MASKED = -1, -2, -3      # the negative labels of group_batch (SOCP_GROUP_*)
 
 _dp = C.POINTER(C.c_double)
@@ -67,6 +68,16 @@ def branch_options(epsfcn=1e-15, jac=0, wtheta=1.0, dir=1, h0=0.1, hmin=1e-8, hm
     """A BranchOptions with the defaults of branch_batch; goal=None: no goal."""
     return BranchOptions(float(epsfcn), int(jac), float(wtheta), int(dir), float(h0), float(hmin), float(hmax), float(grow), int(kfast),
                          int(max_corr), float(ftol), 0 if goal is None else 1, 0.0 if goal is None else float(goal), int(cap), int(rounds))
+
+
+class NewtonOptions(C.Structure):
+    """socp_newton_options (include/socp_hip.h)."""
+    _fields_ = [("jac", C.c_int), ("epsfcn", C.c_double), ("ftol", C.c_double), ("xtol", C.c_double), ("trials", C.c_int), ("rounds", C.c_int)]
+
+
+def newton_options(jac=2, epsfcn=1e-15, ftol=1e-12, xtol=0.0, trials=4, rounds=20):
+    """A NewtonOptions with the defaults of newton_batch."""
+    return NewtonOptions(int(jac), float(epsfcn), float(ftol), float(xtol), int(trials), int(rounds))
 
 
 class ChainStats(C.Structure):
@@ -198,6 +209,12 @@ def lib():
         L.socp_branch_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _bo, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _dp, _dp]
         L.socp_branch_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _bo, _dp, _dp, _dp, _ip, _ip,
                                                _ip, _ip, _ip, _dp, _dp]
+        _no = C.POINTER(NewtonOptions)
+        L.socp_newton_work_bytes.argtypes = [_vp, C.c_int, _no]
+        L.socp_newton_work_bytes.restype = C.c_size_t
+        L.socp_newton_batch_dev.argtypes = [_vp, C.c_int, _vp, _no, _vp, C.c_size_t] + [_vp] * 8
+        L.socp_newton_batch.argtypes = [_vp, C.c_int, _dp, _no, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _dp]
+        L.socp_newton_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _no, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _dp]
         L.socp_singular_work_bytes.argtypes = [_vp, C.c_int]
         L.socp_singular_work_bytes.restype = C.c_size_t
         L.socp_singular_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_double, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]
@@ -1039,6 +1056,36 @@ class Context:
                                                   _d(rn), *(a.ctypes.data_as(_ip) for a in (count, nfold, ifold, status, nreject)), _d(hlast),
                                                   _d(zgoal)))
         return dict(y=Y, ttheta=tth, rnorm=rn, count=count, nfold=nfold, ifold=ifold, status=status, nreject=nreject, hlast=hlast, zgoal=zgoal)
+
+    # -- batched Newton polish
+    def newton_work_bytes(self, B, opts):
+        """Bytes of the workspace newton_batch_dev needs for B rows and opts.trials (socp_newton_work_bytes)."""
+        return int(self.L.socp_newton_work_bytes(self.h, int(B), C.byref(opts)))
+
+    def newton_batch_dev(self, B, d_Z, opts, d_work, work_bytes, d_Zout, d_Fout, d_rnorm, d_dnorm, d_iters, d_nhalf, d_status, d_rhist=None):
+        """Device pointers (ints; d_Fout and d_rhist may be None), opts a NewtonOptions; enqueues exactly opts.rounds rounds on all B
+        slots, no allocation, no copy, no synchronise (socp_newton_batch_dev)."""
+        self._chk(self.L.socp_newton_batch_dev(self.h, int(B), _vp(d_Z), C.byref(opts), _vp(d_work), int(work_bytes), _vp(d_Zout), _vp(d_Fout),
+                                               _vp(d_rnorm), _vp(d_dnorm), _vp(d_iters), _vp(d_nhalf), _vp(d_status), _vp(d_rhist)))
+
+    def newton_batch(self, Z, opts=None, params=None, time=None, xnode=None, residual=True, history=True, **kw):
+        """Damped Newton polish of every row of Z with the exact (jac=2), variational (1) or forward-difference (0) Jacobian
+        (include/socp_hip.h has the definition).  opts: a NewtonOptions, or keyword arguments of newton_options().  Returns dict(z[B][n],
+        f[B][n] (None unless residual), rnorm[B], dnorm[B], iters[B], nhalf[B], status[B] (NEWTON_*), rhist[B][rounds + 1] (None unless
+        history; unused slots NaN)).  params / time / xnode: per-row blocks as in residual_batch_blocks."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        if opts is not None and kw:
+            raise TypeError("newton_batch: give a NewtonOptions or keyword options, not both (%s)" % ", ".join(sorted(kw)))
+        opts = newton_options(**kw) if opts is None else opts
+        blocks = _block_args(B, params, time, xnode)
+        Zout, F = np.full((B, self.n), np.nan), (np.full((B, self.n), np.nan) if residual else None)
+        rn, dn = np.full(B, np.nan), np.full(B, np.nan)
+        rhist = np.full((B, max(int(opts.rounds), 0) + 1), np.nan) if history else None
+        iters, nhalf, status = (np.zeros(B, dtype=np.int32) for _ in range(3))
+        self._chk(self.L.socp_newton_batch_blocks(self.h, B, _d(Z), *blocks, C.byref(opts), _d(Zout), _d(F), _d(rn), _d(dn),
+                                                  *(a.ctypes.data_as(_ip) for a in (iters, nhalf, status)), _d(rhist)))
+        return dict(z=Zout, f=F, rnorm=rn, dnorm=dn, iters=iters, nhalf=nhalf, status=status, rhist=rhist)
 
     # -- row grouping
     def group_batch_dev(self, B, n, ld, d_V, d_mask, atol, rtol, max_groups, d_label, d_leader, d_count, d_radius, d_summary):

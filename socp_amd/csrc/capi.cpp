@@ -2136,6 +2136,225 @@ int socp_branch_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
     });
 }
 
+/* ---- batched Newton polish ------------------------------------------------------------------- */
+
+namespace {
+// the workspace of socp_newton_batch_dev, in doubles from its start: F0 by row; the compact slots' points, residuals, right-hand
+// sides, block rows and Jacobians; the trial rows' points, residuals and block rows; the int pieces (whole doubles); then what the
+// variational Jacobian integrates in (models that have one)
+struct NewtonLayout {
+    size_t F0, cZ, cF, cR, cP, cT, cX, J, tZ, tF, tP, tT, tX, list, info, bcount, live, var, total;
+};
+
+NewtonLayout newton_layout(const socp_ctx *c, int B, int trials)
+{
+    const size_t b = (size_t)B, R = b * trials, nodes = (size_t)c->M + 1, n = c->n, stride = (size_t)c->nparams + 2, ints = (b + 1) / 2;
+    NewtonLayout w{};
+    size_t at = 0;
+    auto take = [&](size_t count) { const size_t here = at; at += (count + 1) & ~(size_t)1; return here; };      // 16-byte aligned pieces
+    w.F0 = take(b * n);
+    w.cZ = take(b * n);
+    w.cF = take(b * n);
+    w.cR = take(b * n);
+    w.cP = take(b * stride);
+    w.cT = take(b * nodes);
+    w.cX = take(b * nodes * c->S);
+    w.J = take(b * n * n);
+    w.tZ = take(R * n);
+    w.tF = take(R * n);
+    w.tP = take(R * stride);
+    w.tT = take(R * nodes);
+    w.tX = take(R * nodes * c->S);
+    w.list = take(ints);
+    w.info = take(ints);
+    w.bcount = take(((size_t)newton_scan_blocks(B) + 1) / 2);
+    w.live = take(2);
+    w.var = take(has_var(c) ? var_work_doubles(c, B) : 0);
+    w.total = at;
+    return w;
+}
+
+// the refusals all three forms share; *A: the options as they travel to the kernels
+int newton_args(socp_ctx *c, const char *who, int B, const socp_newton_options *o, NewtonArgs *A)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (!o) return fail(c, SOCP_ERR_ARG, w + ": null options");
+    if (o->jac < 0 || o->jac > 2) return fail(c, SOCP_ERR_ARG, w + ": jac must be 0 (forward differences), 1 (variational) or 2 (exact)");
+    if (o->trials < 1 || o->trials > 8) return fail(c, SOCP_ERR_ARG, w + ": 1 <= trials <= 8 is required");
+    if (o->rounds < 1) return fail(c, SOCP_ERR_ARG, w + ": rounds >= 1 is required");
+    if (!(o->ftol > 0.0)) return fail(c, SOCP_ERR_ARG, w + ": ftol > 0 is required");
+    if (!(o->xtol >= 0.0)) return fail(c, SOCP_ERR_ARG, w + ": xtol >= 0 is required");
+    if (o->jac == 1 && !has_var(c))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": this model has no variational equations (modelOrder 0): jac = 1 needs them");
+    if (o->jac == 2)
+        if (const int rc = exact_jacobian_args(c, who, B)) return rc;
+    if (!linsolve_fits(c->n, 1))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": too many unknowns for the batched linear solve (2 n + 1 doubles must fit 64 KiB of LDS)");
+    A->trials = o->trials; A->rounds = o->rounds; A->ftol = o->ftol; A->xtol = o->xtol;
+    return SOCP_OK;
+}
+
+NewtonWork newton_work(const socp_ctx *c, int B, int trials, void *d_work, double **J, double **var)
+{
+    const NewtonLayout w = newton_layout(c, B, trials);
+    double *wk = static_cast<double *>(d_work);
+    NewtonWork W;
+    W.F0 = wk + w.F0; W.cZ = wk + w.cZ; W.cF = wk + w.cF; W.cR = wk + w.cR; W.cP = wk + w.cP; W.cT = wk + w.cT; W.cX = wk + w.cX;
+    W.tZ = wk + w.tZ; W.tF = wk + w.tF; W.tP = wk + w.tP; W.tT = wk + w.tT; W.tX = wk + w.tX;
+    W.list = reinterpret_cast<int *>(wk + w.list); W.info = reinterpret_cast<int *>(wk + w.info);
+    W.bcount = reinterpret_cast<int *>(wk + w.bcount); W.live = reinterpret_cast<int *>(wk + w.live);
+    *J = wk + w.J; *var = wk + w.var;
+    return W;
+}
+
+// the start of a checked call: F0 = F(Z) with the rows' blocks, then every row's state and outputs
+int newton_begin(socp_ctx *c, int B, const double *d_Z, const NewtonArgs &A, const NewtonWork &W, const NewtonOut &O)
+{
+    HIP_TRY(c, run_residual(c, B, d_Z, W.F0));
+    c->n_launch += 1;
+    HIP_TRY(c, newton_start(c->stream, c->pb, B, c->n, A, d_Z, W, O));
+    return SOCP_OK;
+}
+
+// the compaction that begins a round: list and live
+int newton_begin_round(socp_ctx *c, int B, const NewtonWork &W, const NewtonOut &O)
+{
+    c->n_launch += 3;
+    HIP_TRY(c, newton_compact(c->stream, B, O.status, W));
+    return SOCP_OK;
+}
+
+// the rest of a round on `slots` compact slots (the _dev form: B; the host forms: the live count they read back)
+int newton_round(socp_ctx *c, int slots, const socp_newton_options *o, const NewtonArgs &A, const NewtonWork &W, const NewtonOut &O,
+                 double *wJ, double *wVar)
+{
+    const int n = c->n;
+    const ProblemDev own = c->pb;                                  // the rows' blocks: read by row, through the list
+    c->n_launch += 1;
+    HIP_TRY(c, newton_gather(c->stream, own, slots, n, W, O));
+    {
+        // the Jacobian at (y, F0) of the slots, each under its own block rows
+        BlocksGuard guard(c);
+        if (own.pp_params) c->pb.pp_params = W.cP;
+        if (own.pp_time) c->pb.pp_time = W.cT;
+        if (own.pp_xnode) c->pb.pp_xnode = W.cX;
+        if (o->jac == 0) {
+            const int r = socp_fd_jacobian_multi_dev(c, slots, W.cZ, W.cF, o->epsfcn, wJ, 1);
+            if (r != SOCP_OK) return r;
+        } else if (o->jac == 1) {
+            HIP_TRY(c, run_var_jacobian(c, slots, W.cZ, wVar, wJ));
+        } else {
+            const int r = exact_jacobian_launch(c, slots, W.cZ, wJ, nullptr);
+            if (r != SOCP_OK) return r;
+        }
+    }
+    // J delta = -F0 in place (reference order in both flavours); the trial points
+    c->n_launch += 2;
+    HIP_TRY(c, linsolve(c->stream, slots, n, 1, wJ, W.cR, W.info));
+    HIP_TRY(c, newton_trials(c->stream, own, slots, n, A.trials, W));
+    {
+        // ONE residual launch of slots x trials rows under the expanded block rows
+        BlocksGuard guard(c);
+        if (own.pp_params) c->pb.pp_params = W.tP;
+        if (own.pp_time) c->pb.pp_time = W.tT;
+        if (own.pp_xnode) c->pb.pp_xnode = W.tX;
+        HIP_TRY(c, run_residual(c, slots * A.trials, W.tZ, W.tF));
+    }
+    c->n_launch += 1;
+    HIP_TRY(c, newton_update(c->stream, slots, n, A, W, O));
+    return SOCP_OK;
+}
+}  // namespace
+
+size_t socp_newton_work_bytes(const socp_ctx *c, int B, const socp_newton_options *opt)
+{
+    if (!c || !c->has_problem || B < 0 || !opt || opt->trials < 1 || opt->trials > 8) return 0;
+    return sizeof(double) * newton_layout(c, B, opt->trials).total;
+}
+
+int socp_newton_batch_dev(socp_ctx *c, int B, const double *d_Z, const socp_newton_options *opt, void *d_work, size_t work_bytes,
+                          double *d_Zout, double *d_Fout, double *d_rnorm, double *d_dnorm, int *d_iters, int *d_nhalf, int *d_status,
+                          double *d_rhist)
+{
+    if (!c) return SOCP_ERR_ARG;
+    NewtonArgs A;
+    const int rc = newton_args(c, "newton_batch", B, opt, &A);
+    if (rc != SOCP_OK) return rc;
+    if (B > 0 && (!d_Z || !d_work || !d_Zout || !d_rnorm || !d_dnorm || !d_iters || !d_nhalf || !d_status))
+        return fail(c, SOCP_ERR_ARG, "newton_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    if (work_bytes < socp_newton_work_bytes(c, B, opt)) return fail(c, SOCP_ERR_ARG, "newton_batch: the workspace is smaller than socp_newton_work_bytes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const NewtonOut O{d_Zout, d_Fout, d_rnorm, d_dnorm, d_iters, d_nhalf, d_status, d_rhist};
+    double *wJ, *wVar;
+    const NewtonWork W = newton_work(c, B, A.trials, d_work, &wJ, &wVar);
+    if (const int r = newton_begin(c, B, d_Z, A, W, O)) return r;
+    for (int round = 0; round < A.rounds; round++) {
+        if (const int r = newton_begin_round(c, B, W, O)) return r;
+        if (const int r = newton_round(c, B, opt, A, W, O, wJ, wVar)) return r;
+    }
+    return SOCP_OK;
+}
+
+int socp_newton_batch(socp_ctx *c, int B, const double *Z, const socp_newton_options *opt, double *Zout, double *Fout, double *rnorm,
+                      double *dnorm, int *iters, int *nhalf, int *status, double *rhist)
+{
+    if (!c) return SOCP_ERR_ARG;
+    NewtonArgs A;
+    const int rc0 = newton_args(c, "newton_batch", B, opt, &A);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B > 0 && (!Z || !Zout || !rnorm || !dnorm || !iters || !nhalf || !status)) return fail(c, SOCP_ERR_ARG, "newton_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nZ = (size_t)B * c->n, nF = Fout ? nZ : 0, nH = rhist ? (size_t)B * ((size_t)A.rounds + 1) : 0;
+    const size_t bytes = socp_newton_work_bytes(c, B, opt);
+    double *d_Z;
+    HIP_TRY(c, c->s_var.reserve(bytes));
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (nZ + nF + 2 * (size_t)B + nH) + sizeof(int) * 3 * (size_t)B));
+    double *dY = c->s_out.as<double>(), *dF = dY + nZ, *dR = dF + nF, *dD = dR + B, *dH = dD + B;
+    int *dI = reinterpret_cast<int *>(dH + nH);                   // iters, nhalf, status: B each
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, d_Z));
+    const NewtonOut O{dY, Fout ? dF : nullptr, dR, dD, dI, dI + B, dI + 2 * (size_t)B, rhist ? dH : nullptr};
+    double *wJ, *wVar;
+    const NewtonWork W = newton_work(c, B, A.trials, c->s_var.p, &wJ, &wVar);
+    if (const int r = newton_begin(c, B, d_Z, A, W, O)) return r;
+    // after every compaction the number of unfinished rows comes back: the round runs on that many slots, 0 ends the call
+    for (int round = 0; round < A.rounds; round++) {
+        if (const int r = newton_begin_round(c, B, W, O)) return r;
+        int live = 0;
+        HIP_TRY(c, copy_down(c, &live, W.live, 1));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (live <= 0) break;
+        if (const int r = newton_round(c, live < B ? live : B, opt, A, W, O, wJ, wVar)) return r;
+    }
+    HIP_TRY(c, copy_down(c, Zout, dY, nZ));
+    if (Fout) HIP_TRY(c, copy_down(c, Fout, dF, nF));
+    HIP_TRY(c, copy_down(c, rnorm, dR, (size_t)B));
+    HIP_TRY(c, copy_down(c, dnorm, dD, (size_t)B));
+    if (rhist) HIP_TRY(c, copy_down(c, rhist, dH, nH));
+    HIP_TRY(c, copy_down(c, iters, O.iters, (size_t)B));
+    HIP_TRY(c, copy_down(c, nhalf, O.nhalf, (size_t)B));
+    HIP_TRY(c, copy_down(c, status, O.status, (size_t)B));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_newton_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time, const double *xnode,
+                             const socp_newton_options *opt, double *Zout, double *Fout, double *rnorm, double *dnorm, int *iters, int *nhalf,
+                             int *status, double *rhist)
+{
+    if (!c) return SOCP_ERR_ARG;
+    NewtonArgs A;
+    const int rc0 = newton_args(c, "newton_batch_blocks", B, opt, &A);
+    if (rc0 != SOCP_OK) return rc0;
+    if (const int rc = blocks_stride(c, "newton_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !Zout || !rnorm || !dnorm || !iters || !nhalf || !status)) return fail(c, SOCP_ERR_ARG, "newton_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_newton_batch(c, B, Z, opt, Zout, Fout, rnorm, dnorm, iters, nhalf, status, rhist); });
+}
+
 /* ---- row grouping --------------------------------------------------------------------------- */
 
 namespace {

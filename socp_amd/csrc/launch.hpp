@@ -152,6 +152,36 @@ hipError_t branch_assemble(hipStream_t st, int B, int n, const BranchArgs &A, in
                            const BranchState &S, const int *status, double *Mx, double *rhs);
 // the transitions of every unfinished row from the solutions X[B][n+1]
 hipError_t branch_update(hipStream_t st, int B, int n, const BranchArgs &A, const BranchState &S, const BranchOut &O, const double *X);
+// socp_newton_batch (kernels_newton.hip: one object without contraction, for both flavours).  The options travel as a kernel argument;
+// the row state is the caller's outputs (y = Zout, rn = rnorm, the counters, status) plus F0 in the workspace.
+struct NewtonArgs {
+    int trials, rounds;
+    double ftol, xtol;
+};
+struct NewtonOut {
+    double *Zout, *Fout, *rnorm, *dnorm;                          // Fout may be null
+    int *iters, *nhalf, *status;
+    double *rhist;                                                // may be null
+};
+// F0[B][n] by row.  By compact slot s: the accepted point cZ, its residual cF, the right-hand side and then the step cR ([B][n] each),
+// the slot's block rows cP / cT / cX, the elimination's info.  By trial row r = s trials + k: tZ, tF ([B trials][n]) and the block
+// rows tP / tT / tX.  list[s]: the row of slot s; bcount: the compaction's per-workgroup counts; live: the number of unfinished rows
+struct NewtonWork {
+    double *F0, *cZ, *cF, *cR, *cP, *cT, *cX, *tZ, *tF, *tP, *tT, *tX;
+    int *list, *info, *bcount, *live;
+};
+inline int newton_scan_blocks(int B) { return (B + 255) / 256; }  // workgroups of the compaction: 256 rows each
+// from F0 = F(Z): every output and the state of every row (BAD_START, CONVERGED with iters = 0, or unfinished); slot b <- row b
+hipError_t newton_start(hipStream_t st, const ProblemDev &pb, int B, int n, const NewtonArgs &A, const double *Z, const NewtonWork &W,
+                        const NewtonOut &O);
+// the unfinished rows (status == 0) in ascending order into list[0 .. live): three launches (count, scan, scatter), none waits on another
+hipError_t newton_compact(hipStream_t st, int B, const int *status, const NewtonWork &W);
+// slots 0 .. min(slots, live) - 1: y, F0, -F0 and the row's own block rows (those pb has) into the compact buffers
+hipError_t newton_gather(hipStream_t st, const ProblemDev &pb, int slots, int n, const NewtonWork &W, const NewtonOut &O);
+// every slot: tZ[s trials + k] = cZ[s] + fl(2^-k cR[s]) and the slot's block rows replicated
+hipError_t newton_trials(hipStream_t st, const ProblemDev &pb, int slots, int n, int trials, const NewtonWork &W);
+// slots 0 .. min(slots, live) - 1: the step's norm, the first trial that passes its bar, the accepted row scattered back, the end tests
+hipError_t newton_update(hipStream_t st, int slots, int n, const NewtonArgs &A, const NewtonWork &W, const NewtonOut &O);
 // socp_svd_batch_dev / socp_singular_batch (kernels_svd.hip, built once per flavour like kernels_tangent.hip).  One matrix per team
 // of L lanes, a lane per pair of rows; T teams per workgroup; the matrix, its n row norms and kSvdFlags doubles of flags in LDS
 constexpr int kSvdLdsBytes = 160 * 1024;             // the LDS of a CU: the most one workgroup can take

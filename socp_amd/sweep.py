@@ -517,6 +517,29 @@ def branch_local(ctx, args, local, lo, rank, params=None):
             "points_median": float(np.median(r["count"])) if len(conv) else None}
 
 
+NEWTON_STATUS_KEYS = ("running", "converged", "small_step", "stalled", "singular", "bad_start")      # by SOCP_NEWTON_* value
+
+
+def newton_local(ctx, args, local, lo, rank, params=None):
+    """--newton-out: damped Newton polish (socp_newton_batch) of this rank's CONVERGED chains, each with its own parameter block when
+    the chains have one: the roots hybrd stopped on at xtol are driven towards rounding level, and every row says how far it got.
+    --newton-jac 2 (the exact Jacobian) where the context has it, else 0.  Written to PATH.rank<r>.npz: index [k] = position of the
+    chain in the sweep's start table, z [k][n] (the polished unknowns), rnorm, dnorm, iters, nhalf, status [k].  Runs after the timed
+    solve.  Returns the record entry of this rank: the rows per status and the residual norms reached."""
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.newton_out)
+    jac = args.newton_jac if args.newton_jac is not None else (2 if ctx.has_exact_jacobian() else 0)
+    r = ctx.newton_batch(z, params=own, jac=jac, ftol=args.newton_ftol, xtol=args.newton_xtol, rounds=args.newton_rounds,
+                         trials=args.newton_trials, residual=False, history=False)
+    np.savez(path, index=index, z=r["z"], rnorm=r["rnorm"], dnorm=r["dnorm"], iters=r["iters"], nhalf=r["nhalf"], status=r["status"])
+    some = len(conv) > 0
+    entry = {"rows": int(len(conv)), "jac": int(jac)}
+    for value, key in enumerate(NEWTON_STATUS_KEYS):
+        entry[key] = int(np.sum(r["status"] == value))
+    entry.update(rnorm_median=float(np.median(r["rnorm"])) if some else None, rnorm_max=float(np.max(r["rnorm"])) if some else None,
+                 iters_median=float(np.median(r["iters"])) if some else None)
+    return entry
+
+
 def roots_global(ctx, args, table, n, with_cost=False, leader_blocks=None):
     """--roots-out: the distinct roots of the WHOLE sweep (socp_group_batch), on rank 0 from the gathered table [P][n+3] as it is:
     ld = n + 3, mask = (info == 1), grouping on the unknown vectors z only, greedy in start order.  Written to PATH.npz: label [P]
@@ -755,6 +778,17 @@ def main():
     ap.add_argument("--branch-h", type=float, default=0.1, metavar="H", help="with --branch-out: the first arclength step (the largest is 8 H)")
     ap.add_argument("--branch-points", type=int, default=64, metavar="C", help="with --branch-out: points kept per row, >= 2")
     ap.add_argument("--branch-rounds", type=int, default=400, metavar="R", help="with --branch-out: rounds, >= 1")
+    ap.add_argument("--newton-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank polishes the converged chains of its own block by damped Newton iteration in one "
+                         "batch (socp_newton_batch), with the chains' own parameter blocks; writes PATH.rank<r>.npz (index, z, rnorm, dnorm, "
+                         "iters, nhalf, status) and adds newton {rows, jac, the rows per status, rnorm_median, rnorm_max, iters_median} to "
+                         "the record.  Not with --model interceptor.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--newton-jac", type=int, default=None, metavar="J",
+                    help="with --newton-out: 0 forward differences, 1 variational, 2 exact; default 2 where the context has it, else 0")
+    ap.add_argument("--newton-ftol", type=float, default=1e-12, metavar="F", help="with --newton-out: CONVERGED when ||F||inf <= F")
+    ap.add_argument("--newton-xtol", type=float, default=0.0, metavar="X", help="with --newton-out: SMALL_STEP when the step is <= X ||z||inf; 0: off")
+    ap.add_argument("--newton-rounds", type=int, default=20, metavar="R", help="with --newton-out: rounds, >= 1")
+    ap.add_argument("--newton-trials", type=int, default=4, metavar="T", help="with --newton-out: step lengths tried per round, 1 .. 8")
     ap.add_argument("--events-refine", type=int, default=2, metavar="R",
                     help="with --events-out: false-position steps per event, 0 .. 8 (0: linear interpolation over the step)")
     args = ap.parse_args()
@@ -800,6 +834,15 @@ def main():
             ap.error("--branch-wtheta and --branch-h must be positive and finite")
         if args.branch_points < 2 or args.branch_rounds < 1:
             ap.error("--branch-points must be >= 2 and --branch-rounds >= 1")
+    if args.newton_out and args.model == "interceptor":
+        ap.error("--newton-out is implemented for the Goddard sweeps")
+    if args.newton_out:
+        if args.newton_jac is not None and args.newton_jac not in (0, 1, 2):
+            ap.error("--newton-jac must be 0, 1 or 2")
+        if not args.newton_ftol > 0 or not args.newton_xtol >= 0:
+            ap.error("--newton-ftol must be positive and --newton-xtol >= 0")
+        if args.newton_rounds < 1 or not 1 <= args.newton_trials <= 8:
+            ap.error("--newton-rounds must be >= 1 and --newton-trials 1 .. 8")
     if args.sing_out and args.model == "interceptor":
         ap.error("--sing-out is implemented for the Goddard sweeps")
     if args.sing_scale not in (0, 1):
@@ -920,6 +963,8 @@ def main():
         extra["singular" if rank == 0 else "singular_rank%d" % rank] = singular_local(ctx, args, local, lo_w, rank, blocks)
     if args.branch_out:
         extra["branch" if rank == 0 else "branch_rank%d" % rank] = branch_local(ctx, args, local, lo_w, rank, blocks)
+    if args.newton_out:
+        extra["newton" if rank == 0 else "newton_rank%d" % rank] = newton_local(ctx, args, local, lo_w, rank, blocks)
     if rank == 0:
         info = table[:, -2].astype(int)
         conv = table[info == 1, :n_unknown]
