@@ -387,6 +387,63 @@ int socp_extrema_batch_blocks(socp_ctx *ctx, int B, const double *Z, const doubl
                               const double *time, const double *xnode, int what,
                               double *vmin, double *vmax, double *tmin, double *tmax, int *count, int *nbad);
 
+/* Model-defined observables along a whole batch of unknown vectors: peak drag and when, burnt fuel, the clearance of an obstacle map,
+ * total intervention -- quantities that are neither a state, a control nor H -- reduced to their extrema and their integrals without
+ * the rows of a trace ever being stored.  [ext] The reference plots its trace files.
+ * Z[B][n] -> ymin, ymax, tmin, tmax, integral [B][M][NO], count[B][M], nbad[B][M];  tmin, tmax, integral and nbad may be NULL.
+ * NO = socp_ctx_observables, the names socp_ctx_observable_name(ctx, k), k = 0 .. NO-1 (NULL outside).
+ * ROWS.  Exactly those of socp_extrema_batch, that is the rows socp_trace_batch keeps with stride = 1 (same timeline, switching times,
+ * start state, per-problem blocks, integrator -- the fixed-step RK4 loop or the adaptive Dormand-Prince one): t, X and the aux pair of
+ * row k = 0 .. R-1;  count[b][i] = R.  A zero-length or backward segment has R = 1.
+ * VALUES.  y[0 .. NO) = the model's observe(P, aux0, aux1, t, X, u) with u what socp_eval_batch(SOCP_EVAL_CONTROL) returns at the row's
+ * (t, X) with the row's aux pair as sw, evaluated once per row.
+ * REDUCTION, per observable, sequential in row order, y the value and t the time of row k:
+ *   row 0:            ymin = ymax = y;  tmin = tmax = t;  I = +0.0
+ *   every later row:  if (y < ymin) { ymin = y; tmin = t; }   if (y > ymax) { ymax = y; tmax = t; }
+ *                     w = t_k - t_{k-1};  s = y_k + y_{k-1};  I = I + (0.5 w) s
+ * The comparisons are strict, as in socp_extrema_batch: the FIRST attainment wins; -0.0 never displaces +0.0; a NaN never displaces
+ * anything and a NaN in row 0 stays.  The integral is the composite trapezoid on the rows: 0.5 w is exact, every other operation
+ * rounds once (the throughput flavour may contract the last two); a value that is not finite ENTERS the sum -- the integral is then
+ * not finite, and nbad says so; a segment with one row has I = +0.0.  nbad[b][i] = the number of rows in which some observable is
+ * not finite.  An extremum inside a step is not interpolated.
+ * THE IN-TREE OBSERVABLES.  Plain IEEE operations, each rounding once, in the order written, products and sums left to right; sqrt
+ * and / correctly rounded; exp is exp_glibc.  X, u as above, p the packed parameters.
+ *   Goddard (both laws), NO = 6:
+ *     r         = sqrt(X0 X0 + X1 X1 + X2 X2)                 v = sqrt(X3 X3 + X4 X4 + X5 X5)          (the model's own r and v)
+ *     norm_u    = sqrt(u0 u0 + u1 u1 + u2 u2)
+ *     drag      = KD v v E,   E = exp(-kr (r - 1))            (the density factor as the right-hand side forms it)
+ *     drag_acc  = drag / X6
+ *     fuel_rate = b norm_u                                    (its integral is the burnt mass: row 6 of the right-hand side)
+ *   vtolUAV, NO = 3:
+ *     speed     = sqrt(X3 X3 + X4 X4 + X5 X5)                 norm_u as above
+ *     clearance = the smallest level of any obstacle of the context's map (socp_ctx_set_map), negative inside one:
+ *       cl = +inf;  for each obstacle in table order:  level -> if (level < cl) cl = level;
+ *       box (type 1):        m = |X0 - x| - radx;  b = |X1 - y| - rady;  c = |X2 - z| - radz;  if (b > m) m = b;  if (c > m) m = c;  level = m
+ *       ellipsoid (type 0):  hx = X0 - x, hy = X1 - y, hz = X2 - z;  d = sqrt(hx hx + hy hy + hz hz);
+ *                            level = d - d / sqrt(hx hx / radx / radx + hy hy / rady / rady + hz hz / radz / radz)
+ *     (the three-term radius of the map's value, not the two-term one of its gradient).  A NaN level -- the centre of an ellipsoid --
+ *     never displaces anything; an empty map gives +inf (which is not finite: every row then counts in nbad); any other type is skipped.  Never contracted: both flavours give the same bits.
+ *   doubleIntegrator, NO = 1:  norm_u.        covid19, NO = 1:  u = u0  (its integral is the total intervention).
+ * The throughput flavour evaluates the same texts with contraction on (clearance excepted).
+ * SOCP_ERR_ARG: no problem set, B < 0, B > 0 with Z, ymin, ymax or count NULL, _blocks with params and param_stride != nparams + 2;
+ * B == 0: SOCP_OK without a launch; SOCP_ERR_UNSUPPORTED ("no observe entry"): the model's launch table has no observe entry
+ * (socp_ctx_has_observe says 0): a model without the trait, or with its own ComputeTraj (the interceptor).  An error writes nothing
+ * and leaves the context unchanged.
+ * One launch, which writes nothing but these arrays; socp_ctx_counters advances by B M trajectories and one launch.  The _dev form
+ * takes device pointers, enqueues on the context's stream and neither copies nor synchronises; the host forms stage through that
+ * stream and return when the results are in the caller's arrays.  _blocks: per-row blocks like socp_extrema_batch_blocks (any of
+ * params / time / xnode may be NULL); the context's own blocks are restored afterwards. */
+int socp_ctx_has_observe(const socp_ctx *ctx);               /* 1 / 0 */
+int socp_ctx_observables(const socp_ctx *ctx);               /* NO; 0: no observe entry  (< 0: error) */
+const char *socp_ctx_observable_name(const socp_ctx *ctx, int k);
+int socp_observe_batch_dev(socp_ctx *ctx, int B, const double *d_Z, double *d_ymin, double *d_ymax, double *d_tmin, double *d_tmax,
+                           double *d_integral, int *d_count, int *d_nbad);
+int socp_observe_batch(socp_ctx *ctx, int B, const double *Z, double *ymin, double *ymax, double *tmin, double *tmax,
+                       double *integral, int *count, int *nbad);
+int socp_observe_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride,
+                              const double *time, const double *xnode, double *ymin, double *ymax, double *tmin, double *tmax,
+                              double *integral, int *count, int *nbad);
+
 /* Conjugate-time test of a whole batch of unknown vectors: the Jacobi fields along every extremal.  [ext] The reference never
  * computes this; indirect shooting finds extremals, not minima, and the standard instrument for telling them apart (cotcot, HamPath)
  * is J(t) = dx(t)/dp(t0), a d x d matrix with J(t0) = 0: the first time det J(t) changes sign is the first conjugate time, and a

@@ -42,6 +42,18 @@
  * socp_ctx_has_exact_jacobian says 0 and the call returns SOCP_ERR_UNSUPPORTED.  A plugin built against an older launch table
  * (ABI <= 12) is refused at registration: rebuild it.
  *
+ * Launch-table ABI 14 adds the batched observables launcher (socp_observe_batch, socp_hip.h) and its optional trait
+ *   static constexpr int kObservables = NO;                         (1 <= NO <= 16)
+ *   static constexpr const char *kObservableNames[NO] = {...};
+ *   __device__ static void observe(const socp::ModelParams &P, double sw0, double sw1, double t, const double (&X)[S],
+ *                                  const double (&u)[NU], double (&y)[NO]);
+ * scalars of one row of a trajectory -- a drag, a clearance, a norm -- whose extrema and trapezoid integrals the library reduces
+ * over the rows of every segment.  u is control_only at the row, evaluated once by the kernel with the row's aux pair; plain IEEE
+ * operations if a CPU restatement is to match bit for bit.  A model without the trait, or with its own ComputeTraj, has no observe
+ * entry: socp_ctx_has_observe says 0 and socp_observe_batch returns SOCP_ERR_UNSUPPORTED (tests/plugin/osc1d_observe_plugin.hip
+ * has the trait, the other example plugins do not).  A plugin built against an older launch table (ABI <= 13) is refused at
+ * registration: rebuild it.
+ *
  * Model ids below SOCP_PLUGIN_ID_MIN are reserved for in-tree models.
  */
 #ifndef SOCP_PLUGIN_H_

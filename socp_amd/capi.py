@@ -170,6 +170,13 @@ def lib():
         L.socp_extrema_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
         L.socp_extrema_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip]
         L.socp_extrema_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip]
+        L.socp_ctx_has_observe.argtypes = [_vp]
+        L.socp_ctx_observables.argtypes = [_vp]
+        L.socp_ctx_observable_name.argtypes = [_vp, C.c_int]
+        L.socp_ctx_observable_name.restype = C.c_char_p
+        L.socp_observe_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.socp_observe_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
+        L.socp_observe_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
         L.socp_events_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_events_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _ip, _ip, _dp]
         L.socp_events_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, _dp, _ip,
@@ -728,6 +735,41 @@ class Context:
                                                    int(what), _d(out["vmin"]), _d(out["vmax"]), _d(out["tmin"]), _d(out["tmax"]),
                                                    count.ctypes.data_as(_ip), nbad.ctypes.data_as(_ip)))
         out.update(count=count, nbad=nbad, channels=self.extrema_channels())
+        return out
+
+    # -- batched observables
+    def has_observe(self):
+        """Whether this model's launch table has an observe entry (socp_ctx_has_observe): a model with the observables trait and
+        without its own ComputeTraj."""
+        return self.L.socp_ctx_has_observe(self.h) == 1
+
+    def observable_names(self):
+        """The names of the model's observables, in their order (socp_ctx_observables / socp_ctx_observable_name); [] without the
+        entry."""
+        return [self.L.socp_ctx_observable_name(self.h, k).decode() for k in range(max(0, self.L.socp_ctx_observables(self.h)))]
+
+    def observe_batch_dev(self, B, d_Z, d_ymin, d_ymax, d_tmin, d_tmax, d_integral, d_count, d_nbad=None):
+        """Device pointers (ints; d_tmin / d_tmax / d_integral / d_nbad may be None); enqueue only, no copy, no synchronise
+        (socp_observe_batch_dev)."""
+        self._chk(self.L.socp_observe_batch_dev(self.h, int(B), _vp(d_Z), _vp(d_ymin), _vp(d_ymax), _vp(d_tmin), _vp(d_tmax),
+                                                _vp(d_integral), _vp(d_count), _vp(d_nbad)))
+
+    def observe_batch(self, Z, blocks=None):
+        """Extrema and trapezoid integrals of the model's observables over the rows trace_batch keeps with stride = 1, in one launch
+        that stores no row (include/socp_hip.h): returns dict(ymin, ymax, tmin, tmax, integral [B][M][NO], count[B][M], nbad[B][M],
+        names) -- per segment and observable (observable_names) the smallest and the largest value, the time of the row that first
+        attains it and the integral over the segment; the number of rows and the number of rows with a value that is not finite.
+        blocks = (params, time, xnode): per-row blocks as in residual_batch_blocks, host arrays or None."""
+        Z = _f64(Z).reshape(-1, self.n)
+        names = self.observable_names()
+        B, NO = Z.shape[0], len(names)
+        out = {k: np.full((B, self.M, NO), np.nan) for k in ("ymin", "ymax", "tmin", "tmax", "integral")}
+        count = np.zeros((B, self.M), dtype=np.int32)
+        nbad = np.zeros((B, self.M), dtype=np.int32)
+        self._chk(self.L.socp_observe_batch_blocks(self.h, B, _d(Z), *_block_args(B, *(blocks if blocks is not None else (None, None, None))),
+                                                   _d(out["ymin"]), _d(out["ymax"]), _d(out["tmin"]), _d(out["tmax"]), _d(out["integral"]),
+                                                   count.ctypes.data_as(_ip), nbad.ctypes.data_as(_ip)))
+        out.update(count=count, nbad=nbad, names=names)
         return out
 
     # -- batched events

@@ -52,6 +52,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.cost = &goddard_by_problem<&plugin::cost<GodSmooth>, &plugin::cost<God>>;
         t.move = &goddard_by_problem<&plugin::move<GodSmooth>, &plugin::move<God>>;
         t.extrema = &goddard_by_problem<&plugin::extrema<GodSmooth>, &plugin::extrema<God>>;
+        t.observe = &goddard_by_problem<&plugin::observe<GodSmooth>, &plugin::observe<God>>;
         t.events = &goddard_by_problem<&plugin::events<GodSmooth>, &plugin::events<God>>;
         t.jacobi = &goddard_by_problem<&plugin::jacobi<GodSmooth>, &plugin::jacobi<God>>;
         t.trace_fill = &goddard_trace_fill<God, GodSmooth>;

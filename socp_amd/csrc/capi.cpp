@@ -1044,6 +1044,82 @@ int socp_extrema_batch_blocks(socp_ctx *c, int B, const double *Z, const double 
                        [&] { return socp_extrema_batch(c, B, Z, what, vmin, vmax, tmin, tmax, count, nbad); });
 }
 
+/* ---- batched observables ------------------------------------------------------------------- */
+
+int socp_ctx_has_observe(const socp_ctx *c) { return c ? (table_of(c)->observe ? 1 : 0) : SOCP_ERR_ARG; }
+
+int socp_ctx_observables(const socp_ctx *c) { return c ? (table_of(c)->observe ? table_of(c)->observables : 0) : SOCP_ERR_ARG; }
+
+const char *socp_ctx_observable_name(const socp_ctx *c, int k)
+{
+    if (!c || k < 0 || k >= socp_ctx_observables(c) || !table_of(c)->observable_names) return nullptr;
+    return table_of(c)->observable_names[k];
+}
+
+namespace {
+int observe_args(socp_ctx *c, const char *who, int B, const void *Z, const void *ymin, const void *ymax, const void *count)
+{
+    if (const int rc = args_head(c, who, B >= 0, "B >= 0 is required")) return rc;
+    if (B > 0 && (!Z || !ymin || !ymax || !count)) return fail(c, SOCP_ERR_ARG, std::string(who) + ": null argument");
+    return args_tail(c, who, table_of(c)->observe != nullptr && table_of(c)->observables > 0, "observe entry", nullptr);
+}
+}  // namespace
+
+int socp_observe_batch_dev(socp_ctx *c, int B, const double *d_Z, double *d_ymin, double *d_ymax, double *d_tmin, double *d_tmax,
+                           double *d_integral, int *d_count, int *d_nbad)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc = observe_args(c, "observe_batch", B, d_Z, d_ymin, d_ymax, d_count);
+    if (rc != SOCP_OK) return rc;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_traj += (long long)B * c->M; c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->observe(c->stream, c->P, c->pb, B, d_Z, d_ymin, d_ymax, d_tmin, d_tmax, d_integral, d_count, d_nbad));
+    return SOCP_OK;
+}
+
+int socp_observe_batch(socp_ctx *c, int B, const double *Z, double *ymin, double *ymax, double *tmin, double *tmax, double *integral,
+                       int *count, int *nbad)
+{
+    if (!c) return SOCP_ERR_ARG;
+    const int rc0 = observe_args(c, "observe_batch", B, Z, ymin, ymax, count);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t segs = (size_t)B * c->M, nV = segs * table_of(c)->observables;
+    double *d_Z;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, (size_t)B * c->n, d_Z));
+    // the launch writes every element of every array it is given: nothing travels up but Z
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * 5 * nV));
+    HIP_TRY(c, c->s_var.reserve(sizeof(int) * 2 * segs));
+    double *dLo = c->s_out.as<double>(), *dHi = dLo + nV, *dTa = dHi + nV, *dTb = dTa + nV, *dI = dTb + nV;
+    int *dC = c->s_var.as<int>(), *dN = dC + segs;
+    const int rc = socp_observe_batch_dev(c, B, d_Z, dLo, dHi, tmin ? dTa : nullptr, tmax ? dTb : nullptr, integral ? dI : nullptr, dC,
+                                          nbad ? dN : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, ymin, dLo, nV));
+    HIP_TRY(c, copy_down(c, ymax, dHi, nV));
+    if (tmin) HIP_TRY(c, copy_down(c, tmin, dTa, nV));
+    if (tmax) HIP_TRY(c, copy_down(c, tmax, dTb, nV));
+    if (integral) HIP_TRY(c, copy_down(c, integral, dI, nV));
+    HIP_TRY(c, copy_down(c, count, dC, segs));
+    if (nbad) HIP_TRY(c, copy_down(c, nbad, dN, segs));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_observe_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                              const double *xnode, double *ymin, double *ymax, double *tmin, double *tmax, double *integral, int *count,
+                              int *nbad)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = observe_args(c, "observe_batch_blocks", B, Z, ymin, ymax, count)) return rc;
+    if (const int rc = blocks_stride(c, "observe_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_observe_batch(c, B, Z, ymin, ymax, tmin, tmax, integral, count, nbad); });
+}
+
 /* ---- batched Move(tf) / re-grid ------------------------------------------------------------- */
 
 namespace {

@@ -36,6 +36,11 @@ template <class M> struct has_switching_state_jac<M, std::void_t<decltype(&M::sw
 // Absent = 0 channels: the model's launch table has no events entry.
 template <class M, class = void> struct event_channels : std::integral_constant<int, 0> {};
 template <class M> struct event_channels<M, std::void_t<decltype(M::kEventChannels)>> : std::integral_constant<int, M::kEventChannels> {};
+// optional trait observables (socp_observe_batch): kObservables scalars of a row the model defines, with their names,
+//   observe(P, sw0, sw1, t, X, u, y)   -- u the row's control_only (models_exact.hpp).
+// Absent = 0: the model's launch table has no observe entry.
+template <class M, class = void> struct observables : std::integral_constant<int, 0> {};
+template <class M> struct observables<M, std::void_t<decltype(M::kObservables)>> : std::integral_constant<int, M::kObservables> {};
 template <class M, class = void> struct has_custom_final : std::false_type {};
 template <class M> struct has_custom_final<M, std::void_t<decltype(M::kCustomFinal)>> : std::bool_constant<M::kCustomFinal> {};
 
@@ -1060,6 +1065,119 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) vo
                                                              double *__restrict__ tmax, int *__restrict__ count, int *__restrict__ nbad)
 {
     extrema_lane<Mdl, INTEG, PERPROB, false>(P, pb, B, Z, 0, vmin, vmax, tmin, tmax, count, nbad);
+}
+
+// ---------------------------------------------------------------------------------------------
+// K_observe: extrema and integrals of the model's observables over the rows K_trace keeps with stride = 1 (socp_observe_batch).
+// Z[B][n] -> ymin, ymax, tmin, tmax, integral [B][M][NO], count[B][M], nbad[B][M];  NO = the model's kObservables.  One lane =
+// (row, segment), T = b M + i, and the loops and step hooks of segment_extrema, so the rows observed are the rows traced.  On
+// every row the hook evaluates control_only once at the row's (t, X) with the row's aux pair -- what K_trace_fill evaluates --
+// hands (t, X, u) to the model's observe() and updates, per observable y, in registers beside the state:
+//     row 0:  ymin = ymax = y, tmin = tmax = t, I = +0.0
+//     later:  if (y < ymin) { ymin = y; tmin = t; }  if (y > ymax) { ymax = y; tmax = t; }
+//             w = t - t_prev;  s = y + y_prev;  I = I + (0.5 w) s            (composite trapezoid, one rounding per operation)
+// (strict comparisons, as in segment_extrema; a value that is not finite enters the sum).  nbad = rows in which an observable
+// is not finite.  The NO-wide results leave once, at the end; every store site is ONE block under ONE computed predicate (see
+// the note in segment_residual).
+// ---------------------------------------------------------------------------------------------
+template <class Mdl, int INTEG, class ZRead>
+__device__ __forceinline__ void segment_observe(const ModelParams &P, const ProblemDev &pb, const ZRead &z, int i,
+                                                double *__restrict__ ymin, double *__restrict__ ymax, double *__restrict__ tmin,
+                                                double *__restrict__ tmax, double *__restrict__ integral, int *__restrict__ count,
+                                                int *__restrict__ nbad)
+{
+    static_assert(!has_custom_traj<Mdl>::value, "the observables of a model with its own ComputeTraj need a definition of their own");
+    constexpr int S = Mdl::S, NU = Mdl::NU, NO = observables<Mdl>::value;
+    const Timeline<ZRead> tl{pb, z};
+    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
+    double sw0 = tl.template switching_time<Mdl>(P.sw0, pb.sw_node0), sw1 = tl.template switching_time<Mdl>(P.sw1, pb.sw_node1);
+    double X[S];
+    segment_start(z, S * i, X);
+
+    double lo[NO], hi[NO], tlo[NO], thi[NO], sum[NO], prev[NO];
+#pragma unroll
+    for (int c = 0; c < NO; c++) lo[c] = hi[c] = tlo[c] = thi[c] = sum[c] = prev[c] = 0.0;     // row 0 overwrites all but the sum
+    double tprev = 0.0;
+    int rows = 0, bad = 0;
+    auto finite = [](double v) { return fabs(v) <= 1.7976931348623157e308; };      // false for NaN and the infinities
+    auto row = [&](double t, const double (&Xr)[S], double b0, double b1) {
+        double u3[3], u[NU], y[NO];
+        Mdl::control_only(P, b0, b1, t, Xr, u3);
+#pragma unroll
+        for (int k = 0; k < NU; k++) u[k] = u3[k];
+        Mdl::observe(P, b0, b1, t, Xr, u, y);
+        const bool first = rows == 0;
+        const double hw = 0.5 * (t - tprev);
+        bool ok = true;
+#pragma unroll
+        for (int c = 0; c < NO; c++) {
+            ok = ok && finite(y[c]);
+            const bool dn = first || y[c] < lo[c], up = first || y[c] > hi[c];
+            lo[c] = dn ? y[c] : lo[c];
+            tlo[c] = dn ? t : tlo[c];
+            hi[c] = up ? y[c] : hi[c];
+            thi[c] = up ? t : thi[c];
+            const double s = y[c] + prev[c];
+            const double next = sum[c] + hw * s;
+            sum[c] = first ? 0.0 : next;
+            prev[c] = y[c];
+        }
+        tprev = t;
+        bad += ok ? 0 : 1;
+        rows++;
+    };
+
+    row(t1, X, sw0, sw1);                                            // row 0 = (t1, X_start)
+    auto after = [&](double t, const double (&Xr)[S]) { row(t, Xr, sw0, sw1); };
+    if constexpr (INTEG == 1) Lane<Mdl>::integrate_dopri5(P, sw0, sw1, t1, t2, X, NoStepHook(), after);
+    else Lane<Mdl>::integrate(P, sw0, sw1, t1, t2, X, after);
+
+#pragma unroll
+    for (int c = 0; c < NO; c++) { ymin[c] = lo[c]; ymax[c] = hi[c]; }
+    const bool sa = tmin != nullptr;
+    if (sa) {
+#pragma unroll
+        for (int c = 0; c < NO; c++) tmin[c] = tlo[c];
+    }
+    const bool sb = tmax != nullptr;
+    if (sb) {
+#pragma unroll
+        for (int c = 0; c < NO; c++) tmax[c] = thi[c];
+    }
+    const bool si = integral != nullptr;
+    if (si) {
+#pragma unroll
+        for (int c = 0; c < NO; c++) integral[c] = sum[c];
+    }
+    *count = rows;
+    const bool sn = nbad != nullptr;
+    if (sn) *nbad = bad;
+}
+
+template <class Mdl, int WPE, int INTEG = 0, bool PERPROB = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) void observe_lane_kernel(ModelParams P, ProblemDev pb, int B,
+                                                             const double *__restrict__ Z, double *__restrict__ ymin,
+                                                             double *__restrict__ ymax, double *__restrict__ tmin,
+                                                             double *__restrict__ tmax, double *__restrict__ integral,
+                                                             int *__restrict__ count, int *__restrict__ nbad)
+{
+    constexpr int NO = observables<Mdl>::value;
+    const long T = (long)blockIdx.x * 64 + threadIdx.x;              // = b * M + i: index into count / nbad, span of the five arrays
+    if (T >= (long)B * pb.M) return;
+    const long b = T / pb.M;
+    const int i = (int)(T - b * pb.M);
+    const double *zr = Z + b * pb.n;
+    auto z = [=](int k) -> double { return zr[k]; };
+    double *ta = tmin ? tmin + T * NO : nullptr, *tb = tmax ? tmax + T * NO : nullptr, *in = integral ? integral + T * NO : nullptr;
+    int *nb = nbad ? nbad + T : nullptr;
+    if constexpr (PERPROB) {
+        ModelParams Pq = P;
+        ProblemDev pq = pb;
+        load_problem_block(pb, b, Pq, pq);
+        segment_observe<Mdl, INTEG>(Pq, pq, z, i, ymin + T * NO, ymax + T * NO, ta, tb, in, count + T, nb);
+    } else {
+        segment_observe<Mdl, INTEG>(P, pb, z, i, ymin + T * NO, ymax + T * NO, ta, tb, in, count + T, nb);
+    }
 }
 
 // K_trace_fill: u and H of every stored row, in place; one lane = (row b, segment i, kept row k), the rows at or beyond

@@ -39,12 +39,13 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 13;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 14;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
                                    // kPluginAbi = 12: batched extrema launcher
                                    // kPluginAbi = 13: batched exact shooting-Jacobian launcher
+                                   // kPluginAbi = 14: batched observables launcher
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -93,6 +94,13 @@ struct ModelLaunchers {
     // hamiltonian_t, switching_fn_t, or has a switching_state hook, custom final rows or its own ComputeTraj (plugin_impl.hpp).  The
     // in-tree models' entries live in kernels_exact_jacobian.hip, one object without contraction that both flavours' tables point to
     hipError_t (*exact_jacobian)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *);
+    // batched observables (socp_observe_batch): Z[B][n] -> ymin, ymax, tmin, tmax, integral [B][M][NO] (tmin, tmax, integral may be
+    // null), count[B][M], nbad[B][M] (may be null), NO = observables; both integrators, one launch.  observables = 0 and null
+    // entries: the model has no observables (no kObservables / kObservableNames / observe trait) or its own ComputeTraj
+    int observables;
+    const char *const *observable_names;
+    hipError_t (*observe)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *, double *, double *,
+                          double *, int *, int *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)

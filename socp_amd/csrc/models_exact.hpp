@@ -441,6 +441,27 @@ struct GoddardExactT {
         const double norm_pv = sqrt(p_vx*p_vx + p_vy*p_vy + p_vz*p_vz);
         return P.p[GP_MU1] - P.p[GP_B]*p_mass - P.p[GP_C] / mass*norm_pv;
     }
+
+    // observables (socp_observe_batch, include/socp_hip.h has the definitions): plain IEEE operations, one rounding each, in the
+    // order written; r, v and E carry the bits `common` gives them (sqrt_in_range is the correctly rounded sqrt where it applies).
+    // tests/observe_reference.py restates them in numpy bit for bit.
+    static constexpr int kObservables = 6;
+    static constexpr const char *kObservableNames[kObservables] = {"r", "v", "norm_u", "drag", "drag_acc", "fuel_rate"};
+    __device__ static __forceinline__ void observe(const ModelParams &P, double, double, double, const double (&X)[S], const double (&u)[NU],
+                                                  double (&y)[kObservables])
+    {
+        const double r = sqrt(X[0]*X[0] + X[1]*X[1] + X[2]*X[2]);
+        const double v = sqrt(X[3]*X[3] + X[4]*X[4] + X[5]*X[5]);
+        const double E = exp_glibc(-P.p[GP_KR]*(r - 1));
+        const double norm_u = sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
+        const double drag = P.p[GP_KD]*v*v*E;
+        y[0] = r;
+        y[1] = v;
+        y[2] = norm_u;
+        y[3] = drag;
+        y[4] = drag / X[6];
+        y[5] = P.p[GP_B]*norm_u;
+    }
 };
 
 using GoddardExact = GoddardExactT<false>;        // general law (any mu2)
@@ -511,6 +532,15 @@ struct DIntExact {
         const double a_max = P.p[DP_AMAX];
         const double u0 = -X[9] / a_max, u1 = -X[10] / a_max, u2 = -X[11] / a_max;
         return sqrt(u0*u0 + u1*u1 + u2*u2);
+    }
+
+    // observable (socp_observe_batch): the norm of the applied control
+    static constexpr int kObservables = 1;
+    static constexpr const char *kObservableNames[kObservables] = {"norm_u"};
+    __device__ static __forceinline__ void observe(const ModelParams &, double, double, double, const double (&)[S], const double (&u)[NU],
+                                                  double (&y)[kObservables])
+    {
+        y[0] = sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
     }
 
     // doubleIntegrator.cpp:264-300, isJac == 0
@@ -589,6 +619,15 @@ struct CovidExact {
     {
         const double u = (X[5] - X[4])*X[0]*X[2] / P.p[CP_TINF] / P.p[CP_N] * P.p[CP_R0];
         return chan == 0 ? u : X[2];
+    }
+
+    // observable (socp_observe_batch): the control; its integral is the total intervention
+    static constexpr int kObservables = 1;
+    static constexpr const char *kObservableNames[kObservables] = {"u"};
+    __device__ static __forceinline__ void observe(const ModelParams &, double, double, double, const double (&)[S], const double (&u)[NU],
+                                                  double (&y)[kObservables])
+    {
+        y[0] = u[0];
     }
 
     // covid19.cpp:53-95.  All ten divisions are by the model constants Tinf, Tinc, N: shared denominators (see Den).

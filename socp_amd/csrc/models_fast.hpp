@@ -167,6 +167,14 @@ struct GoddardFastT {
     {
         return GoddardExactT<SMOOTH>::event_fn(P, sw0, sw1, t, X, chan);
     }
+    // the observables of the reference-order flavour (one evaluation per row: nothing to restructure), contraction on
+    static constexpr int kObservables = GoddardExactT<SMOOTH>::kObservables;
+    static constexpr const char *const (&kObservableNames)[kObservables] = GoddardExactT<SMOOTH>::kObservableNames;
+    __device__ static __forceinline__ void observe(const ModelParams &P, double sw0, double sw1, double t, const double (&X)[S],
+                                                  const double (&u)[NU], double (&y)[kObservables])
+    {
+        GoddardExactT<SMOOTH>::observe(P, sw0, sw1, t, X, u, y);
+    }
 };
 
 using GoddardFast = GoddardFastT<false>;

@@ -78,6 +78,44 @@ struct VtolT {
         }
     }
 
+    // ---- observables (socp_observe_batch, include/socp_hip.h has the definitions) ---------------------------
+    // clearance: the smallest level of any obstacle of the table, negative inside one.  Plain IEEE operations in the order written,
+    // never contracted (the pragma), so both flavours give the same bits; no tanh.  A NaN level (an ellipsoid's centre) never
+    // displaces the running minimum; an empty table gives +inf.  The table is read like map_exact reads it.
+    __device__ static __forceinline__ double clearance(const ModelParams &P, double px, double py, double pz)
+    {
+#pragma clang fp contract(off)
+        double cl = __builtin_inf();
+        const MapTable tab = map_table(P);
+        for (int i = 0; i < P.n_map; i++) {
+            const MapTable o = tab + (long)i * kMapStride;
+            const double type = o[0], x = o[1], y = o[2], z = o[3], radx = o[4], rady = o[5], radz = o[6];
+            if (type == 0) {
+                const double hx = px - x, hy = py - y, hz = pz - z;
+                const double d = sqrt(hx*hx + hy*hy + hz*hz);
+                const double level = d - d / sqrt(hx*hx / radx / radx + hy*hy / rady / rady + hz*hz / radz / radz);
+                if (level < cl) cl = level;
+            } else if (type == 1) {
+                const double dx = px - x, dy = py - y, dz = pz - z;
+                double m = fabs(dx) - radx;
+                const double b = fabs(dy) - rady, c = fabs(dz) - radz;
+                if (b > m) m = b;
+                if (c > m) m = c;
+                if (m < cl) cl = m;
+            }
+        }
+        return cl;
+    }
+    static constexpr int kObservables = 3;
+    static constexpr const char *kObservableNames[kObservables] = {"speed", "norm_u", "clearance"};
+    __device__ static __forceinline__ void observe(const ModelParams &P, double, double, double, const double (&X)[S], const double (&u)[NU],
+                                                  double (&y)[kObservables])
+    {
+        y[0] = sqrt(X[3]*X[3] + X[4]*X[4] + X[5]*X[5]);
+        y[1] = sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
+        y[2] = clearance(P, X[0], X[1], X[2]);
+    }
+
     // ---- reference-order map (obstacle.cpp:186-319) ------------------------------------------------------
     // WANT_F / WANT_G: the penalty value (Function) and / or its gradient (Gradient), as the reference's two loops
     template <bool WANT_F, bool WANT_G>

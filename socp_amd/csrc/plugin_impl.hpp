@@ -32,6 +32,14 @@
 //       static constexpr int kEventChannels = ...;                                        // 1 .. 16
 //       __device__ static double event_fn(const socp::ModelParams &P, double sw0, double sw1, double t,
 //                                         const double (&X)[S], int chan);
+//       // OPTIONAL -- observables (socp_observe_batch): scalars of a row whose extrema and integrals the library reduces along the
+//       // trajectories -- drag, clearance, a norm.  u is control_only at the row, evaluated once by the kernel with the row's aux
+//       // pair.  Plain IEEE operations if a CPU restatement is to match bit for bit.  A model with its own ComputeTraj does not
+//       // get the entry.
+//       static constexpr int kObservables = ...;                                          // 1 .. 16
+//       static constexpr const char *kObservableNames[kObservables] = {...};
+//       __device__ static void observe(const socp::ModelParams &P, double sw0, double sw1, double t,
+//                                      const double (&X)[S], const double (&u)[NU], double (&y)[kObservables]);
 //       // OPTIONAL -- variational equations, for classes with modelOrder = 1 (hybrj; model.hpp:104-120,149-183):
 //       __device__ static double aug_rhs(const socp::ModelParams &P, double t, int e, const double *Y);
 //                 // element e of Model(t, Y, isJac = 1), Y = [X(S) ; R(S x S)], R[k][i] at Y[S (k+1) + i]  
@@ -57,7 +65,7 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, batched exact shooting Jacobian when it has hamiltonian_t and switching_fn_t too, batched extrema, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, batched exact shooting Jacobian when it has hamiltonian_t and switching_fn_t too, batched extrema, batched observables when the model has the trait, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
 #include "fields.hpp"
@@ -183,6 +191,16 @@ hipError_t extrema(hipStream_t st, const ModelParams &P, const ProblemDev &pb, i
     if (what < 0 || what > 7) return hipErrorInvalidValue;
     if (what == 0) SOCP_PLUGIN_LAUNCH_PB(extrema_state_lane_kernel, blocks_for((long)B * pb.M), st, P, pb, B, Z, vmin, vmax, tmin, tmax, count, nbad);
     else SOCP_PLUGIN_LAUNCH_PB(extrema_lane_kernel, blocks_for((long)B * pb.M), st, P, pb, B, Z, what, vmin, vmax, tmin, tmax, count, nbad);
+    return hipGetLastError();
+}
+
+// batched observables: one lane per (row, segment) like the extrema, both integrators
+template <class Mdl>
+hipError_t observe(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *ymin, double *ymax,
+                   double *tmin, double *tmax, double *integral, int *count, int *nbad)
+{
+    if (B <= 0) return hipSuccess;
+    SOCP_PLUGIN_LAUNCH_PB(observe_lane_kernel, blocks_for((long)B * pb.M), st, P, pb, B, Z, ymin, ymax, tmin, tmax, integral, count, nbad);
     return hipGetLastError();
 }
 
@@ -329,6 +347,11 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     if constexpr (event_channels<Mdl>::value > 0 && !has_custom_traj<Mdl>::value) {
         static_assert(event_channels<Mdl>::value <= 16, "a watch's channel travels in four bits");
         t.event_channels = event_channels<Mdl>::value; t.events = &events<Mdl>;
+    }
+    if constexpr (observables<Mdl>::value > 0 && !has_custom_traj<Mdl>::value) {
+        static_assert(observables<Mdl>::value <= 16, "at most 16 observables: their running pairs and sums live in registers");
+        static_assert(sizeof(Mdl::kObservableNames) / sizeof(Mdl::kObservableNames[0]) == observables<Mdl>::value, "one name per observable");
+        t.observables = observables<Mdl>::value; t.observable_names = Mdl::kObservableNames; t.observe = &observe<Mdl>;
     }
     if constexpr (!has_custom_traj<Mdl>::value && !no_jacobi<Mdl>::value) t.jacobi = &jacobi<Mdl>;   // nor Jacobi fields (their chart changes rewrite the costate)
     if constexpr (FIELDS && has_fields<Mdl>::value && !has_custom_traj<Mdl>::value) t.fields = &fields<Mdl>;

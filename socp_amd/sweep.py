@@ -452,6 +452,31 @@ def extrema_local(ctx, args, local, lo, rank, params=None):
             "what": args.extrema_what, "wall_s": wall, "file": path}
 
 
+def observe_local(ctx, args, local, lo, rank, params=None):
+    """--observe-out: the model-defined observables (socp_observe_batch) of this rank's CONVERGED chains, each with its own parameter
+    block when the chains have one: over every row of every segment (the rows of a trace with stride 1, none of them stored) the
+    smallest and the largest value of each observable, the times of their first attainment and the trapezoid integral.  Written to
+    PATH.rank<r>.npz: index [k] = position of the chain in the sweep's start table, names [NO], ymin / ymax / tmin / tmax / integral
+    [k][M][NO], count [k][M], nbad [k][M].  Runs after the timed solve.  Returns the record entry of this rank: per name the smallest
+    minimum, the largest maximum and the median over the chains of the integral summed over the segments (in numpy, in segment
+    order), and the number of chains with a value that is not finite."""
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.observe_out)
+    t0 = time.perf_counter()
+    r = ctx.observe_batch(z, blocks=None if own is None else (own, None, None))
+    wall = time.perf_counter() - t0
+    np.savez(path, index=index, names=np.array(r["names"]), ymin=r["ymin"], ymax=r["ymax"], tmin=r["tmin"], tmax=r["tmax"],
+             integral=r["integral"], count=r["count"], nbad=r["nbad"])
+    entry = {"rows": int(len(conv)), "nbad_rows": int(np.sum(r["nbad"].sum(axis=1) > 0)), "wall_s": wall, "file": path}
+    some = len(conv) > 0
+    total = np.zeros((len(conv), len(r["names"])))
+    for i in range(r["integral"].shape[1]):                # segment order
+        total = total + r["integral"][:, i, :]
+    for k, name in enumerate(r["names"]):
+        entry[name] = {"min": float(r["ymin"][:, :, k].min()) if some else None, "max": float(r["ymax"][:, :, k].max()) if some else None,
+                       "integral_median": float(np.median(total[:, k])) if some else None}
+    return entry
+
+
 def tangent_local(ctx, args, local, lo, rank, params=None):
     """--tangent-out: the sensitivity dz/dtheta (socp_tangent_batch) of this rank's CONVERGED chains to the packed parameter
     --tangent-param, each chain with its own parameter block when the chains have one, written to PATH.rank<r>.npz: index [k] =
@@ -746,6 +771,14 @@ def main():
                          "chains' own parameter blocks; writes PATH.rank<r>.npz (index, vmin, vmax, tmin, tmax, count, nbad) and adds "
                          "extrema {rows, h_spread_max, h_spread_median, nbad_rows} to the record.  Not with --model interceptor.  "
                          "Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--observe-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank reduces the model-defined observables along the trajectories of the converged "
+                         "chains of its own block in one launch that stores no row (socp_observe_batch): for Goddard r, v, norm_u, drag, "
+                         "drag_acc and fuel_rate -- their smallest and largest value over all rows of every segment, when, and their "
+                         "trapezoid integral (that of fuel_rate is the burnt mass), with the chains' own parameter blocks; writes "
+                         "PATH.rank<r>.npz (index, names, ymin, ymax, tmin, tmax, integral, count, nbad) and adds observe {rows, "
+                         "nbad_rows, and per name min, max, integral_median} to the record.  Not with --model interceptor.  Absent: the "
+                         "timed wall and the printed record are unchanged")
     ap.add_argument("--extrema-what", type=int, default=7, metavar="N",
                     help="with --extrema-out: 0 .. 7, the sum of 1 (controls), 2 (Hamiltonian), 4 (event channels); the states always")
     ap.add_argument("--fields-stride", type=int, default=100, metavar="K", help="with --fields-out: sample every K-th step (and the last)")
@@ -804,6 +837,8 @@ def main():
         ap.error("--exactjac-out: the interceptor has no exact-Jacobian kernel (its own ComputeTraj and final rows)")
     if args.extrema_out and args.model == "interceptor":
         ap.error("--extrema-out is implemented for the Goddard sweeps")
+    if args.observe_out and args.model == "interceptor":
+        ap.error("--observe-out: the interceptor has no observe entry (a model with its own ComputeTraj)")
     if not 0 <= args.extrema_what <= 7:
         ap.error("--extrema-what must be 0 .. 7")
     if args.fields_stride < 1 or args.fields_skip < 0:
@@ -959,6 +994,8 @@ def main():
         extra["exact_jacobian" if rank == 0 else "exact_jacobian_rank%d" % rank] = exactjac_local(ctx, args, local, lo_w, rank, blocks)
     if args.extrema_out:
         extra["extrema" if rank == 0 else "extrema_rank%d" % rank] = extrema_local(ctx, args, local, lo_w, rank, blocks)
+    if args.observe_out:
+        extra["observe" if rank == 0 else "observe_rank%d" % rank] = observe_local(ctx, args, local, lo_w, rank, blocks)
     if args.sing_out:
         extra["singular" if rank == 0 else "singular_rank%d" % rank] = singular_local(ctx, args, local, lo_w, rank, blocks)
     if args.branch_out:
