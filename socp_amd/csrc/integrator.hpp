@@ -108,8 +108,11 @@ struct Lane {
     // [ext] Boost.Odeint is not vendored; restated from its published algorithm.  PINNED: the tableau to the
     // published Dormand-Prince pair (order conditions in rational arithmetic, SciPy's copy) and every stage sum, the error estimate
     // and every controller decision to a 240-bit step-by-step replay of this loop, at rounding level (tests/dopri5_reference.py,
-    // tests/test_gpu_dopri5_pin.py).  NOT verified: agreement with Boost's own code.  The interceptor's compute_traj drives this
-    // same template through its chart-change hook and is not pinned by scenarios of its own; vtolUAV is not pinned either.  FSAL stages
+    // tests/test_gpu_dopri5_pin.py).  The interceptor's compute_traj, which drives this same template through its chart-change
+    // hook, and vtolUAV with its obstacle map are pinned the same way by scenarios of their own, both flavours: the hook before
+    // every step, the FSAL derivative recomputed after a chart change, both phases, the hand-back, the box selections at every
+    // stage (tests/adaptive_models_reference.py, tests/test_gpu_adaptive_models_pin.py).  NOT verified: agreement with Boost's
+    // own code, modeMPP 1 / 2, and trajectories longer than those scenarios (at most 9 trial steps).  FSAL stages
     // summed left to right, error max_i |e_i| / (tol + tol (|x_i| + dt |k1_i|)) on the OLD state, reject ->
     // dt *= max(0.9 err^-1/3, 0.2), accept with err < 0.5 -> dt *= 0.9 max(5^-5, err)^-1/5, stepping while
     // t + dt <= tf and finishing with dt = tf - t.  Step control is PER LANE: lanes of a wave take different

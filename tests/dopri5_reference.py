@@ -40,6 +40,11 @@ DECISIONS.  Every comparison goes through the kit's cmp and is recorded with its
 err > 5^-5, the two loop conditions, and every kink of the right-hand side at every stage.  A scenario is DECIDABLE when every
 margin exceeds DECIDE_FACTOR x its bound.  The loop conditions at the end of a segment have margin eps = 2u against a bound of
 u (|h| + |tf|): decidable iff |h| + |tf| < 1/2, so the scenarios keep tf <= 1/4.
+
+MODELS WITH A HOOK OR A MAP.  `replay` also takes a start time other than zero, a right-hand side with auxiliary scalars and a hook
+called before every step (the interceptor's chart change), and D5Tracked has every function the interceptor and vtolUAV call -- sin,
+cos, tan, acos, atan2, tanh, the library exp, the short sincos, copysign -- each with its derivative row and the budget the model's
+own module uses (fast_reference.C_*, interceptor_reference.C_SINCOS_FAST).  adaptive_models_reference.py composes them.
 """
 from fractions import Fraction as Fr
 
@@ -90,6 +95,9 @@ class _Trail:
         self.taken[name] = d
         return d
 
+    def cmp_exact(self, name, a, b, op):
+        return super().cmp_exact(self.prefix + name, a, b, op)
+
     def start(self, nsrc=0):
         self.taken = {}
         self.margins = {}
@@ -121,6 +129,11 @@ class Affine:
     @staticmethod
     def lift(x):
         return x if isinstance(x, Affine) else Affine(x)
+
+    @property
+    def exact(self):
+        """No bound at all: an input, or a structural zero (interceptor_reference.lu6_solve leaves those out)."""
+        return self.e == 0 and (self.d is None or not self.d.any())
 
     @staticmethod
     def _rounded(res, prop, d, c=1, underflow=True):
@@ -162,7 +175,10 @@ class Affine:
 
     def __mul__(self, o):
         o = Affine.lift(o)
-        return Affine._rounded(self.v * o.v, abs(self.v) * o.e + abs(o.v) * self.e, Affine._lin(o.v, self.d, self.v, o.d))
+        prop = abs(self.v) * o.e + abs(o.v) * self.e
+        if fr.Tracked.second_order:                     # fast_reference.second_order_products(): vtolUAV's vanishing factors
+            prop += self.e * o.e
+        return Affine._rounded(self.v * o.v, prop, Affine._lin(o.v, self.d, self.v, o.d))
 
     __rmul__ = __mul__
 
@@ -179,9 +195,10 @@ class D5Tracked(_Trail, fr._Kit):
     """The bound.  fast_reference.TrackedKit's error model on Affine numbers, with pow and the maximum of the error norm."""
     AD_SLACK = 1 + 2.0 ** -20                            # the derivative rows are float64: their own rounding, generously
 
-    def __init__(self, flip=(), c_pow=C_POW):
+    def __init__(self, flip=(), c_pow=C_POW, c_exp=fr.C_EXP):
         super().__init__(flip)
         self.c_pow = c_pow
+        self.c_exp = c_exp                              # vtolUAV's throughput flavour calls the library's exp: C_EXP_LIB
 
     def start(self, nsrc=0):
         super().start()
@@ -220,13 +237,80 @@ class D5Tracked(_Trail, fr._Kit):
             return Affine(res)
         return Affine._rounded(res, a.e / (2 * res) if a.e else mpf(0), Affine._lin(1 / (2 * res), a.d, 0, None))
 
-    @staticmethod
-    def exp(a):
+    def exp(self, a, c=None):
         res = mpmath.exp(a.v)
-        e = res * a.e + fr.C_EXP * fr.U * res
+        e = res * a.e + (self.c_exp if c is None else c) * fr.U * res
         if res < fr.TINY:
             e += fr.EXP_FLOOR
         return Affine(res, e, Affine._lin(res, a.d, 0, None))
+
+    def exp_lib(self, a):
+        """The device library's exp as the interceptor's throughput flavour calls it (interceptor_reference.FastTrackedKit)."""
+        return self.exp(a, fr.C_EXP_LIB)
+
+    # The functions the interceptor and vtolUAV call, each with its derivative row and the budget its model module uses
+    # (fast_reference.TrackedKit's error model, term for term).
+    @staticmethod
+    def _fn(res, prop, c, da, d):
+        return Affine(res, prop + c * fr.U * abs(res), Affine._lin(da, d, 0, None))
+
+    @staticmethod
+    def tanh(a):
+        res = mpmath.tanh(a.v)
+        return D5Tracked._fn(res, (1 - res * res) * a.e, fr.C_TANH, 1 - res * res, a.d)
+
+    @staticmethod
+    def sin(a):
+        res, c = mpmath.sin(a.v), mpmath.cos(a.v)
+        return D5Tracked._fn(res, abs(c) * a.e, fr.C_SIN, c, a.d)
+
+    @staticmethod
+    def cos(a):
+        res, s = mpmath.cos(a.v), mpmath.sin(a.v)
+        return D5Tracked._fn(res, abs(s) * a.e, fr.C_COS, -s, a.d)
+
+    @staticmethod
+    def tan(a):
+        res = mpmath.tan(a.v)
+        return D5Tracked._fn(res, (1 + res * res) * a.e, fr.C_TAN, 1 + res * res, a.d)
+
+    @staticmethod
+    def atan2(y, x, y_negative_zero=False):
+        res = fr._atan2_mpf(y.v, x.v, y_negative_zero)
+        n2 = x.v * x.v + y.v * y.v
+        if not n2:
+            return Affine(res, fr.C_ATAN2 * fr.U * abs(res))
+        return Affine(res, (abs(x.v) * y.e + abs(y.v) * x.e) / n2 + fr.C_ATAN2 * fr.U * abs(res), Affine._lin(x.v / n2, y.d, -y.v / n2, x.d))
+
+    @staticmethod
+    def acos(a):
+        """The enclosure of TrackedKit.acos for the local bound; the sources enter to first order, -1 / sqrt(1 - a^2)."""
+        v = fr._clamp1(a.v)
+        res = mpmath.acos(v)
+        prop = max(mpmath.acos(fr._clamp1(v - a.e)) - res, res - mpmath.acos(fr._clamp1(v + a.e))) if a.e else mpf(0)
+        d = None
+        if a.d is not None and a.d.any():
+            assert abs(v) < 1, "acos at +-1 of a number that depends on a source: no first-order bound"
+            d = float(-1 / mpmath.sqrt(1 - v * v)) * a.d
+        return Affine(res, prop + fr.C_ACOS * fr.U * abs(res), d)
+
+    @staticmethod
+    def copysign(a, b):
+        pos = b.v >= 0
+        same = (a.v >= 0) == pos
+        return Affine(abs(a.v) if pos else -abs(a.v), a.e, a.d if same or a.d is None else -a.d)
+
+    @staticmethod
+    def sincos_fast(a, c_rel, k_abs):
+        """ifast::sincos (interceptor_reference._sincos_fast): relative budget c_rel u and the absolute part k_abs of the reduction."""
+        s, c = mpmath.sin(a.v), mpmath.cos(a.v)
+        return (Affine(s, abs(c) * (a.e + k_abs) + c_rel * fr.U * abs(s), Affine._lin(c, a.d, 0, None)),
+                Affine(c, abs(s) * (a.e + k_abs) + c_rel * fr.U * abs(c), Affine._lin(-s, a.d, 0, None)))
+
+    def exact_diff(self, a, b):
+        """fast_reference's cmp_exact compares two INPUTS; along a trajectory the position is computed, so the difference carries
+        its operands' bounds (and no rounding of its own: only its sign is read) and the decision is judged like any other."""
+        return Affine(a.v - b.v, a.e + b.e, Affine._lin(1, a.d, -1, b.d))
 
     @staticmethod
     def rcp(a):
@@ -334,15 +418,34 @@ KINKS = ("Switch", "Switch+2mu2umax", "t-sw0", "t-sw1", "|alpha|-umax", "u-umin"
 
 # ---- the replay ------------------------------------------------------------------------------------------------------------
 
-def replay(K, model, flavour, P, sw, tol, tf, step_nbr, X0, mut=None):
-    """integrate_dopri5(t0 = 0, tf) on the kit K.  Returns a dict: times / states (t0 and the end of every accepted step, kit
+HOOK_MUTATIONS = {
+    "stale_k1": "the FSAL derivative kept after the hook rewrote the state",
+}
+
+
+def replay(K, model, flavour, P, sw, tol, tf, step_nbr, X0, mut=None, t0=0.0, rhs=None, aux=None, hook=None, resume=None,
+           h0_from=None, max_trials=MAX_TRIALS):
+    """integrate_dopri5(t0, tf) on the kit K.  Returns a dict: times / states (t0 and the end of every accepted step, kit
     numbers), trials [dict(step, t, h, err, accepted, fresh, clamp, start_taken: the kink decisions at the step's
-    start)], stage_taken (the decisions of the stages of each trial).  `mut` names one entry of MUTATIONS."""
-    assert mut is None or mut in MUTATIONS, mut
-    K.start((len(X0) + 2) * (MAX_TRIALS + 2))
+    start)], stage_taken (the decisions of the stages of each trial).  `mut` names one entry of MUTATIONS or HOOK_MUTATIONS.
+
+    t0 != 0: h0 = (tf - t0) / step_nbr has a rounded subtraction, which is counted (and promoted to a source, as every later step
+    size is).  rhs(K, t, X, aux) replaces the table's right-hand side (model, flavour, P and sw are then unused); aux is whatever
+    the model carries beside the state (the interceptor's stage and chart, vtolUAV's lifted obstacle table).  hook(K, t, X, aux) ->
+    (changed, X, aux) is called where integrate_dopri5 calls its hook: before every step, inside the inner loop; its decisions go
+    through K.cmp under the prefix H<n>.; when it reports a change k1 is recomputed at the new X.  The result has `aux` (one entry
+    per row of states) and `hooks` (per call: whether it changed the state, and the index of the trial that follows).  resume: the
+    result of the segment run just before this one on the SAME kit -- the kit is not restarted, X0 are its numbers, and rows,
+    trials and decision names count on (the interceptor's second phase).  h0_from: the first step formed from tf - h0_from (a
+    mutation of the callers').  max_trials: where the replay stops and says "truncated"; it also sizes the sources."""
+    assert mut is None or mut in MUTATIONS or mut in HOOK_MUTATIONS, mut
     L = K.lift
-    rhs = RHS[(model, flavour)]
-    Pk, swk = [L(p) for p in P], [L(s) for s in sw]
+    if resume is None:
+        K.start((len(X0) + 2) * (max_trials + 2))
+    if rhs is None:
+        table_rhs = RHS[(model, flavour)]
+        Pk, swk = [L(p) for p in P], [L(s) for s in sw]
+        rhs = lambda K_, t_, X_, aux_: table_rhs(K_, Pk, swk, t_, X_)
     n = len(X0)
 
     def q(c):                                           # a coefficient as the kernel forms it: numerator / denominator in double
@@ -364,7 +467,7 @@ def replay(K, model, flavour, P, sw, tol, tf, step_nbr, X0, mut=None):
 
     def f(tag, t, X):
         K.prefix = tag
-        out = rhs(K, Pk, swk, t, X)
+        out = rhs(K, t, X, aux)
         K.prefix = ""
         return out
 
@@ -378,27 +481,45 @@ def replay(K, model, flavour, P, sw, tol, tf, step_nbr, X0, mut=None):
             out.append(s)
         return out
 
-    t = L(0.0)
+    t = L(float(t0))
     # h0 = (tf - t0) / step_nbr with t0 = 0: the subtraction is exact, and so is the division when step_nbr is 1
-    h = tfk if step_nbr == 1 else tfk / L(float(step_nbr))
-    X = [L(x) for x in X0]
-    res = {"times": [t], "states": [X], "trials": [], "stage_taken": []}
+    if t0 == 0.0 and h0_from is None:
+        h = tfk if step_nbr == 1 else tfk / L(float(step_nbr))
+    else:
+        h = tfk - L(float(t0 if h0_from is None else h0_from))
+        h = K.promote(h if step_nbr == 1 else h / L(float(step_nbr)))
+    if resume is None:
+        X = [L(x) for x in X0]
+        res = {"times": [t], "states": [X], "aux": [aux], "trials": [], "stage_taken": [], "hooks": [], "outer": 0, "step": 0}
+    else:
+        X = list(X0)
+        res = {k: (list(v) if isinstance(v, list) else v) for k, v in resume.items()}
+        res["times"].append(t)
+        res["states"].append(X)
+        res["aux"].append(aux)
     if not K.value(h) > 0:
         return res
     k1 = None
     fresh = False                                       # h is tf - t, formed at this t and not resized since
-    step = 0
-    outer = 0
+    step = res["step"]
+    outer = res["outer"]
     while K.cmp("O%d.tf-t>eps" % outer, (tfk - t) - eps, ">"):
         while True:
             if not K.cmp("I%d.t+h-tf<=eps" % len(res["trials"]), (t + h - tfk) - eps, "<="):
                 break
+            if hook is not None:
+                K.prefix = "H%d." % len(res["hooks"])
+                changed, X, aux = hook(K, t, X, aux)
+                K.prefix = ""
+                res["hooks"].append((bool(changed), len(res["trials"])))
+                if changed and mut != "stale_k1":
+                    k1 = None
             if k1 is None:
                 k1 = f("S%d.k1." % step, t, X)
                 start_taken = {k.split(".", 2)[2]: v for k, v in K.taken.items() if k.startswith("S%d.k1." % step)}
             while True:
                 T = len(res["trials"])
-                if T >= MAX_TRIALS:                     # (a mutated controller may not get there: its rows so far are kept)
+                if T >= max_trials:                     # (a mutated controller may not get there: its rows so far are kept)
                     res["truncated"] = True
                     return res
                 tag = "T%d." % T
@@ -443,12 +564,15 @@ def replay(K, model, flavour, P, sw, tol, tf, step_nbr, X0, mut=None):
             X, k1 = [K.promote(x) for x in xn], kn      # FSAL: the next step starts from the accepted trial's last stage
             start_taken = {k.split(".", 2)[2]: v for k, v in res["stage_taken"][-1].items() if k.startswith(tag + "k7.")}
             step += 1
+            res["step"] = step
             res["times"].append(t)
             res["states"].append(X)
+            res["aux"].append(aux)
         h = tfk - t
         fresh = True
         k1 = None
         outer += 1
+        res["outer"] = outer
     return res
 
 
@@ -462,8 +586,10 @@ def emulate(model, flavour, P, sw, tol, tf, step_nbr, X0, mut=None):
 
 # ---- the instrument --------------------------------------------------------------------------------------------------------
 
-def branches(r, step_nbr, value=float):
-    """The rows of the controller's branch table a replay went through (names of BRANCHES)."""
+def branches(r, step_nbr, value=float, kinks=KINKS):
+    """The rows of the controller's branch table a replay went through (names of BRANCHES).  kinks: the decision names that count
+    as a kink of the right-hand side, or a predicate on the name."""
+    is_kink = kinks if callable(kinks) else (lambda name: name in kinks)
     out = set()
     tr = r["trials"]
     v = [value(x["err"]) for x in tr]
@@ -494,7 +620,7 @@ def branches(r, step_nbr, value=float):
         start = x["start_taken"]
         for k, d in st.items():
             name = k.split(".", 2)[2]
-            if name in KINKS and name in start and start[name] != d:
+            if is_kink(name) and name in start and start[name] != d:
                 out.add("kink")
     return out
 

@@ -86,6 +86,9 @@ def _sincos_fast(K, a):
     """(sin a, cos a) as ifast::sincos forms them, on the kit's numbers."""
     if isinstance(K, F64Kit):
         return sincos_fast_f64(a, getattr(K, "mutation", None))
+    if hasattr(K, "sincos_fast"):                                         # dopri5_reference.D5Tracked: the same budget on its numbers
+        assert abs(a.v) <= SINCOS_FAST_RANGE + 1, "outside the range ifast::sincos' budget is derived for"
+        return K.sincos_fast(a, C_SINCOS_FAST, abs(mpmath.nint(a.v * 2 / mpmath.pi)) * mpf(2) ** -108)
     if isinstance(K, TrackedKit):
         assert abs(a.v) <= SINCOS_FAST_RANGE + 1, "outside the range ifast::sincos' budget is derived for"
         s, c = mpmath.sin(a.v), mpmath.cos(a.v)
@@ -424,7 +427,9 @@ def lu6_solve(K, A, y, tag=""):
 
 
 def _exact_zero(q):
-    return not isinstance(q, Tracked) or q.e == 0
+    if isinstance(q, Tracked):
+        return q.e == 0
+    return getattr(q, "exact", True)                                      # dopri5_reference.Affine says so itself; a plain number is exact
 
 
 def new_angles(K, from1, a1, a2, raw_a1, tag=""):

@@ -181,7 +181,11 @@ def test_config5_interceptor_dopri5_253_unknowns(built, variant):
     adaptive integrator (oracle/interceptor_oracle.c: orc_interceptor_compute_traj_adaptive -- PARITY UNPINNED: no Boost,
     no Eigen, no reference-held vectors, and the reference's interceptor is RK4-only, so this combination is an
     extrapolation of the reference; the tolerance is the one the single-trajectory adaptive tests use, 100 x tol),
-    the FD Jacobian identical with and without the segment dedup, and every entry finite."""
+    the FD Jacobian identical with and without the segment dedup, and every entry finite.  What this comparison cannot see -- an
+    error of the size of one step's local error, such as a stale FSAL derivative after a chart change or a hook that is not
+    called before every step -- is pinned on short segments by test_gpu_adaptive_models_pin.py against a 240-bit replay of this
+    very loop (both flavours, at rounding level).  Agreement with Boost's own code stays unverified, and so do trajectories as
+    long as these 21 segments: the pinned scenarios have at most 9 trial steps."""
     from socp_amd import capi
     tol = 1e-8
     o = Oracle(MODEL_INTERCEPTOR)

@@ -239,7 +239,7 @@ def vtol_ref(K, P, tab, X, want_h=True):
     return d, u, _hamiltonian(K, P, X, u, obs), nan[1:]
 
 
-def vtol_fast(K, P, tab, X):
+def vtol_fast(K, P, tab, X, want_h=True):
     """VtolT<true>.  Returns (Xdot[12], u[3], H, reset[3]); control and Hamiltonian are the reference-order expressions (compiled
     with contraction), the Hamiltonian around map_fast<F>."""
     vx, vy, vz, p_x, p_y, p_z, p_vx, p_vy, p_vz = X[3:12]
@@ -270,6 +270,8 @@ def vtol_fast(K, P, tab, X):
         d[9] = -p_x + ca*(p_vx*normV + vx*pv) - w*vx
         d[10] = -p_y + ca*(p_vy*normV + vy*pv) - w*vy
         d[11] = -p_z + ca*(p_vz*normV + vz*pv) - w*vz
+    if not want_h:
+        return d, u, None, nan[1:]
     obs = map_fast(K, P, tab, X[0], X[1], X[2], True, False)[0]
     return d, u, _hamiltonian(K, P, X, u, obs), nan[1:]
 
