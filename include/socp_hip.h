@@ -982,6 +982,74 @@ int socp_newton_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
                              const double *xnode, const socp_newton_options *opt, double *Zout, double *Fout, double *rnorm,
                              double *dnorm, int *iters, int *nhalf, int *status, double *rhist);
 
+/* EXACT parameter sensitivities of a whole batch of converged unknown vectors: dz/dtheta from J dz = -dF/dtheta, where BOTH sides are
+ * exact for the discrete flow -- J is socp_exact_jacobian_batch's, dF/dtheta comes from dual numbers carried through the residual's own
+ * RK4 steps and rows with the PARAMETER as the seeded quantity.  [ext] socp_tangent_batch differences both sides; on the nominal Goddard
+ * extremal its predictor z + dtheta dz then carries a first-order error (README).  Directions (dir_kind[K], dir_index[K]: HOST arrays,
+ * read before the call returns; 1 <= K <= 16) with the kinds and ranges of socp_tangent_batch, except that a SOCP_DIR_PARAM index must
+ * be < nparams: the slots nparams and nparams + 1 (sw0, sw1) are refused, the discrete flow is piecewise constant in them and a zero
+ * would mislead.  Z[B][n] -> dZ[B][K][n], info[B], Gp[B][K][n] (may be NULL: G = dF/dtheta_k).  SETUP, timeline, switching times and
+ * per-row blocks are those of socp_residual_batch; DUAL NUMBERS as in socp_fields_batch.  Per row b:
+ *   1. J: exactly what socp_exact_jacobian_batch_dev stores for the row (the same launch, the same bits; its F is not requested).
+ *   2. G[b][k][:], zero-filled first on the call's stream; every entry then has exactly one writer: the lane of the segment that owns
+ *      the row in the ROWS paragraph of socp_exact_jacobian_batch.  One lane per (row, segment, integrating direction); the directions
+ *      of one kind of one (row, segment) are neighbouring lanes, 64 / (their number) groups per wave; one launch per kind present.
+ *      SOCP_DIR_PARAM, index q.  The lane reads the row's packed block as dual numbers: every one of the nparams slots is (p_i, +0.0),
+ *      the addressed one (p_q, 1.0).  A parameter takes part by the full dual x dual rules, its zero terms computed; literals, t, N,
+ *      the switching times and the step stay plain, as in socp_fields_batch.  The start state is (z, +0.0).  The step loop and the RK4
+ *      step are socp_fields_batch's (plain t and h).  The rows are segment_residual on duals with the dual parameters: row ft_row[0]
+ *      (t0 FREE): hamiltonian_t(t1, X) on the start state of segment 0; on the END state X of segment i < M - 1: row ft_row[i + 1]
+ *      (that time FREE): switching_fn_t(t2, X, (Xp, +0.0)) -- the -H(Xp) term of a model with kSwitchingReadsXp sees the parameter in
+ *      this same evaluation -- and the derivative parts of X[j] at row S (i + 1) + j and, unless component j is FIXED, of X[j + d] at
+ *      row S (i + 1) + d + j; on the END state of segment M - 1: X[j + d] where component j of node M is FREE, else X[j], at row d + j,
+ *      and hamiltonian_t(t2, X) at row ft_row[M] (tf FREE).  (x - c).d is x.d for a plain c, so the subtractions of xd and Xp are not
+ *      formed.  The rows j < d of node 0 and the second row of a FIXED interior component read no parameter: nothing is stored.
+ *      Comparisons read value parts (mu2 > 0, singularControl < 0, the u_max saturation, covid19's bounds and Imax): a kink
+ *      differentiates the branch taken, and a control clamped to a bound IS that parameter, (u_max, its derivative part).  The value
+ *      parts are the reference-order residual's, bit for bit.
+ *      SOCP_DIR_TIME, node f.  Where node f is FIXED (a junction of the timeline whose time is the table's), the lane of segment i
+ *      runs the LENGTH column of socp_exact_jacobian_batch unchanged -- t2 = (t2, 1.0), dual step, plain parameters -- and stores
+ *      w (d row / d L), one product, at (row, k) for the END-state rows above, w = c(i + 1, f) - c(i, f) the free-time columns' weight
+ *      with FIXED in place of FREE; nothing is stored when w == 0.0.  A FREE or CONTINUOUS node's table time is never read: G = +0.0,
+ *      no lane is launched, and the direction is not refused (as in socp_tangent_batch).  What socp_exact_jacobian_batch does not
+ *      differentiate (an explicit t, the mu2 = 0 comparisons against sw0 / sw1) is not differentiated here either.
+ *      SOCP_DIR_XNODE, (j, c).  No integration.  -1.0 at every row that reads xd[j][c]: row c where component c of node 0 is not
+ *      FREE, row d + c where component c of node M is not FREE, rows S j + c and S j + d + c of a FIXED interior component; otherwise
+ *      nothing.
+ *   3. rhs = -G entry by entry (exact; a +0.0 becomes -0.0); dZ[b][k] = the solution of J x = rhs[k] by step 6 of socp_tangent_batch,
+ *      run in REFERENCE ORDER in both flavours (as socp_newton_batch and socp_branch_batch do); info[b] as there.
+ * ONE OBJECT, NO CONTRACTION: a throughput-flavour context returns the same bits.  tests/sensitivity_reference.py restates the
+ * definition; the tests compare whole buffers to it.
+ * socp_ctx_has_sensitivity: 1 when the model's launch table has the entry -- everything socp_ctx_has_exact_jacobian asks for, and
+ * rhs_t / hamiltonian_t / switching_fn_t generic in the parameter view (Goddard in both laws, the double integrator, covid19, a plugin
+ * that writes its traits so: tests/plugin/osc1d_sensitivity_plugin.hip) -- else 0.
+ * socp_sensitivity_work_bytes: the bytes of d_work for (B, K) on this context's problem (0 for arguments the call would refuse):
+ * J[B][n*n] and G[B][K][n].
+ * Launches of the _dev form: the exact Jacobian (its zero-fill and ONE launch); G's zero-fill and one launch per integrating kind
+ * present (PARAM; TIME on a FIXED node); the finish (XNODE stores, rhs = -G); the elimination.  socp_ctx_counters advances by
+ * B M (S + 1) trajectories plus B M per integrating direction, and by 3 launches plus one per integrating kind present.
+ * SOCP_ERR_ARG: socp_tangent_batch's argument errors (no problem set, B < 0, K outside 1 .. 16, a kind outside 0 .. 2 or an index
+ * outside its range, a NULL required pointer, work_bytes below socp_sensitivity_work_bytes, a wrong parameter stride in _blocks), and
+ * a SOCP_DIR_PARAM index >= nparams.  SOCP_ERR_UNSUPPORTED (the message says which): the context's integrator is SOCP_INT_DOPRI5, the
+ * launch table has no sensitivity entry (the interceptor, vtolUAV, a model without the generic traits, with a switching_state hook or
+ * custom final rows; a plugin built before launch-table ABI 15 is refused when it registers: rebuild it), a FREE state component on an
+ * interior node, n beyond the elimination's bound.  B == 0: SOCP_OK without a launch.  An error writes nothing and leaves the context
+ * and its counters unchanged.
+ * The _dev form takes device pointers (the directions stay host arrays), only enqueues on the context's stream and neither allocates,
+ * copies nor synchronises.  The host forms stage through that stream and the context's grow-only buffers; _blocks: per-row blocks like
+ * socp_residual_batch_blocks, the context's own blocks restored afterwards.
+ * Not covered: jac = 2 inside socp_tangent_batch / socp_singular_batch / socp_branch_batch, a predictor inside socp_chains_solve, the
+ * adaptive integrator, the interceptor, vtolUAV, derivatives in sw0 / sw1, second derivatives, more than one GPU. */
+int socp_ctx_has_sensitivity(const socp_ctx *ctx);      /* 1 / 0; SOCP_ERR_ARG for a NULL context */
+size_t socp_sensitivity_work_bytes(const socp_ctx *ctx, int B, int K);
+int socp_sensitivity_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int K, const int *dir_kind, const int *dir_index, void *d_work,
+                               size_t work_bytes, double *d_dZ, int *d_info, double *d_Gp /* or NULL */);
+int socp_sensitivity_batch(socp_ctx *ctx, int B, const double *Z, int K, const int *dir_kind, const int *dir_index, double *dZ,
+                           int *info, double *Gp);
+int socp_sensitivity_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                                  const double *xnode, int K, const int *dir_kind, const int *dir_index, double *dZ, int *info,
+                                  double *Gp);
+
 /* The distinct roots of a whole sweep: which distinct rows does a table hold, how many rows went to each, and which row went where.
  * Model-independent (no problem has to be set, no launch table is used).
  * Rows V[B][ld]; the first n <= ld entries of a row are compared.  Greedy leader grouping IN ROW ORDER:

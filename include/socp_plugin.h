@@ -54,6 +54,18 @@
  * has the trait, the other example plugins do not).  A plugin built against an older launch table (ABI <= 13) is refused at
  * registration: rebuild it.
  *
+ * Launch-table ABI 15 adds the batched exact-sensitivities launcher (socp_sensitivity_batch, socp_hip.h).  Its trait is a way of
+ * writing the three traits of ABI 13: generic in the PARAMETER view as well,
+ *   template <class T, class PV> __device__ static void rhs_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S]);
+ *   template <class T, class PV> __device__ static T hamiltonian_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S]);
+ *   template <class T, class PV> __device__ static T switching_fn_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S],
+ *                                                                   const T (&Xp)[S]);
+ * where PV is anything with p[i]: socp::ModelParams (the texts are then what they were) or the dual view of a parameter block.  A
+ * local that holds a parameter is `auto`, a comparison reads d_val (tests/plugin/osc1d_sensitivity_plugin.hip).  A model whose traits
+ * take socp::ModelParams only keeps its fields and exact-Jacobian entries and has no sensitivity entry: socp_ctx_has_sensitivity says 0
+ * and the call returns SOCP_ERR_UNSUPPORTED.  A plugin built against an older launch table (ABI <= 14) is refused at registration:
+ * rebuild it.
+ *
  * Model ids below SOCP_PLUGIN_ID_MIN are reserved for in-tree models.
  */
 #ifndef SOCP_PLUGIN_H_

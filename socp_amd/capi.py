@@ -207,6 +207,12 @@ def lib():
         L.socp_tangent_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _ip, C.c_double, C.c_int, _dp, _ip, _dp]
         L.socp_tangent_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, C.c_double, C.c_int, _dp, _ip,
                                                 _dp]
+        L.socp_ctx_has_sensitivity.argtypes = [_vp]
+        L.socp_sensitivity_work_bytes.argtypes = [_vp, C.c_int, C.c_int]
+        L.socp_sensitivity_work_bytes.restype = C.c_size_t
+        L.socp_sensitivity_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _ip, _vp, C.c_size_t, _vp, _vp, _vp]
+        L.socp_sensitivity_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _ip, _dp, _ip, _dp]
+        L.socp_sensitivity_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, _dp, _ip, _dp]
         L.socp_linsolve_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
         L.socp_svd_batch_dev.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_branch_work_bytes.argtypes = [_vp, C.c_int]
@@ -1026,6 +1032,40 @@ class Context:
         self._chk(self.L.socp_tangent_batch_blocks(self.h, B, _d(Z), *blocks, K, kinds.ctypes.data_as(_ip), index.ctypes.data_as(_ip),
                                                    float(epsfcn), int(jac), _d(dz), info.ctypes.data_as(_ip), _d(G)))
         return dict(dz=dz, info=info, fp=G)
+
+    # -- batched exact sensitivities
+    def has_sensitivity(self):
+        """Whether this model has the exact-sensitivities kernel (socp_ctx_has_sensitivity): the in-tree Goddard, double integrator
+        and covid19, and a plugin whose rhs_t / hamiltonian_t / switching_fn_t are generic in the parameter view."""
+        return self.L.socp_ctx_has_sensitivity(self.h) == 1
+
+    def sensitivity_work_bytes(self, B, K):
+        """Bytes of the workspace sensitivity_batch_dev needs for B rows and K directions (socp_sensitivity_work_bytes)."""
+        return int(self.L.socp_sensitivity_work_bytes(self.h, int(B), int(K)))
+
+    def sensitivity_batch_dev(self, B, d_Z, dirs, d_work, work_bytes, d_dZ, d_info, d_Gp=None):
+        """Device pointers (ints; d_Gp may be None), dirs a host list of (kind, index); enqueue only, no allocation, no copy, no
+        synchronise (socp_sensitivity_batch_dev)."""
+        kinds, index = _dirs(dirs)
+        self._chk(self.L.socp_sensitivity_batch_dev(self.h, int(B), _vp(d_Z), len(kinds), kinds.ctypes.data_as(_ip), index.ctypes.data_as(_ip),
+                                                    _vp(d_work), int(work_bytes), _vp(d_dZ), _vp(d_info), _vp(d_Gp)))
+
+    def sensitivity_batch(self, Z, dirs, params=None, time=None, xnode=None, g=False):
+        """The exact dz/dtheta of every row of Z for the K directions dirs = [(kind, index), ...] (as tangent_batch; a DIR_PARAM index
+        must be below nparams): the solution of J dz = -dF/dtheta with the exact shooting Jacobian and the exact dF/dtheta of the
+        discrete flow (include/socp_hip.h has the definition).  Returns dict(dz[B][K][n], info[B] as tangent_batch,
+        g[B][K][n] = dF/dtheta or None).  params / time / xnode: per-row blocks as in residual_batch_blocks."""
+        Z = _f64(Z).reshape(-1, self.n)
+        B = Z.shape[0]
+        kinds, index = _dirs(dirs)
+        K = len(kinds)
+        blocks = _block_args(B, params, time, xnode)
+        dz = np.full((B, K, self.n), np.nan)
+        info = np.zeros(B, dtype=np.int32)
+        G = np.full((B, K, self.n), np.nan) if g else None
+        self._chk(self.L.socp_sensitivity_batch_blocks(self.h, B, _d(Z), *blocks, K, kinds.ctypes.data_as(_ip), index.ctypes.data_as(_ip),
+                                                       _d(dz), info.ctypes.data_as(_ip), _d(G)))
+        return dict(dz=dz, info=info, g=G)
 
     def linsolve_batch_dev(self, B, n, K, d_A, d_Y, d_info):
         """Device pointers (ints): A[B][n*n] column-major, Y[B][K][n] overwritten by the solutions, info[B]; enqueue only

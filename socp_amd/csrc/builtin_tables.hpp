@@ -43,6 +43,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         ModelLaunchers t = plugin::table<God, false>(SOCP_GODDARD_NPARAMS, 10, {3.5, 7.0, 310.0, 500.0, 1.0, 1.0, 0.0, -1.0});
         t.fields = &fields_goddard;                  // kernels_fields.hip: the same reference-order object in both flavours
         t.exact_jacobian = &exact_jacobian_goddard;  // kernels_exact_jacobian.hip: likewise
+        t.sensitivity = &sensitivity_goddard;        // kernels_sensitivity.hip: likewise
         t.traj = &goddard_by_params<&plugin::traj<GodSmooth>, &plugin::traj<God>>;
         t.eval = &goddard_by_params<&plugin::eval<GodSmooth>, &plugin::eval<God>>;
         t.residual = &goddard_by_problem<&plugin::residual<GodSmooth>, &plugin::residual<God>>;
@@ -63,6 +64,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         ModelLaunchers t = plugin::table<DInt, false>(SOCP_DINT_NPARAMS, 30, {1.0, 1.0, 0.01});
         t.fields = &fields_dint;
         t.exact_jacobian = &exact_jacobian_dint;
+        t.sensitivity = &sensitivity_dint;
         return t;
     }();
     // covid19.cpp:25-38 defaults; its ModelInt integrates with its own stepNbr = 1000
@@ -70,6 +72,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         ModelLaunchers t = plugin::table<Covid, false>(SOCP_COVID_NPARAMS, 1000, {4, 10, 5, 1, 0.1, 1, -10, 20});
         t.fields = &fields_covid;
         t.exact_jacobian = &exact_jacobian_covid;
+        t.sensitivity = &sensitivity_covid;
         return t;
     }();
     switch (model_id) {

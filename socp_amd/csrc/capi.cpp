@@ -2431,6 +2431,152 @@ int socp_newton_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
                        [&] { return socp_newton_batch(c, B, Z, opt, Zout, Fout, rnorm, dnorm, iters, nhalf, status, rhist); });
 }
 
+/* ---- batched exact sensitivities ------------------------------------------------------------- */
+
+int socp_ctx_has_sensitivity(const socp_ctx *c) { return c ? (table_of(c)->sensitivity ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+// the workspace of socp_sensitivity_batch_dev, in doubles from its start
+struct SensitivityWork {
+    size_t J, G, total;
+};
+
+SensitivityWork sensitivity_layout(const socp_ctx *c, int B, int K)
+{
+    const size_t n = c->n;
+    SensitivityWork w{};
+    w.J = 0;
+    w.G = ((size_t)B * n * n + 1) & ~(size_t)1;
+    w.total = w.G + (((size_t)B * K * n + 1) & ~(size_t)1);
+    return w;
+}
+
+// the directions of a checked call as they travel to the kernels: the PARAM directions, the TIME directions on a FIXED node (the
+// others read nothing), and the XNODE directions' mask and packed (node, component)
+struct SensitivityPlan {
+    SensDirs param, time;
+    unsigned xnode_mask;
+    unsigned long long xnode_index[4];
+};
+
+// the refusals all three forms share
+int sensitivity_args(socp_ctx *c, const char *who, int B, int K, const int *dir_kind, const int *dir_index, SensitivityPlan *plan)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (K < 1 || K > kMaxTangentDirs) return fail(c, SOCP_ERR_ARG, w + ": 1 <= K <= 16 directions are required");
+    if (!dir_kind || !dir_index) return fail(c, SOCP_ERR_ARG, w + ": null direction table");
+    TangentDirs dirs;
+    if (const int rc = direction_args(c, w, K, dir_kind, dir_index, &dirs)) return rc;
+    for (int k = 0; k < K; k++)
+        if (dirs.kind[k] == SOCP_DIR_PARAM && dirs.index[k] >= c->nparams)
+            return fail(c, SOCP_ERR_ARG, w + ": direction " + std::to_string(k) + " addresses a switching time (slot " +
+                                             std::to_string(dirs.index[k]) + " of the block): the discrete flow is piecewise constant in it");
+    if (!table_of(c)->sensitivity)
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": this model's launch table has no sensitivity entry (a model whose rhs_t, hamiltonian_t and "
+                                                 "switching_fn_t are not generic in the parameter view, or one with a switching_state hook, custom "
+                                                 "final rows or its own ComputeTraj; rebuild a plugin written for an older launch table)");
+    if (const int rc = exact_jacobian_args(c, who, B)) return rc;
+    if (!linsolve_fits(c->n, K))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": too many unknowns for the batched linear solve (2 n + K doubles must fit 64 KiB of LDS)");
+    SensitivityPlan p{};
+    p.param.kind = kSensParam; p.time.kind = kSensTime;
+    auto put = [](SensDirs &d, int k, int index) {
+        d.slot |= (unsigned long long)k << (4 * d.n);
+        d.index[d.n >> 2] |= (unsigned long long)index << (16 * (d.n & 3));
+        d.n += 1;
+    };
+    for (int k = 0; k < K; k++) {
+        const int index = dirs.index[k];
+        if (dirs.kind[k] == SOCP_DIR_PARAM) put(p.param, k, index);
+        else if (dirs.kind[k] == SOCP_DIR_TIME) {
+            if (c->mode_t[index] == SOCP_FIXED) put(p.time, k, index);
+        } else {
+            p.xnode_mask |= 1u << k;
+            p.xnode_index[k >> 2] |= (unsigned long long)(((index / c->S) << 5) | (index % c->S)) << (16 * (k & 3));
+        }
+    }
+    *plan = p;
+    return SOCP_OK;
+}
+}  // namespace
+
+size_t socp_sensitivity_work_bytes(const socp_ctx *c, int B, int K)
+{
+    if (!c || !c->has_problem || B < 0 || K < 1 || K > kMaxTangentDirs) return 0;
+    return sizeof(double) * sensitivity_layout(c, B, K).total;
+}
+
+int socp_sensitivity_batch_dev(socp_ctx *c, int B, const double *d_Z, int K, const int *dir_kind, const int *dir_index, void *d_work,
+                               size_t work_bytes, double *d_dZ, int *d_info, double *d_Gp)
+{
+    if (!c) return SOCP_ERR_ARG;
+    SensitivityPlan plan;
+    const int rc = sensitivity_args(c, "sensitivity_batch", B, K, dir_kind, dir_index, &plan);
+    if (rc != SOCP_OK) return rc;
+    if (B > 0 && (!d_Z || !d_work || !d_dZ || !d_info)) return fail(c, SOCP_ERR_ARG, "sensitivity_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    const SensitivityWork w = sensitivity_layout(c, B, K);
+    if (work_bytes < sizeof(double) * w.total)
+        return fail(c, SOCP_ERR_ARG, "sensitivity_batch: the workspace is smaller than socp_sensitivity_work_bytes");
+    double *wk = static_cast<double *>(d_work);
+    double *wJ = wk + w.J, *G = d_Gp ? d_Gp : wk + w.G;
+    // J: the exact Jacobian's own launch
+    if (const int r = exact_jacobian_launch(c, B, d_Z, wJ, nullptr)) return r;
+    // G: zero-filled, then the integrating directions kind by kind
+    HIP_TRY(c, hipMemsetAsync(G, 0, sizeof(double) * (size_t)B * K * c->n, c->stream));
+    for (const SensDirs *d : {&plan.param, &plan.time}) {
+        if (d->n == 0) continue;
+        c->n_traj += (long long)B * c->M * d->n; c->n_launch += 1;
+        HIP_TRY(c, table_of(c)->sensitivity(c->stream, c->P, c->pb, B, d_Z, *d, K, G));
+    }
+    // the XNODE directions' entries and rhs = -G into dZ; J x = rhs in place, in reference order in both flavours
+    c->n_launch += 2;
+    HIP_TRY(c, sensitivity_finish(c->stream, c->pb, B, K, plan.xnode_mask, plan.xnode_index, G, d_dZ));
+    HIP_TRY(c, linsolve(c->stream, B, c->n, K, wJ, d_dZ, d_info));
+    return SOCP_OK;
+}
+
+int socp_sensitivity_batch(socp_ctx *c, int B, const double *Z, int K, const int *dir_kind, const int *dir_index, double *dZ, int *info,
+                           double *Gp)
+{
+    if (!c) return SOCP_ERR_ARG;
+    SensitivityPlan plan;
+    const int rc0 = sensitivity_args(c, "sensitivity_batch", B, K, dir_kind, dir_index, &plan);
+    if (rc0 != SOCP_OK) return rc0;
+    if (B > 0 && (!Z || !dZ || !info)) return fail(c, SOCP_ERR_ARG, "sensitivity_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nZ = (size_t)B * c->n, nD = (size_t)B * K * c->n, nG = Gp ? nD : 0, bytes = socp_sensitivity_work_bytes(c, B, K);
+    double *d_Z;
+    HIP_TRY(c, c->s_var.reserve(bytes));
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (nD + nG) + sizeof(int) * (size_t)B));
+    double *dD = c->s_out.as<double>(), *dG = dD + nD;
+    int *dI = reinterpret_cast<int *>(dG + nG);
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, d_Z));
+    const int rc = socp_sensitivity_batch_dev(c, B, d_Z, K, dir_kind, dir_index, c->s_var.p, bytes, dD, dI, Gp ? dG : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, dZ, dD, nD));
+    if (Gp) HIP_TRY(c, copy_down(c, Gp, dG, nG));
+    HIP_TRY(c, copy_down(c, info, dI, (size_t)B));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_sensitivity_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                                  const double *xnode, int K, const int *dir_kind, const int *dir_index, double *dZ, int *info, double *Gp)
+{
+    if (!c) return SOCP_ERR_ARG;
+    SensitivityPlan plan;
+    const int rc0 = sensitivity_args(c, "sensitivity_batch_blocks", B, K, dir_kind, dir_index, &plan);
+    if (rc0 != SOCP_OK) return rc0;
+    if (const int rc = blocks_stride(c, "sensitivity_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !dZ || !info)) return fail(c, SOCP_ERR_ARG, "sensitivity_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_sensitivity_batch(c, B, Z, K, dir_kind, dir_index, dZ, info, Gp); });
+}
+
 /* ---- row grouping --------------------------------------------------------------------------- */
 
 namespace {

@@ -18,9 +18,10 @@
 
 namespace socp {
 
-// Lane::rk4's reference-order arm (odeTools.cpp:89-98) on dual numbers; t and step are plain doubles
-template <class Mdl>
-__device__ __forceinline__ void fields_rk4(const ModelParams &P, double sw0, double sw1, double t, Dual (&X)[Mdl::S], double step)
+// Lane::rk4's reference-order arm (odeTools.cpp:89-98) on dual numbers; t and step are plain doubles.  PV: ModelParams, or the
+// dual view of a parameter block (sensitivity.hpp)
+template <class Mdl, class PV>
+__device__ __forceinline__ void fields_rk4(const PV &P, double sw0, double sw1, double t, Dual (&X)[Mdl::S], double step)
 {
     constexpr int S = Mdl::S;
     Dual F1[S], Fs[S], F[S], Y[S];

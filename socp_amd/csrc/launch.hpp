@@ -39,13 +39,22 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 14;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 15;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
                                    // kPluginAbi = 12: batched extrema launcher
                                    // kPluginAbi = 13: batched exact shooting-Jacobian launcher
                                    // kPluginAbi = 14: batched observables launcher
+                                   // kPluginAbi = 15: batched exact-sensitivities launcher
+// the integrating directions of one kind of socp_sensitivity_batch as they travel to the kernel (sensitivity.hpp): 16 bits per
+// direction, four to a word.  slot: the direction's place k in the call's table (4 bits each); index: the parameter or the node
+constexpr int kSensParam = 0, kSensTime = 1;
+struct SensDirs {
+    int kind, n;                                     // kSensParam / kSensTime; 1 <= n <= 16
+    unsigned long long slot, index[4];
+};
+
 struct ModelLaunchers {
     int abi, dim, control_dim, nparams, default_step_nbr;
     double default_params[kMaxParams];
@@ -101,6 +110,11 @@ struct ModelLaunchers {
     const char *const *observable_names;
     hipError_t (*observe)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *, double *, double *,
                           double *, int *, int *);
+    // batched exact sensitivities (socp_sensitivity_batch): Z[B][n], the integrating directions of ONE kind, K -> their rows of
+    // G[B][K][n] (zero-filled by the caller; ONE launch); fixed-step integrator only.  Null: the model has no exact_jacobian entry, or
+    // its rhs_t / hamiltonian_t / switching_fn_t are not generic in the parameter view (plugin_impl.hpp).  The in-tree models' entries
+    // live in kernels_sensitivity.hip, one object without contraction that both flavours' tables point to
+    hipError_t (*sensitivity)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, const SensDirs &, int, double *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
@@ -252,6 +266,18 @@ hipError_t fields_covid(hipStream_t st, const ModelParams &P, const ProblemDev &
 hipError_t exact_jacobian_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
 hipError_t exact_jacobian_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
 hipError_t exact_jacobian_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
+
+// socp_sensitivity_batch of the in-tree models (kernels_sensitivity.hip: one object without contraction, for both flavours), and its
+// model-independent finish: the XNODE directions' -1.0 into G[B][K][n] (kind / index: 2 and 16 bits per direction, the index
+// (node << 5) | component), then rhs = -G
+hipError_t sensitivity_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, const SensDirs &dirs, int K,
+                               double *G);
+hipError_t sensitivity_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, const SensDirs &dirs, int K,
+                            double *G);
+hipError_t sensitivity_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, const SensDirs &dirs, int K,
+                             double *G);
+hipError_t sensitivity_finish(hipStream_t st, const ProblemDev &pb, int B, int K, unsigned xnode_mask, const unsigned long long (&index)[4],
+                              double *G, double *rhs);
 
 // the in-tree models' tables, one translation unit each
 // Goddard, double integrator, covid19 by SOCP_MODEL_* id (builtin_tables.hpp); null for any other id

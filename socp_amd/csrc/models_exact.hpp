@@ -253,13 +253,16 @@ struct GoddardExactT {
     // (goddard_ref) is the same text in Python.  With T = double it gives the bits of rhs.  The thrust magnitude is a plain
     // double where the law makes it a constant (off, full, a given singular value) and a T where it depends on the state; the
     // text from there on is written once (`thrust`) and instantiated for both.
-    template <class T>
-    __device__ static __forceinline__ void costate_dots_t(const ModelParams &P, const T (&X)[S], const T &r, const T &v, const T &g,
+    // The texts are generic in the PARAMETER view as well (socp_sensitivity_batch: PV = SeededParams, whose p[i] is a dual number):
+    // PV is deduced, a local that holds a parameter is `auto`, a comparison reads d_val.  With PV = ModelParams -- every call that
+    // passes the packed block -- the parameters are the plain doubles they were and the texts are unchanged, bit for bit.
+    template <class T, class PV>
+    __device__ static __forceinline__ void costate_dots_t(const PV &P, const T (&X)[S], const T &r, const T &v, const T &g,
                                                          const T &E, const T &pvdotv, T (&pd)[6])
     {
         const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
         const T p_x = X[7], p_y = X[8], p_z = X[9], p_vx = X[10], p_vy = X[11], p_vz = X[12];
-        const double KD = P.p[GP_KD], kr = P.p[GP_KR];
+        const auto KD = P.p[GP_KD], kr = P.p[GP_KR];
         const T A = -kr*KD / mass*v*E;
         const T Q = KD / mass*E;
         pd[0] = A*x / r*pvdotv + g*(p_vx*(1 - 3 * x*x / r / r) / r - p_vy * 3 * x*y / r / r / r - p_vz * 3 * x*z / r / r / r);
@@ -271,13 +274,13 @@ struct GoddardExactT {
     }
 
     // goddard.cpp:188-253 on T
-    template <class T>
-    __device__ static __forceinline__ T singular_control_t(const ModelParams &P, const T (&X)[S], const T &r, const T &v, const T &g,
+    template <class T, class PV>
+    __device__ static __forceinline__ T singular_control_t(const PV &P, const T (&X)[S], const T &r, const T &v, const T &g,
                                                           const T &norm_pv, const T &E, const T &pvdotv, const T (&pd)[6])
     {
         const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
         const T p_x = X[7], p_y = X[8], p_z = X[9], p_vx = X[10], p_vy = X[11], p_vz = X[12];
-        const double b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
+        const auto b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
         const T rdotv = x*vx + y*vy + z*vz;
         const T D = KD*E;
         const T prdotdotpv = pd[0]*p_vx + pd[1]*p_vy + pd[2]*p_vz;
@@ -303,13 +306,13 @@ struct GoddardExactT {
 
     // goddard.cpp:104-185 on T: the control u of both laws, the closed-form singular control included, from the quantities Model() and
     // Hamiltonian() both derive from the state.  ONE text for rhs_t and hamiltonian_t.
-    template <class T>
-    __device__ static __forceinline__ void control_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T &r,
+    template <class T, class PV>
+    __device__ static __forceinline__ void control_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], const T &r,
                                                     const T &v, const T &g, const T &norm_pv, const T &E, const T &pvdotv, const T (&pd)[6],
                                                     T (&u)[3])
     {
         const T mass = X[6], p_vx = X[10], p_vy = X[11], p_vz = X[12], p_mass = X[13];
-        const double b = P.p[GP_B], C = P.p[GP_C], u_max = P.p[GP_UMAX];
+        const auto b = P.p[GP_B], C = P.p[GP_C], u_max = P.p[GP_UMAX];
         const T Switch = P.p[GP_MU1] - b*p_mass - C / mass*norm_pv;
         // goddard.cpp:147-185 from the thrust magnitude on; A = double or T
         auto thrust = [&](const auto &alpha_u) {
@@ -317,30 +320,30 @@ struct GoddardExactT {
             u[1] = -p_vy*alpha_u / norm_pv;
             u[2] = -p_vz*alpha_u / norm_pv;
             const auto norm_a = d_abs(alpha_u);
-            if (d_val(norm_a) > u_max) {
+            if (d_val(norm_a) > d_val(u_max)) {
                 u[0] = u[0] / norm_a*u_max;
                 u[1] = u[1] / norm_a*u_max;
                 u[2] = u[2] / norm_a*u_max;
             }
         };
-        if (SMOOTH || P.p[GP_MU2] > 0) {
+        if (SMOOTH || d_val(P.p[GP_MU2]) > 0) {
             if (d_val(Switch) < 0) thrust(-Switch / 2 / P.p[GP_MU2]);
             else thrust(0.0);
         } else if constexpr (!SMOOTH) {
             if (t <= sw0) thrust(1.0);
             else if (t > sw0 && t <= sw1) {
-                if (P.p[GP_SING] < 0) thrust(singular_control_t<T>(P, X, r, v, g, norm_pv, E, pvdotv, pd));
+                if (d_val(P.p[GP_SING]) < 0) thrust(singular_control_t<T>(P, X, r, v, g, norm_pv, E, pvdotv, pd));
                 else thrust(P.p[GP_SING]);
             } else thrust(0.0);
         }
     }
 
-    template <class T>
-    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ void rhs_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S])
     {
         const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
         const T p_vx = X[10], p_vy = X[11], p_vz = X[12];
-        const double b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
+        const auto b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
         const T r = d_sqrt(x*x + y*y + z*z);
         const T v = d_sqrt(vx*vx + vy*vy + vz*vz);
         const T pvdotv = p_vx*vx + p_vy*vy + p_vz*vz;
@@ -399,12 +402,12 @@ struct GoddardExactT {
     // the Hamiltonian and the free-interior-time row over a number type T (socp_exact_jacobian_batch: T = Dual): goddard.cpp:256-295 on
     // plain IEEE operations in the reference's association order, the control from control_t -- the text rhs_t runs.  With T = double:
     // the bits of hamiltonian / switching_fn.  tests/fast_reference.py (goddard_ref's H) is the same text in Python.
-    template <class T>
-    __device__ static __forceinline__ T hamiltonian_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ T hamiltonian_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S])
     {
         const T x = X[0], y = X[1], z = X[2], vx = X[3], vy = X[4], vz = X[5], mass = X[6];
         const T p_x = X[7], p_y = X[8], p_z = X[9], p_vx = X[10], p_vy = X[11], p_vz = X[12], p_mass = X[13];
-        const double b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
+        const auto b = P.p[GP_B], C = P.p[GP_C], KD = P.p[GP_KD], kr = P.p[GP_KR];
         const T r = d_sqrt(x*x + y*y + z*z);
         const T v = d_sqrt(vx*vx + vy*vy + vz*vz);
         const T pvdotv = p_vx*vx + p_vy*vy + p_vz*vz;
@@ -425,8 +428,8 @@ struct GoddardExactT {
     }
     // the free interior-time row is H(t, X-): Xp is not read, so the lanes of the next segment have no part in it
     static constexpr bool kSwitchingReadsXp = false;
-    template <class T>
-    __device__ static __forceinline__ T switching_fn_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T (&)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ T switching_fn_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], const T (&)[S])
     {
         return hamiltonian_t<T>(P, sw0, sw1, t, X);
     }
@@ -504,16 +507,16 @@ struct DIntExact {
 
     // the right-hand side over a number type T (socp_fields_batch: T = Dual, dual.hpp): doubleIntegrator.cpp:67-108, 218-259 on
     // plain IEEE operations; with T = double the bits of rhs
-    template <class T>
-    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double, double, double, const T (&X)[S], T (&dX)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ void rhs_t(const PV &P, double, double, double, const T (&X)[S], T (&dX)[S])
     {
-        const double a_max = P.p[DP_AMAX], u_max = P.p[DP_UMAX];
+        const auto a_max = P.p[DP_AMAX], u_max = P.p[DP_UMAX];
         T u[3];
         u[0] = -X[9] / a_max;
         u[1] = -X[10] / a_max;
         u[2] = -X[11] / a_max;
         const T norm_u = d_sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
-        if (d_val(norm_u) > u_max) {
+        if (d_val(norm_u) > d_val(u_max)) {
             u[0] = u[0] / norm_u*u_max;
             u[1] = u[1] / norm_u*u_max;
             u[2] = u[2] / norm_u*u_max;
@@ -563,16 +566,16 @@ struct DIntExact {
 
     // the Hamiltonian and the free-interior-time row over a number type T (socp_exact_jacobian_batch: T = Dual):
     // doubleIntegrator.cpp:218-300 on plain IEEE operations; with T = double the bits of hamiltonian / switching_fn
-    template <class T>
-    __device__ static __forceinline__ T hamiltonian_t(const ModelParams &P, double, double, double, const T (&X)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ T hamiltonian_t(const PV &P, double, double, double, const T (&X)[S])
     {
-        const double a_max = P.p[DP_AMAX], u_max = P.p[DP_UMAX];
+        const auto a_max = P.p[DP_AMAX], u_max = P.p[DP_UMAX];
         T u[3];
         u[0] = -X[9] / a_max;
         u[1] = -X[10] / a_max;
         u[2] = -X[11] / a_max;
         const T norm_c = d_sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
-        if (d_val(norm_c) > u_max) {
+        if (d_val(norm_c) > d_val(u_max)) {
             u[0] = u[0] / norm_c*u_max;
             u[1] = u[1] / norm_c*u_max;
             u[2] = u[2] / norm_c*u_max;
@@ -583,8 +586,8 @@ struct DIntExact {
     }
     // model.hpp:299-304 default, H(t, X-) - H(t, X+): the lanes of the next segment own -grad H(X+)
     static constexpr bool kSwitchingReadsXp = true;
-    template <class T>
-    __device__ static __forceinline__ T switching_fn_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T (&Xp)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ T switching_fn_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], const T (&Xp)[S])
     {
         return hamiltonian_t<T>(P, sw0, sw1, t, X) - hamiltonian_t<T>(P, sw0, sw1, t, Xp);
     }
@@ -663,21 +666,20 @@ struct CovidExact {
     // the right-hand side over a number type T (socp_fields_batch: T = Dual, dual.hpp): covid19.cpp:53-126 on plain IEEE
     // operations; with T = double the bits of rhs.  A clamped control and an inactive penalty are plain doubles, as the
     // definition has them: the text from the control on is written once (`rest`) and instantiated for both.
-    template <class T>
-    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double, double, double, const T (&X)[S], T (&dX)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ void rhs_t(const PV &P, double, double, double, const T (&X)[S], T (&dX)[S])
     {
         const T Sx = X[0], E = X[1], I = X[2], R = X[3], pS = X[4], pE = X[5], pI = X[6], pR = X[7];
-        const double R0 = P.p[CP_R0], Tinf = P.p[CP_TINF], Tinc = P.p[CP_TINC], N = P.p[CP_N];
+        const auto R0 = P.p[CP_R0], Tinf = P.p[CP_TINF], Tinc = P.p[CP_TINC], N = P.p[CP_N];
         auto rest = [&](const auto &u) {
             const auto Rt = R0 * (1 - u);
             dX[0] = -Rt / Tinf / N*Sx*I;
             dX[1] = Rt / Tinf / N*Sx*I - E / Tinc;
         };
         const T u = (pE - pS)*Sx*I / Tinf / N * R0;
-        double uc = 0.0;
-        bool clamped = false;
-        if (d_val(u) <= P.p[CP_UMIN]) { uc = P.p[CP_UMIN]; clamped = true; }
-        if ((clamped ? uc : d_val(u)) >= P.p[CP_UMAX]) { uc = P.p[CP_UMAX]; clamped = true; }
+        auto uc = P.p[CP_UMIN];                                       // read only when clamped
+        bool clamped = d_val(u) <= d_val(uc);
+        if ((clamped ? d_val(uc) : d_val(u)) >= d_val(P.p[CP_UMAX])) { uc = P.p[CP_UMAX]; clamped = true; }
         if (clamped) rest(uc);
         else rest(u);
         dX[2] = E / Tinc - I / Tinf;
@@ -685,7 +687,7 @@ struct CovidExact {
         dX[4] = (pS - pE)*R*I / Tinf / N;
         dX[5] = (pE - pI) / Tinc;
         const T d6 = (pS - pE)*R*Sx / Tinf / N + (pI - pR) / Tinf;
-        if (d_val(I) >= P.p[CP_IMAX]) dX[6] = d6 + -P.p[CP_MUI]*(I - P.p[CP_IMAX]);
+        if (d_val(I) >= d_val(P.p[CP_IMAX])) dX[6] = d6 + -P.p[CP_MUI]*(I - P.p[CP_IMAX]);
         else dX[6] = d6 + 0.0;
         dX[7] = T(0.0);
     }
@@ -716,11 +718,11 @@ struct CovidExact {
     // the Hamiltonian and the free-interior-time row over a number type T (socp_exact_jacobian_batch: T = Dual): covid19.cpp:97-165 on
     // plain IEEE operations; with T = double the bits of hamiltonian / switching_fn.  As in rhs_t a clamped control and an inactive
     // penalty are plain doubles: the sum is written once (`rest`) and instantiated for the four combinations.
-    template <class T>
-    __device__ static __forceinline__ T hamiltonian_t(const ModelParams &P, double, double, double, const T (&X)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ T hamiltonian_t(const PV &P, double, double, double, const T (&X)[S])
     {
         const T Sx = X[0], E = X[1], I = X[2], pS = X[4], pE = X[5], pI = X[6], pR = X[7];
-        const double R0 = P.p[CP_R0], Tinf = P.p[CP_TINF], Tinc = P.p[CP_TINC], N = P.p[CP_N];
+        const auto R0 = P.p[CP_R0], Tinf = P.p[CP_TINF], Tinc = P.p[CP_TINC], N = P.p[CP_N];
         auto rest = [&](const auto &u, const auto &Ipen) -> T {
             const auto Rt = R0 * (1 - u);
             return u*u / 2 + Ipen
@@ -730,11 +732,10 @@ struct CovidExact {
                 + pR * (I / Tinf);
         };
         const T u = (pE - pS)*Sx*I / Tinf / N * R0;
-        double uc = 0.0;
-        bool clamped = false;
-        if (d_val(u) <= P.p[CP_UMIN]) { uc = P.p[CP_UMIN]; clamped = true; }
-        if ((clamped ? uc : d_val(u)) >= P.p[CP_UMAX]) { uc = P.p[CP_UMAX]; clamped = true; }
-        if (d_val(I) >= P.p[CP_IMAX]) {
+        auto uc = P.p[CP_UMIN];                                       // read only when clamped
+        bool clamped = d_val(u) <= d_val(uc);
+        if ((clamped ? d_val(uc) : d_val(u)) >= d_val(P.p[CP_UMAX])) { uc = P.p[CP_UMAX]; clamped = true; }
+        if (d_val(I) >= d_val(P.p[CP_IMAX])) {
             const T Ipen = P.p[CP_MUI]*(I - P.p[CP_IMAX])*(I - P.p[CP_IMAX]) / 2;
             return clamped ? rest(uc, Ipen) : rest(u, Ipen);
         }
@@ -742,8 +743,8 @@ struct CovidExact {
     }
     // model.hpp:299-304 default, H(t, X-) - H(t, X+): the lanes of the next segment own -grad H(X+)
     static constexpr bool kSwitchingReadsXp = true;
-    template <class T>
-    __device__ static __forceinline__ T switching_fn_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T (&Xp)[S])
+    template <class T, class PV>
+    __device__ static __forceinline__ T switching_fn_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], const T (&Xp)[S])
     {
         return hamiltonian_t<T>(P, sw0, sw1, t, X) - hamiltonian_t<T>(P, sw0, sw1, t, Xp);
     }

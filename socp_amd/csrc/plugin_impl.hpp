@@ -58,6 +58,10 @@
 //       template <class T> __device__ static T switching_fn_t(const socp::ModelParams &P, double sw0, double sw1, double t,
 //                                                             const T (&X)[S], const T (&Xp)[S]);
 //       static constexpr bool kSwitchingReadsXp = ...;
+//       // OPTIONAL -- the same three texts generic in the PARAMETER view as well (socp_sensitivity_batch: exact dF/dtheta): a second
+//       // template argument for anything with p[i], locals that hold a parameter `auto`, comparisons through d_val.  With
+//       // socp::ModelParams the texts are what they were (tests/plugin/osc1d_sensitivity_plugin.hip):
+//       template <class T, class PV> __device__ static void rhs_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S]);
 //   };
 //   SOCP_DEFINE_MODEL_PLUGIN(1001, MyModel, 3 /*nparams*/, 30 /*stepNbr*/, {1.0, 2.0, 3.0})
 //
@@ -65,11 +69,12 @@
 //                       -I<repo>/include my_model.hip -o libmy_model.so
 // and loaded with socp_plugin_load("libmy_model.so"); afterwards socp_ctx_create(&ctx, 1001, dev) gives a
 // context on which every entry point of socp_hip.h works (trajectories, residual, FD Jacobian, dense output,
-// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, batched exact shooting Jacobian when it has hamiltonian_t and switching_fn_t too, batched extrema, batched observables when the model has the trait, adaptive integrator, lock-step multi-start).
+// evaluation, batched trace, batched cost, batched Move(tf) / re-grid, batched events when the model has the trait, batched Jacobi fields, batched exact fields when the model has rhs_t, batched exact shooting Jacobian when it has hamiltonian_t and switching_fn_t too, batched extrema, batched observables when the model has the trait, batched exact sensitivities when the traits are generic in the parameter view, adaptive integrator, lock-step multi-start).
 #pragma once
 #include "integrator.hpp"
 #include "fields.hpp"
 #include "exact_jacobian.hpp"
+#include "sensitivity.hpp"
 #include "jacobi.hpp"
 #include "launch.hpp"
 #include "variational.hpp"
@@ -322,6 +327,46 @@ hipError_t exact_jacobian(hipStream_t st, const ModelParams &P, const ProblemDev
     return hipGetLastError();
 }
 
+// optional: rhs_t, hamiltonian_t and switching_fn_t are generic in the parameter view too (they take SeededParams, sensitivity.hpp)
+// beside everything the exact Jacobian asks for -> the model has exact parameter sensitivities (socp_sensitivity_batch)
+template <class M, class = void> struct has_sensitivity : std::false_type {};
+template <class M>
+struct has_sensitivity<M, std::void_t<decltype(M::template rhs_t<Dual>(std::declval<const SeededParams &>(), 0.0, 0.0, 0.0,
+                                                                        std::declval<const Dual (&)[M::S]>(), std::declval<Dual (&)[M::S]>())),
+                                      decltype(M::template hamiltonian_t<Dual>(std::declval<const SeededParams &>(), 0.0, 0.0, 0.0,
+                                                                                std::declval<const Dual (&)[M::S]>())),
+                                      decltype(M::template switching_fn_t<Dual>(std::declval<const SeededParams &>(), 0.0, 0.0, 0.0,
+                                                                                 std::declval<const Dual (&)[M::S]>(),
+                                                                                 std::declval<const Dual (&)[M::S]>()))>>
+    : std::bool_constant<has_exact_jacobian<M>::value> {};
+
+// the integrating directions of ONE kind of socp_sensitivity_batch: fixed-step integrator only.  G is zero-filled by the caller; one
+// group of dirs.n neighbouring lanes per (row, segment), 64 / dirs.n groups per single-wave workgroup (sensitivity.hpp); always one wave
+// per SIMD.  The translation unit must be built without contraction
+template <class Mdl, int KIND>
+hipError_t sensitivity_kind(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, const SensDirs &dirs, int K,
+                            double *G)
+{
+    const int gpw = 64 / dirs.n;
+    const long slabs = (long)B * pb.M;
+    const unsigned grid = (unsigned)((slabs + gpw - 1) / gpw);
+    if (pb.pp_params || pb.pp_time || pb.pp_xnode)
+        hipLaunchKernelGGL((sensitivity_kernel<Mdl, KIND, true>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, dirs, K, G);
+    else
+        hipLaunchKernelGGL((sensitivity_kernel<Mdl, KIND, false>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, dirs, K, G);
+    return hipGetLastError();
+}
+template <class Mdl>
+hipError_t sensitivity(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, const SensDirs &dirs, int K,
+                       double *G)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0 || dirs.n < 1 || dirs.n > kMaxTangentDirs || K < dirs.n || K > kMaxTangentDirs) return hipErrorInvalidValue;
+    if (dirs.kind == kSensParam) return sensitivity_kind<Mdl, kSensParam>(st, P, pb, B, Z, dirs, K, G);
+    if (dirs.kind == kSensTime) return sensitivity_kind<Mdl, kSensTime>(st, P, pb, B, Z, dirs, K, G);
+    return hipErrorInvalidValue;
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -329,8 +374,8 @@ struct has_variational<M, std::void_t<decltype(M::aug_rhs(std::declval<const Mod
                                       decltype(M::dhamiltonian(std::declval<const ModelParams &>(), 0.0, (const double *)nullptr,
                                                                std::declval<double (&)[M::S + 1]>()))>> : std::true_type {};
 
-// FIELDS = false: leave the fields and exact_jacobian entries to the caller (the in-tree models' entries live in kernels_fields.hip and
-// kernels_exact_jacobian.hip, builtin_tables.hpp)
+// FIELDS = false: leave the fields, exact_jacobian and sensitivity entries to the caller (the in-tree models' entries live in
+// kernels_fields.hip, kernels_exact_jacobian.hip and kernels_sensitivity.hip, builtin_tables.hpp)
 template <class Mdl, bool FIELDS = true>
 ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> defaults)
 {
@@ -356,6 +401,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     if constexpr (!has_custom_traj<Mdl>::value && !no_jacobi<Mdl>::value) t.jacobi = &jacobi<Mdl>;   // nor Jacobi fields (their chart changes rewrite the costate)
     if constexpr (FIELDS && has_fields<Mdl>::value && !has_custom_traj<Mdl>::value) t.fields = &fields<Mdl>;
     if constexpr (FIELDS && has_exact_jacobian<Mdl>::value) t.exact_jacobian = &exact_jacobian<Mdl>;
+    if constexpr (FIELDS && has_sensitivity<Mdl>::value) t.sensitivity = &sensitivity<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

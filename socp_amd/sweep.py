@@ -497,6 +497,24 @@ def tangent_local(ctx, args, local, lo, rank, params=None):
             "median_norm_dz": float(np.median(np.linalg.norm(dz[solved], axis=1))) if solved.any() else None, "wall_s": wall, "file": path}
 
 
+def sensitivity_local(ctx, args, local, lo, rank, params=None):
+    """--sens-out: the EXACT sensitivity dz/dtheta (socp_sensitivity_batch: the exact shooting Jacobian and the exact dF/dtheta of the
+    discrete flow, nothing differenced) of this rank's CONVERGED chains to the packed parameter --sens-param, each chain with its own
+    parameter block when the chains have one, written to PATH.rank<r>.npz: index [k] = position of the chain in the sweep's start
+    table, dz [k][n], info [k] (0: solved), theta [k] = the chain's value of the parameter, z [k][n] = the unknown vectors
+    differentiated, g [k][n] = dF/dtheta.  Runs after the timed solve.  Returns the record entry of this rank."""
+    from . import capi
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.sens_out)
+    slot = capi.GODDARD_PARAM_NAMES.index(args.sens_param)
+    theta = np.full(len(conv), ctx.get_params()[slot]) if own is None else own[:, slot].copy()
+    r = ctx.sensitivity_batch(z, [(capi.DIR_PARAM, slot)], params=own, g=True)
+    dz, info, g = r["dz"][:, 0, :], r["info"], r["g"][:, 0, :]
+    np.savez(path, index=index, dz=dz, info=info, theta=theta, z=z, g=g)
+    solved = info == 0
+    return {"parameter": args.sens_param, "rows": int(len(conv)), "refused": int(np.sum(~solved)),
+            "dz_norm_median": float(np.median(np.linalg.norm(dz[solved], axis=1))) if solved.any() else None, "file": path}
+
+
 def singular_local(ctx, args, local, lo, rank, params=None):
     """--sing-out: the singular values of the shooting Jacobian (socp_singular_batch) at this rank's CONVERGED chains, each with its
     own parameter block when the chains have one; --sing-scale 1 brings the columns to unit norm first.  Written to PATH.rank<r>.npz:
@@ -736,6 +754,15 @@ def main():
     ap.add_argument("--tangent-param", default="KD", metavar="NAME",
                     help="with --tangent-out: the parameter, by its name in the model's packed block (C, b, KD, kr, u_max, mu1, mu2, "
                          "singularControl)")
+    ap.add_argument("--sens-out", default=None, metavar="PATH",
+                    help="after the timed solve, each rank computes the EXACT sensitivity dz/dtheta of the converged chains of its own block "
+                         "to one packed parameter in one batch (socp_sensitivity_batch: exact Jacobian, exact dF/dtheta), with the chains' "
+                         "own parameter blocks, writes PATH.rank<r>.npz (index, dz, info, theta, z, g) and adds sensitivity {parameter, "
+                         "rows, refused, dz_norm_median, file} to the record.  Not with --model interceptor.  Absent: the timed wall and "
+                         "the printed record are unchanged")
+    ap.add_argument("--sens-param", default="KD", metavar="NAME",
+                    help="with --sens-out: the parameter, by its name in the model's packed block (C, b, KD, kr, u_max, mu1, mu2, "
+                         "singularControl)")
     ap.add_argument("--roots-out", default=None, metavar="PATH",
                     help="after the timed solve, rank 0 groups the converged rows of the gathered table into distinct roots in one call "
                          "(socp_group_batch: greedy in start order, a row joins the FIRST leader l with |z_i - l_i| <= atol + rtol |l_i| for "
@@ -857,6 +884,12 @@ def main():
         from .capi import GODDARD_PARAM_NAMES            # (the module only: the library is loaded by the first context)
         if args.tangent_param not in GODDARD_PARAM_NAMES:
             ap.error("--tangent-param: not a name of the packed parameter block (%s)" % ", ".join(GODDARD_PARAM_NAMES))
+    if args.sens_out and args.model == "interceptor":
+        ap.error("--sens-out: the interceptor has no sensitivity kernel (its own ComputeTraj and final rows)")
+    if args.sens_out:
+        from .capi import GODDARD_PARAM_NAMES
+        if args.sens_param not in GODDARD_PARAM_NAMES:
+            ap.error("--sens-param: not a name of the packed parameter block (%s)" % ", ".join(GODDARD_PARAM_NAMES))
     if args.branch_out and args.model == "interceptor":
         ap.error("--branch-out is implemented for the Goddard sweeps")
     if args.branch_out:
@@ -986,6 +1019,8 @@ def main():
         extra["events_rank%d" % rank] = events_local(ctx, args, local, lo_w, rank, blocks)
     if args.tangent_out:
         extra["tangent_rank%d" % rank] = tangent_local(ctx, args, local, lo_w, rank, blocks)
+    if args.sens_out:
+        extra["sensitivity" if rank == 0 else "sensitivity_rank%d" % rank] = sensitivity_local(ctx, args, local, lo_w, rank, blocks)
     if args.jacobi_out:
         extra["jacobi" if rank == 0 else "jacobi_rank%d" % rank] = jacobi_local(ctx, args, local, lo_w, rank, blocks)
     if args.fields_out:
