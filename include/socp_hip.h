@@ -1050,6 +1050,49 @@ int socp_sensitivity_batch_blocks(socp_ctx *ctx, int B, const double *Z, const d
                                   const double *xnode, int K, const int *dir_kind, const int *dir_index, double *dZ, int *info,
                                   double *Gp);
 
+/* HAMILTONIAN GRADIENT: the costate equations a model's Hamiltonian text implies, G = (dH/dp, -dH/dx), at a batch of points -- the
+ * check of a hand-written right-hand side against its Hamiltonian, and the right-hand side of a model that brings no dynamics at all
+ * (include/socp_plugin.h, "A MODEL FROM ITS HAMILTONIAN").  A model-authoring instrument: no problem has to be set, there is no sweep
+ * flag and no per-row parameter block.
+ * t[B], sw[B][2] (or NULL: the context's switching times), X[B][S] exactly as socp_eval_batch takes them -> G[B][S], directly comparable
+ * with what SOCP_EVAL_RHS writes.  One lane per point, ONE launch.  Per point, with H = the model's hamiltonian_t (the Hamiltonian
+ * over a number type, the control law evaluated INSIDE it: X -> H(X, u(X))):
+ *   1. Y[i] = (X[i]; e_i), i < S: the value X[i] and S derivative parts, 1.0 in part i and +0.0 elsewhere.
+ *   2. h = hamiltonian_t(P, sw0, sw1, t, Y) on numbers with S derivative parts.  Part k of every operation is the DUAL NUMBERS rule
+ *      of socp_fields_batch on (v, d[k]), one IEEE rounding per listed step, no contraction; the value part and whatever reads value
+ *      parts only (a quotient's q = a.v / b.v, a root's s + s, exp's e) is computed once.  A plain double (a parameter, a literal, t,
+ *      a control or penalty the law makes a constant) takes part with its zero terms DROPPED, as there.  Parts never meet, so part k
+ *      is what a single dual number seeded with e_k gives, bit for bit: the result does not depend on how many directions travel in
+ *      one evaluation (the kernel may cut the S directions into passes of any width; it takes one pass for every in-tree model).
+ *   3. G[i] = h.d[i + d] and G[i + d] = -(h.d[i]) for i < d: one unary minus, nothing else.
+ * WHAT IT IS: the TOTAL derivative of X -> H(X, u(X)).  It equals Pontryagin's x' = dH/dp, p' = -dH/dx (partials at fixed u) where
+ * the law minimises H(X, .) over a set that does not depend on X -- at an interior minimiser dH/du = 0, on the set's boundary the
+ * extra term is a multiplier times the derivative of a constraint X does not move (envelope theorem) -- up to the rounding of the
+ * rules above.  A kink (a clamp, a penalty's onset, Goddard's t <= sw0) differentiates the BRANCH TAKEN at X.  A law that is not such
+ * a minimiser gives something else, and its model needs a hand-written right-hand side.  For the in-tree models (measured in 240
+ * bits, tests/test_hamiltonian_model_cpu.py): the double integrator on both sides of its saturation, and Goddard with the thrust
+ * saturated, interior and off (mu2 > 0) and full, at a given singular value and off (mu2 = 0) agree with their right-hand sides to
+ * rounding.  Goddard's CLOSED-FORM singular control (mu2 = 0, singularControl < 0, sw0 < t <= sw1) is a feedback that minimises H only
+ * ON the singular surface Switch = mu1 - b p_m - C |p_v| / m = 0: there G agrees too; off it G - rhs = Switch (d alpha/dp, -d alpha/dx)
+ * with alpha the singular thrust -- not an error of either text, but a model written from H alone would leave that surface where the
+ * hand-written dynamics stay on it.  covid19 does NOT agree in rows 4 and 6, by exactly (pS - pE) (Rt - R) I / Tinf / N and
+ * (pS - pE) (Rt - R) S / Tinf / N with Rt = R0 (1 - u): the upstream dynamics (covid19.cpp:88,90) multiply by the state R = X[3] where
+ * -dH/dx has Rt.  The library keeps the upstream text for parity, bit for bit; the call is how to see it.
+ * ONE OBJECT, NO CONTRACTION: a throughput-flavour context returns the same bits.  Goddard takes the law from the context's mu2 as
+ * socp_eval_batch does.  tests/hamiltonian_model_reference.py restates the definition; the tests compare whole buffers to it.
+ * socp_ctx_has_hamiltonian_gradient: 1 when the model's launch table has the entry -- any model with the hamiltonian_t trait: Goddard,
+ * the double integrator, covid19, a plugin that brings it -- else 0 (the interceptor, vtolUAV, a plugin without the trait).
+ * socp_ctx_counters advances by one launch and no trajectory.  SOCP_ERR_ARG: B < 0, or t, X or G NULL with B > 0.
+ * SOCP_ERR_UNSUPPORTED: the launch table has no hamiltonian_gradient entry (a plugin built before launch-table ABI 16 is refused when
+ * it registers: rebuild it).  B == 0: SOCP_OK without a launch.  An error writes nothing and leaves the context and its counters
+ * unchanged.  The _dev form takes device pointers, only enqueues on the context's stream and neither allocates, copies nor
+ * synchronises; the host form stages through that stream and the context's grow-only buffers.
+ * Not covered: per-row parameter blocks, second derivatives (exact fields of a model written from H alone), reverse mode. */
+int socp_ctx_has_hamiltonian_gradient(const socp_ctx *ctx);      /* 1 / 0; SOCP_ERR_ARG for a NULL context */
+int socp_hamiltonian_gradient_batch_dev(socp_ctx *ctx, int B, const double *d_t, const double *d_sw /* or NULL */, const double *d_X,
+                                        double *d_G);
+int socp_hamiltonian_gradient_batch(socp_ctx *ctx, int B, const double *t, const double *sw /* or NULL */, const double *X, double *G);
+
 /* The distinct roots of a whole sweep: which distinct rows does a table hold, how many rows went to each, and which row went where.
  * Model-independent (no problem has to be set, no launch table is used).
  * Rows V[B][ld]; the first n <= ld entries of a row are compared.  Greedy leader grouping IN ROW ORDER:

@@ -66,6 +66,24 @@
  * and the call returns SOCP_ERR_UNSUPPORTED.  A plugin built against an older launch table (ABI <= 14) is refused at registration:
  * rebuild it.
  *
+ * Launch-table ABI 16 adds the Hamiltonian-gradient launcher (socp_hamiltonian_gradient_batch, socp_hip.h).  Its trait is hamiltonian_t
+ * alone, in either of the two ways above: any model that has it gets the entry.
+ *   CHECKING A HAND-WRITTEN MODEL.  The call returns G = (dH/dp, -dH/dx) of the model's own Hamiltonian text, by dual numbers, at the
+ * points socp_eval_batch takes; compare it with SOCP_EVAL_RHS at states on every arc of the control law.  The two agree to rounding
+ * where the law minimises H over a set that does not depend on the state (socp_hip.h says what G is otherwise); a row that is off
+ * by more than rounding is a derivation error in rhs or in hamiltonian -- or a property to write down, as covid19's rows 4 and 6 are.
+ *   A MODEL FROM ITS HAMILTONIAN.  A struct that brings only D, S, NU, kRefOrder, control_only and hamiltonian_t (T = double must
+ * work: it is the model's Hamiltonian) becomes a whole model through
+ *   SOCP_DEFINE_HAMILTONIAN_PLUGIN(MODEL_ID, MDL, NPARAMS, STEP_NBR, {defaults})
+ * which registers socp::plugin::FromHamiltonian<MDL> (socp_amd/csrc/hamiltonian_model.hpp): rhs = that gradient, hamiltonian =
+ * hamiltonian_t<double>, switching_fn = H(t, X-) - H(t, X+) unless MDL has one; event channels, observables and a switching_fn of
+ * MDL's own pass through.  Trajectories, residuals, FD Jacobians, hybrd sweeps, trace, cost, move, extrema, events and observe then
+ * run through the unchanged launch-table kernels (tests/plugin/osc1d_h_plugin.hip, dint_h_plugin.hip).  Build with
+ * -ffp-contract=off.  Such a model has no rhs_t -- the gradient of a gradient needs nested dual numbers -- so it has no fields,
+ * exact-Jacobian or sensitivity entry and no variational equations; a right-hand side costs (1 + S) x the operations of H.  An
+ * optional hint `static constexpr int kGradientWidth = W;` cuts the S directions into passes of W (registers against time, never a
+ * bit).  A plugin built against an older launch table (ABI <= 15) is refused at registration: rebuild it.
+ *
  * Model ids below SOCP_PLUGIN_ID_MIN are reserved for in-tree models.
  */
 #ifndef SOCP_PLUGIN_H_

@@ -213,6 +213,9 @@ def lib():
         L.socp_sensitivity_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _ip, _vp, C.c_size_t, _vp, _vp, _vp]
         L.socp_sensitivity_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _ip, _dp, _ip, _dp]
         L.socp_sensitivity_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, _dp, _ip, _dp]
+        L.socp_ctx_has_hamiltonian_gradient.argtypes = [_vp]
+        L.socp_hamiltonian_gradient_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
+        L.socp_hamiltonian_gradient_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
         L.socp_linsolve_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
         L.socp_svd_batch_dev.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_branch_work_bytes.argtypes = [_vp, C.c_int]
@@ -567,6 +570,32 @@ class Context:
             swp = _d(sw)
         self._chk(self.L.socp_eval_batch(self.h, what, B, _d(t), swp, _d(X), X.shape[1], _d(out), int(is_jac)))
         return out
+
+    # -- Hamiltonian gradient
+    def has_hamiltonian_gradient(self):
+        """Whether this model has the Hamiltonian-gradient kernel (socp_ctx_has_hamiltonian_gradient): any model with the
+        hamiltonian_t trait -- the in-tree Goddard, double integrator and covid19, a plugin that brings it."""
+        return self.L.socp_ctx_has_hamiltonian_gradient(self.h) == 1
+
+    def hamiltonian_gradient_batch_dev(self, B, d_t, d_sw, d_X, d_G):
+        """Device pointers (ints; d_sw may be None): t[B], sw[B][2], X[B][S] -> G[B][S]; one launch, enqueue only, no allocation, no
+        copy, no synchronise (socp_hamiltonian_gradient_batch_dev)."""
+        self._chk(self.L.socp_hamiltonian_gradient_batch_dev(self.h, int(B), _vp(d_t), _vp(d_sw), _vp(d_X), _vp(d_G)))
+
+    def hamiltonian_gradient_batch(self, t, X, sw=None):
+        """G[B][S] = (dH/dp, -dH/dx) of the model's Hamiltonian text at the points (t, X[B][S]), by dual numbers through
+        hamiltonian_t, the control law inside (include/socp_hip.h has the definition and says when this equals the costate
+        equations).  Takes t, X and sw as eval_batch does; directly comparable with eval_batch(EVAL_RHS, t, X, sw)."""
+        X = _f64(X).reshape(-1, self.s)
+        B = X.shape[0]
+        t = _f64(np.broadcast_to(t, (B,)))
+        G = np.full((B, self.s), np.nan)
+        swp = None
+        if sw is not None:
+            sw = _f64(sw)
+            swp = _d(sw)
+        self._chk(self.L.socp_hamiltonian_gradient_batch(self.h, B, _d(t), swp, _d(X), _d(G)))
+        return G
 
     def var_jacobian(self, z):
         """Analytic (variational) shooting Jacobian J[row, col] (hybrj path)."""

@@ -44,6 +44,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.fields = &fields_goddard;                  // kernels_fields.hip: the same reference-order object in both flavours
         t.exact_jacobian = &exact_jacobian_goddard;  // kernels_exact_jacobian.hip: likewise
         t.sensitivity = &sensitivity_goddard;        // kernels_sensitivity.hip: likewise
+        t.hamiltonian_gradient = &hamiltonian_gradient_goddard;      // kernels_hamiltonian.hip: likewise
         t.traj = &goddard_by_params<&plugin::traj<GodSmooth>, &plugin::traj<God>>;
         t.eval = &goddard_by_params<&plugin::eval<GodSmooth>, &plugin::eval<God>>;
         t.residual = &goddard_by_problem<&plugin::residual<GodSmooth>, &plugin::residual<God>>;
@@ -65,6 +66,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.fields = &fields_dint;
         t.exact_jacobian = &exact_jacobian_dint;
         t.sensitivity = &sensitivity_dint;
+        t.hamiltonian_gradient = &hamiltonian_gradient_dint;
         return t;
     }();
     // covid19.cpp:25-38 defaults; its ModelInt integrates with its own stepNbr = 1000
@@ -73,6 +75,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.fields = &fields_covid;
         t.exact_jacobian = &exact_jacobian_covid;
         t.sensitivity = &sensitivity_covid;
+        t.hamiltonian_gradient = &hamiltonian_gradient_covid;
         return t;
     }();
     switch (model_id) {

@@ -656,6 +656,52 @@ int socp_eval_batch(socp_ctx *c, int what, int B, const double *t, const double 
     return SOCP_OK;
 }
 
+/* ---- Hamiltonian gradient: (dH/dp, -dH/dx) of the model's hamiltonian_t by dual numbers ------ */
+
+int socp_ctx_has_hamiltonian_gradient(const socp_ctx *c) { return c ? (table_of(c)->hamiltonian_gradient ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+// every refusal comes before anything is counted, reserved or enqueued
+int hamiltonian_gradient_args(socp_ctx *c, int B, const void *t, const void *X, const void *G)
+{
+    if (B < 0 || (B > 0 && (!t || !X || !G))) return fail(c, SOCP_ERR_ARG, "hamiltonian_gradient_batch: B >= 0 and non-null t, X, G are required");
+    if (!table_of(c)->hamiltonian_gradient)
+        return fail(c, SOCP_ERR_UNSUPPORTED, "hamiltonian_gradient_batch: this model's launch table has no hamiltonian_gradient entry (a model "
+                                             "without the hamiltonian_t trait)");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_hamiltonian_gradient_batch_dev(socp_ctx *c, int B, const double *d_t, const double *d_sw, const double *d_X, double *d_G)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = hamiltonian_gradient_args(c, B, d_t, d_X, d_G)) return rc;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->hamiltonian_gradient(c->stream, c->P, B, d_t, d_sw, d_X, d_G));
+    return SOCP_OK;
+}
+
+int socp_hamiltonian_gradient_batch(socp_ctx *c, int B, const double *t, const double *sw, const double *X, double *G)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = hamiltonian_gradient_args(c, B, t, X, G)) return rc;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nX = (size_t)B * c->S;
+    double *d_t, *d_X, *d_sw = nullptr;
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * nX));
+    HIP_TRY(c, stage_up(c, c->s_t0, t, B, d_t));
+    HIP_TRY(c, stage_up(c, c->s_in, X, nX, d_X));
+    if (sw) HIP_TRY(c, stage_up(c, c->s_sw, sw, (size_t)2 * B, d_sw));
+    const int rc = socp_hamiltonian_gradient_batch_dev(c, B, d_t, d_sw, d_X, c->s_out.as<double>());
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, G, c->s_out.as<double>(), nX));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
 /* ---- shooting problem --------------------------------------------------------------------- */
 
 int socp_problem_set(socp_ctx *c, int M, const int *mode_t, const int *mode_x, const double *time, const double *xnode)

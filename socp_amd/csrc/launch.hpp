@@ -39,7 +39,7 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 15;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 16;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
@@ -47,6 +47,7 @@ constexpr int kPluginAbi = 15;     // 3: ProblemDev carries per-problem blocks; 
                                    // kPluginAbi = 13: batched exact shooting-Jacobian launcher
                                    // kPluginAbi = 14: batched observables launcher
                                    // kPluginAbi = 15: batched exact-sensitivities launcher
+                                   // kPluginAbi = 16: Hamiltonian-gradient launcher
 // the integrating directions of one kind of socp_sensitivity_batch as they travel to the kernel (sensitivity.hpp): 16 bits per
 // direction, four to a word.  slot: the direction's place k in the call's table (4 bits each); index: the parameter or the node
 constexpr int kSensParam = 0, kSensTime = 1;
@@ -115,6 +116,11 @@ struct ModelLaunchers {
     // its rhs_t / hamiltonian_t / switching_fn_t are not generic in the parameter view (plugin_impl.hpp).  The in-tree models' entries
     // live in kernels_sensitivity.hip, one object without contraction that both flavours' tables point to
     hipError_t (*sensitivity)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, const SensDirs &, int, double *);
+    // Hamiltonian gradient (socp_hamiltonian_gradient_batch): t[B], sw[B][2] or null, X[B][S] -> G[B][S] = (dH/dp, -dH/dx) of the
+    // model's hamiltonian_t by dual numbers (hamiltonian_model.hpp), the arguments of `eval`; ONE launch.  Null: the model has no
+    // hamiltonian_t trait (plugin_impl.hpp).  The in-tree models' entries live in kernels_hamiltonian.hip, one object without
+    // contraction that both flavours' tables point to
+    hipError_t (*hamiltonian_gradient)(hipStream_t, const ModelParams &, int, const double *, const double *, const double *, double *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
@@ -278,6 +284,13 @@ hipError_t sensitivity_covid(hipStream_t st, const ModelParams &P, const Problem
                              double *G);
 hipError_t sensitivity_finish(hipStream_t st, const ProblemDev &pb, int B, int K, unsigned xnode_mask, const unsigned long long (&index)[4],
                               double *G, double *rhs);
+
+// socp_hamiltonian_gradient_batch of the in-tree models (kernels_hamiltonian.hip: one object without contraction, for both flavours);
+// Goddard's picks the law from the context's mu2 like its eval entry
+hipError_t hamiltonian_gradient_goddard(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X,
+                                        double *G);
+hipError_t hamiltonian_gradient_dint(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X, double *G);
+hipError_t hamiltonian_gradient_covid(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X, double *G);
 
 // the in-tree models' tables, one translation unit each
 // Goddard, double integrator, covid19 by SOCP_MODEL_* id (builtin_tables.hpp); null for any other id

@@ -62,6 +62,9 @@
 //       // template argument for anything with p[i], locals that hold a parameter `auto`, comparisons through d_val.  With
 //       // socp::ModelParams the texts are what they were (tests/plugin/osc1d_sensitivity_plugin.hip):
 //       template <class T, class PV> __device__ static void rhs_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S]);
+//       // hamiltonian_t ALONE already gives the model socp_hamiltonian_gradient_batch: (dH/dp, -dH/dx) of that text by dual numbers,
+//       // the check of rhs against it (hamiltonian_model.hpp).  And a struct with control_only and hamiltonian_t and NO rhs at all is
+//       // a whole model through SOCP_DEFINE_HAMILTONIAN_PLUGIN below (tests/plugin/dint_h_plugin.hip).
 //   };
 //   SOCP_DEFINE_MODEL_PLUGIN(1001, MyModel, 3 /*nparams*/, 30 /*stepNbr*/, {1.0, 2.0, 3.0})
 //
@@ -75,6 +78,7 @@
 #include "fields.hpp"
 #include "exact_jacobian.hpp"
 #include "sensitivity.hpp"
+#include "hamiltonian_model.hpp"
 #include "jacobi.hpp"
 #include "launch.hpp"
 #include "variational.hpp"
@@ -367,6 +371,23 @@ hipError_t sensitivity(hipStream_t st, const ModelParams &P, const ProblemDev &p
     return hipErrorInvalidValue;
 }
 
+// optional trait hamiltonian_t alone -> the model has the Hamiltonian gradient (socp_hamiltonian_gradient_batch): the check of a
+// hand-written rhs against its Hamiltonian text (hamiltonian_model.hpp)
+template <class M, class = void> struct has_hamiltonian_gradient : std::false_type {};
+template <class M>
+struct has_hamiltonian_gradient<M, std::void_t<decltype(M::template hamiltonian_t<DualN<1>>(std::declval<const ModelParams &>(), 0.0, 0.0, 0.0,
+                                                                                            std::declval<const DualN<1> (&)[M::S]>()))>>
+    : std::true_type {};
+
+// one lane per point, one launch, like eval.  The translation unit must be built without contraction
+template <class Mdl>
+hipError_t hamiltonian_gradient(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X, double *G)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(hamiltonian_gradient_kernel<Mdl>, dim3(blocks_for(B)), dim3(64), 0, st, P, B, t, sw, X, G);
+    return hipGetLastError();
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -374,8 +395,9 @@ struct has_variational<M, std::void_t<decltype(M::aug_rhs(std::declval<const Mod
                                       decltype(M::dhamiltonian(std::declval<const ModelParams &>(), 0.0, (const double *)nullptr,
                                                                std::declval<double (&)[M::S + 1]>()))>> : std::true_type {};
 
-// FIELDS = false: leave the fields, exact_jacobian and sensitivity entries to the caller (the in-tree models' entries live in
-// kernels_fields.hip, kernels_exact_jacobian.hip and kernels_sensitivity.hip, builtin_tables.hpp)
+// FIELDS = false: leave the fields, exact_jacobian, sensitivity and hamiltonian_gradient entries to the caller (the in-tree models'
+// entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip and kernels_hamiltonian.hip,
+// builtin_tables.hpp)
 template <class Mdl, bool FIELDS = true>
 ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> defaults)
 {
@@ -402,6 +424,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     if constexpr (FIELDS && has_fields<Mdl>::value && !has_custom_traj<Mdl>::value) t.fields = &fields<Mdl>;
     if constexpr (FIELDS && has_exact_jacobian<Mdl>::value) t.exact_jacobian = &exact_jacobian<Mdl>;
     if constexpr (FIELDS && has_sensitivity<Mdl>::value) t.sensitivity = &sensitivity<Mdl>;
+    if constexpr (FIELDS && has_hamiltonian_gradient<Mdl>::value) t.hamiltonian_gradient = &hamiltonian_gradient<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }
@@ -418,3 +441,8 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
         static const socp::ModelLaunchers t = socp::plugin::table<MDL>(NPARAMS, STEP_NBR, __VA_ARGS__);   \
         return socp_register_model(MODEL_ID, &t, (int)sizeof(t));                                         \
     }
+
+// the same for a model written from its Hamiltonian alone: MDL brings control_only and hamiltonian_t, the right-hand side is
+// symplectic_gradient (hamiltonian_model.hpp: plugin::FromHamiltonian).  Build the plugin with -ffp-contract=off
+#define SOCP_DEFINE_HAMILTONIAN_PLUGIN(MODEL_ID, MDL, NPARAMS, STEP_NBR, ...)                             \
+    SOCP_DEFINE_MODEL_PLUGIN(MODEL_ID, socp::plugin::FromHamiltonian<MDL>, NPARAMS, STEP_NBR, __VA_ARGS__)
