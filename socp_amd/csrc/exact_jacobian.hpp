@@ -2,7 +2,7 @@
 // the definition is the comment of the entry points in include/socp_hip.h, tests/exact_jacobian_reference.py restates it in Python).
 //
 // The kernel shape of fields_group_kernel (fields.hpp): the S + 1 columns of one (row, segment) take identical steps, so they sit
-// in G = S + 1 NEIGHBOURING lanes of one wavefront, 64 / G groups per wave (the remaining lanes idle).  Lane c < S carries the
+// in G = S + 1 NEIGHBOURING lanes of one wavefront (group_lane, segment_views.hpp).  Lane c < S carries the
 // state as S dual numbers started from (X0, e_c): column S i + c of the matrix, the unknown z[S i + c].  Lane S -- the LENGTH lane --
 // starts from (X0, 0) and carries the derivative with respect to the segment's length L = t2 - t1: t2 = (t2, 1.0) there, (t2, +0.0)
 // in the state lanes.  ONE text for every lane: the step length is a dual number in all of them, h F is the full dual product, and
@@ -13,9 +13,10 @@
 // depends on the NEXT segment's start state is stored by that segment's state lanes, which own those columns: every entry of the
 // matrix has one writer, so there is no atomic and no second launch; the matrix is zero-filled on the stream before the launch
 // (plugin_impl.hpp).  Every store site is ONE block under ONE computed predicate; no register array is indexed by a run-time
-// value (see the note in segment_residual).  Idle and tail lanes integrate a copy of the launch's last slab and store nothing.
+// value (see the note in segment_residual).
 #pragma once
 #include "dual.hpp"
+#include "fields.hpp"
 #include "integrator.hpp"
 
 namespace socp {
@@ -24,32 +25,6 @@ namespace socp {
 // of the next segment store -grad H(X+).  Absent or false: the row does not read X+ (Goddard: goddard.cpp:343-370)
 template <class M, class = void> struct switching_reads_xp : std::false_type {};
 template <class M> struct switching_reads_xp<M, std::void_t<decltype(M::kSwitchingReadsXp)>> : std::bool_constant<M::kSwitchingReadsXp> {};
-
-// Lane::rk4's reference-order arm (odeTools.cpp:89-98) on dual numbers with a DUAL step; the right-hand side is given the value
-// part of the stage time
-template <class Mdl>
-__device__ __forceinline__ void exact_jacobian_rk4(const ModelParams &P, double sw0, double sw1, const Dual &t, Dual (&X)[Mdl::S],
-                                                   const Dual &step)
-{
-    constexpr int S = Mdl::S;
-    Dual F1[S], Fs[S], F[S], Y[S];
-    const Dual h2 = step / 2.0;
-    const Dual th = t + step / 2.0;
-    Mdl::template rhs_t<Dual>(P, sw0, sw1, t.v, X, F1);
-#pragma unroll
-    for (int i = 0; i < S; i++) Y[i] = X[i] + h2 * F1[i];
-    Mdl::template rhs_t<Dual>(P, sw0, sw1, th.v, Y, Fs);               // F2
-#pragma unroll
-    for (int i = 0; i < S; i++) Y[i] = X[i] + h2 * Fs[i];
-    Mdl::template rhs_t<Dual>(P, sw0, sw1, th.v, Y, F);                // F3
-#pragma unroll
-    for (int i = 0; i < S; i++) { Y[i] = X[i] + step * F[i]; Fs[i] = Fs[i] + F[i]; }   // F2 + F3
-    const Dual te = t + step;
-    Mdl::template rhs_t<Dual>(P, sw0, sw1, te.v, Y, F);                // F4
-    const Dual h6 = step / 6.0;
-#pragma unroll
-    for (int i = 0; i < S; i++) X[i] = X[i] + h6 * (F1[i] + (F[i] + 2.0 * Fs[i]));
-}
 
 // c(j, f): the weight of junction f's time in node j's (Timeline::nt): 1.0 for j == f; (double)(j - a) / (double)(b - a) for
 // f == b, 1.0 minus that for f == a when node j is interpolated between the junctions a and b; 0.0 otherwise
@@ -72,27 +47,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     constexpr int S = Mdl::S;
     constexpr int D = Mdl::D;
     constexpr int G = S + 1;                                          // one lane per column: S state columns and the length
-    constexpr int GPW = 64 / G;                                       // groups per wavefront
     static_assert(G <= 64, "a group fits one wavefront");
-    const int lane = threadIdx.x;
-    const int g = lane / G;
-    const int c = lane - g * G;                                       // column
-    const long total = (long)B * pb.M;
-    const long Tl = (long)blockIdx.x * GPW + g;
-    const bool live = g < GPW && Tl < total;
-    const long T = live ? Tl : total - 1;                             // = b * M + i
-    const long b = T / pb.M;
-    const int i = (int)(T - b * pb.M);
-    const double *zr = Z + b * pb.n;
+    const GroupLane L = group_lane(B, pb.M, G);
+    const double *zr = Z + L.b * pb.n;
     auto z = [=](int k) -> double { return zr[k]; };
     ModelParams Pq = P;
     ProblemDev pq = pb;
-    if constexpr (PERPROB) load_problem_block(pb, b, Pq, pq);
+    if constexpr (PERPROB) load_problem_block(pb, L.b, Pq, pq);
+    const int c = L.c, i = L.i;
+    const long b = L.b;
+    const bool live = L.live;
     const int M = pq.M, n = pq.n;
-
-    const Timeline<decltype(z)> tl{pq, z};
-    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
-    const double sw0 = tl.template switching_time<Mdl>(Pq.sw0, pq.sw_node0), sw1 = tl.template switching_time<Mdl>(Pq.sw1, pq.sw_node1);
+    double X0[S];
+    const SegmentSpan<Mdl> sp(Pq, pq, z, i, X0);
+    const double t1 = sp.t1, t2 = sp.t2, sw0 = sp.sw0, sw1 = sp.sw1;
 
     const bool len = c == S;                                          // the length lane
     const bool ws = live && !len;                                     // stores derivative parts into its own column S i + c
@@ -102,12 +70,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     double *const Fb = Fout + (Fout != nullptr ? b * n : 0);
 
     Dual X[S];
-    {
-        double X0[S];
-        segment_start(z, S * i, X0);
-#pragma unroll
-        for (int j = 0; j < S; j++) X[j] = Dual(X0[j], j == c ? 1.0 : 0.0);
-    }
+    dual_start(X0, c, X);                                             // the length lane: c == S, no unit entry
 
     // ---- the rows that read the segment's START state: the length lane has no part in them
     if (i == 0) {
@@ -148,16 +111,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         }
     }
 
-    // ---- the loop of Lane::integrate on duals: t1 = (t1, 0), t2 = (t2, delta), delta = 1.0 in the length lane
-    const Dual t2d(t2, len ? 1.0 : 0.0);
-    const Dual dt = (t2d - Dual(t1, 0.0)) / (double)Pq.step_nbr;
-    Dual t(t1, 0.0);
-    int guard = Pq.step_nbr + 8;
-    while (t.v < (t2 - dt.v / 2) && guard-- > 0) {
-        const Dual step = (t.v + dt.v > t2) ? (t2d - t) : dt;
-        exact_jacobian_rk4<Mdl>(Pq, sw0, sw1, t, X, step);
-        t = t + dt;
-    }
+    // ---- the steps: t2 = (t2, delta), delta = 1.0 in the length lane
+    fixed_steps_dual(Pq.step_nbr, t1, Dual(t2, len ? 1.0 : 0.0),
+                     [&](const Dual &t, const Dual &step) { dual_rk4<Mdl>(Pq, sw0, sw1, t, X, step); });
 
     // ---- the free times this segment's length depends on: the junctions A <= i and Bn >= i + 1 that bracket it
     const int A = pq.node_kind[i] == -2 ? pq.lo[i] : i;

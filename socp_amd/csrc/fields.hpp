@@ -2,15 +2,16 @@
 // comment of the entry points in include/socp_hip.h, tests/fields_reference.py restates it in Python).
 //
 // Modelled on jacobi_group_kernel (jacobi.hpp): the C columns of one (row, segment) take identical steps, so they sit in G = C
-// NEIGHBOURING lanes of one wavefront, 64 / G groups per wave (the remaining lanes idle).  Lane c carries the state as S dual
+// NEIGHBOURING lanes of one wavefront (group_lane, segment_views.hpp).  Lane c carries the state as S dual
 // numbers (dual.hpp): the value parts are the residual's trajectory, the same in every lane of the group, the derivative parts
 // are column c of the transition matrix dX(t)/dX(t_i) -- column d + c with cols = COSTATE.  Nothing is differenced, so no base
 // trajectory and no step length: the lanes only meet in the determinant, which is jacobi_det's elimination across the lanes
 // that hold the costate columns (lanes base + OFF .. base + OFF + D, OFF = 0 or D).
-// The loop over the SAMPLES is wave-uniform, the residual-shaped per-lane step loop sits inside it; idle and tail lanes integrate
-// a copy of the launch's last slab and store nothing; every store site is ONE block under ONE computed predicate; no register
-// array is indexed by a run-time value.  A lane holds 2 S doubles per RK4 array (five arrays): the Goddard instantiations live
+// The loop over the SAMPLES is wave-uniform, the residual-shaped per-lane step loop sits inside it, as in jacobi_group_kernel.
+// A lane holds 2 S doubles per RK4 array (five arrays): the Goddard instantiations live
 // in the 264 .. 512-register step at one wave per SIMD, which is what the kernel asks for (profiles/fields_kernel_meta.txt).
+//
+// Also here, for this kernel, exact_jacobian.hpp and sensitivity.hpp: the RK4 step and the fixed-step loop on dual numbers.
 #pragma once
 #include "dual.hpp"
 #include "integrator.hpp"
@@ -18,28 +19,53 @@
 
 namespace socp {
 
-// Lane::rk4's reference-order arm (odeTools.cpp:89-98) on dual numbers; t and step are plain doubles.  PV: ModelParams, or the
-// dual view of a parameter block (sensitivity.hpp)
-template <class Mdl, class PV>
-__device__ __forceinline__ void fields_rk4(const PV &P, double sw0, double sw1, double t, Dual (&X)[Mdl::S], double step)
+// Lane::rk4's reference-order arm (odeTools.cpp:89-98) on dual numbers.  TS = double: t and step are plain and take part through
+// the mixed overloads of dual.hpp; TS = Dual: a DUAL step, h F the full dual product.  The right-hand side is given the value part
+// of the stage time.  PV: ModelParams, or the dual view of a parameter block (sensitivity.hpp)
+template <class Mdl, class PV, class TS>
+__device__ __forceinline__ void dual_rk4(const PV &P, double sw0, double sw1, const TS &t, Dual (&X)[Mdl::S], const TS &step)
 {
     constexpr int S = Mdl::S;
     Dual F1[S], Fs[S], F[S], Y[S];
-    const double h2 = step / 2.0;
-    const double th = t + step / 2.0;
-    Mdl::template rhs_t<Dual>(P, sw0, sw1, t, X, F1);
+    const TS h2 = step / 2.0;
+    const TS th = t + step / 2.0;
+    Mdl::template rhs_t<Dual>(P, sw0, sw1, d_val(t), X, F1);
 #pragma unroll
     for (int i = 0; i < S; i++) Y[i] = X[i] + h2 * F1[i];
-    Mdl::template rhs_t<Dual>(P, sw0, sw1, th, Y, Fs);                 // F2
+    Mdl::template rhs_t<Dual>(P, sw0, sw1, d_val(th), Y, Fs);          // F2
 #pragma unroll
     for (int i = 0; i < S; i++) Y[i] = X[i] + h2 * Fs[i];
-    Mdl::template rhs_t<Dual>(P, sw0, sw1, th, Y, F);                  // F3
+    Mdl::template rhs_t<Dual>(P, sw0, sw1, d_val(th), Y, F);           // F3
 #pragma unroll
     for (int i = 0; i < S; i++) { Y[i] = X[i] + step * F[i]; Fs[i] = Fs[i] + F[i]; }   // F2 + F3
-    Mdl::template rhs_t<Dual>(P, sw0, sw1, t + step, Y, F);            // F4
-    const double h6 = step / 6.0;
+    Mdl::template rhs_t<Dual>(P, sw0, sw1, d_val(t + step), Y, F);     // F4
+    const TS h6 = step / 6.0;
 #pragma unroll
     for (int i = 0; i < S; i++) X[i] = X[i] + h6 * (F1[i] + (F[i] + 2.0 * Fs[i]));
+}
+
+// The loop of Lane::integrate with a dual end time: t1 = (t1, 0), t2 = (t2, delta) -- delta = 1.0 differentiates with respect
+// to the segment's length.  The step length is a dual number; the loop condition and the clamp read value parts, so lanes with
+// different delta never diverge.  step(t, h) gets both as duals.
+template <class Step>
+__device__ __forceinline__ void fixed_steps_dual(int step_nbr, double t1, const Dual &t2, Step &&step)
+{
+    const Dual dt = (t2 - Dual(t1, 0.0)) / (double)step_nbr;
+    Dual t(t1, 0.0);
+    int guard = step_nbr + 8;
+    while (t.v < (t2.v - dt.v / 2) && guard-- > 0) {
+        const Dual h = (t.v + dt.v > t2.v) ? (t2 - t) : dt;
+        step(t, h);
+        t = t + dt;
+    }
+}
+
+// the dual start state (X0, e_k) of the column that differentiates with respect to entry k of X0; k < 0: (X0, +0.0)
+template <int S>
+__device__ __forceinline__ void dual_start(const double (&X0)[S], int k, Dual (&X)[S])
+{
+#pragma unroll
+    for (int j = 0; j < S; j++) X[j] = Dual(X0[j], j == k ? 1.0 : 0.0);
 }
 
 // ALL = false: SOCP_FIELDS_COSTATE (C = D columns), ALL = true: SOCP_FIELDS_ALL (C = S columns)
@@ -55,37 +81,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     constexpr int D = Mdl::D;
     constexpr int G = ALL ? S : D;                                    // = C: one lane per column
     constexpr int OFF = ALL ? D : 0;                                  // the group's lane of costate column 0
-    constexpr int GPW = 64 / G;                                       // groups per wavefront
     static_assert(G <= 64, "a group fits one wavefront");
-    const int lane = threadIdx.x;
-    const int g = lane / G;
-    const int c = lane - g * G;                                       // column
-    const int base = lane - c;                                        // the group's first lane
-    const long total = (long)B * pb.M;
-    const long Tl = (long)blockIdx.x * GPW + g;
-    const bool live = g < GPW && Tl < total;
-    const long T = live ? Tl : total - 1;                             // = b * M + i: index into count, slab of tq / det / Phi
-    const long b = T / pb.M;
-    const int i = (int)(T - b * pb.M);
-    const double *zr = Z + b * pb.n;
+    const GroupLane L = group_lane(B, pb.M, G);
+    const double *zr = Z + L.b * pb.n;
     auto z = [=](int k) -> double { return zr[k]; };
     ModelParams Pq = P;
     ProblemDev pq = pb;
-    if constexpr (PERPROB) load_problem_block(pb, b, Pq, pq);
-
-    const Timeline<decltype(z)> tl{pq, z};
-    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
-    const double sw0 = tl.template switching_time<Mdl>(Pq.sw0, pq.sw_node0), sw1 = tl.template switching_time<Mdl>(Pq.sw1, pq.sw_node1);
+    if constexpr (PERPROB) load_problem_block(pb, L.b, Pq, pq);
+    const int c = L.c;
+    double X0[S];
+    const SegmentSpan<Mdl> sp(Pq, pq, z, L.i, X0);
     Dual X[S];
-    {
-        double X0[S];
-        segment_start(z, S * i, X0);
-        const int k = ALL ? c : D + c;                                // the unit vector this column starts from
-#pragma unroll
-        for (int j = 0; j < S; j++) X[j] = Dual(X0[j], j == k ? 1.0 : 0.0);
-    }
-
-    // the loop of Lane::integrate, its condition carried in `act`
+    dual_start(X0, ALL ? c : D + c, X);                           // the unit vector this column starts from
+    // the loop of Lane::integrate, its condition carried in `act` (the scan of jacobi_group_kernel; see the note there)
+    const int base = L.base;
+    const long T = L.T;
+    const bool live = L.live;
+    const double t1 = sp.t1, t2 = sp.t2, sw0 = sp.sw0, sw1 = sp.sw1;
     const double dt = (t2 - t1) / Pq.step_nbr;
     double t = t1;
     int guard = Pq.step_nbr + 8;
@@ -100,7 +112,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         double ts = t;
         while (act && !due) {
             const double step = (t + dt > t2) ? (t2 - t) : dt;
-            fields_rk4<Mdl>(Pq, sw0, sw1, t, X, step);
+            dual_rk4<Mdl>(Pq, sw0, sw1, t, X, step);
             ts = t + step;
             t += dt;
             act = t < (t2 - dt / 2) && guard-- > 0;
@@ -136,9 +148,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         tconj[T] = tc;
     }
     // column c of the transition matrix after the last step; no step: the unit column it started from
-    const bool sp = live && Phi != nullptr;
-    if (sp) {
-        double *out = Phi + T * (S * G) + c;
+    const bool st = L.live && Phi != nullptr;
+    if (st) {
+        double *out = Phi + L.T * (S * G) + c;
 #pragma unroll
         for (int r = 0; r < S; r++) out[r * G] = X[r].d;
     }

@@ -11,11 +11,11 @@
 //   pivot row, the pivot and the multipliers; every lane swaps and updates its column with fully unrolled selects over r, so no
 //   register array is ever indexed by a run-time value (no private segment: profiles/jacobi_kernel_meta.txt)
 //   every lane of the group ends up with the same determinant, and carries the sign test's few scalars itself.
+// The groups are group_lane's (segment_views.hpp: tail and idle lanes run a copy of the launch's last slab and store nothing).
 // The loop over the SAMPLES is wave-uniform -- it runs while ANY lane has a step left; inside it every lane takes its steps up to
 // its next sample in a per-lane loop of the residual's own shape, and all 64 lanes meet again before anything crosses lanes.  A
 // group with fewer steps (another timeline under per-row blocks, a zero-length segment) and the tail lanes skip the inner loop
-// and stay in the outer one -- so every cross-lane read is executed by all 64 lanes and reads a defined register.  Tail and idle lanes integrate a copy of the
-// launch's last slab and store nothing.
+// and stay in the outer one -- so every cross-lane read is executed by all 64 lanes and reads a defined register.
 // Every store site is ONE block under ONE computed predicate (see the note in segment_residual): the sample (tq, det) inside
 // the loop, the slab's summary and Jend after it.  Jend is formed after the loop from the state the last step left, by the
 // operations of the last sample.
@@ -99,32 +99,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) vo
 {
     static_assert(INTEG == 0, "the Jacobi fields follow the fixed-step integrator only");
     static_assert(!has_custom_traj<Mdl>::value, "the Jacobi fields of a model with its own ComputeTraj need a definition of their own");
-    constexpr int S = Mdl::S;
     constexpr int D = Mdl::D;
-    constexpr int G = D + 1;
-    constexpr int GPW = 64 / G;                                       // groups per wavefront
+    constexpr int G = D + 1;                                          // column 0 the extremal, c >= 1 costate component c - 1 moved
     static_assert(G < 64, "a group fits one wavefront");
-    const int lane = threadIdx.x;
-    const int g = lane / G;
-    const int c = lane - g * G;                                       // column: 0 the extremal, c >= 1 costate component c - 1 moved
-    const int base = lane - c;                                        // the group's first lane
-    const long total = (long)B * pb.M;
-    const long Tl = (long)blockIdx.x * GPW + g;
-    const bool live = g < GPW && Tl < total;
-    const long T = live ? Tl : total - 1;                             // = b * M + i: index into count, slab of tq / det / Jend
-    const long b = T / pb.M;
-    const int i = (int)(T - b * pb.M);
-    const double *zr = Z + b * pb.n;
+    const GroupLane L = group_lane(B, pb.M, G);
+    const double *zr = Z + L.b * pb.n;
     auto z = [=](int k) -> double { return zr[k]; };
     ModelParams Pq = P;
     ProblemDev pq = pb;
-    if constexpr (PERPROB) load_problem_block(pb, b, Pq, pq);
-
-    const Timeline<decltype(z)> tl{pq, z};
-    const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
-    const double sw0 = tl.template switching_time<Mdl>(Pq.sw0, pq.sw_node0), sw1 = tl.template switching_time<Mdl>(Pq.sw1, pq.sw_node1);
-    double X[S];
-    segment_start(z, S * i, X);
+    if constexpr (PERPROB) load_problem_block(pb, L.b, Pq, pq);
+    const int c = L.c, base = L.base;
+    double X[Mdl::S];
+    const SegmentSpan<Mdl> sp(Pq, pq, z, L.i, X);
     // column c: X[D + c - 1] + h_c, h_c by MINPACK's rule; x + -0.0 == x bit for bit in every other entry and in column 0
     double h = 1.0;
     {
@@ -135,8 +121,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) vo
 #pragma unroll
         for (int j = 0; j < D; j++) X[D + j] = X[D + j] + ((j == c - 1) ? h : -0.0);
     }
-
-    // the loop of Lane::integrate, its condition carried in `act`
+    // the loop of Lane::integrate, its condition carried in `act`.  Spelled out here and in fields_group_kernel: with the scan handed to
+    // one helper the reference-order Goddard instantiations are allocated 278 registers for 308 and run 1.8 % longer at stride 1
+    const double t1 = sp.t1, t2 = sp.t2, sw0 = sp.sw0, sw1 = sp.sw1;
+    const long T = L.T;
+    const bool live = L.live;
     const double dt = (t2 - t1) / Pq.step_nbr;
     double t = t1;
     int guard = Pq.step_nbr + 8;
@@ -205,3 +194,4 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, WPE))) vo
 }
 
 }  // namespace socp
+

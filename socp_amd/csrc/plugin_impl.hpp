@@ -110,12 +110,24 @@ template <class M> struct one_wave_per_simd<M, std::void_t<decltype(M::kOneWaveP
     } while (0)
 #define SOCP_PLUGIN_LAUNCH(KERNEL, GRID, ST, ...) SOCP_PLUGIN_LAUNCH_T(KERNEL, true, false, GRID, 0, ST, __VA_ARGS__)
 // kernels that read a shooting problem `pb`: per-problem blocks (dev_common.hpp) select the PERPROB instantiation
+inline bool has_blocks(const ProblemDev &pb) { return pb.pp_params || pb.pp_time || pb.pp_xnode; }
 #define SOCP_PLUGIN_LAUNCH_PB_LDS(KERNEL, ADAPTIVE, GRID, LDS, ST, ...)                                                 \
     do {                                                                                                               \
-        if (pb.pp_params || pb.pp_time || pb.pp_xnode) SOCP_PLUGIN_LAUNCH_T(KERNEL, ADAPTIVE, true, GRID, LDS, ST, __VA_ARGS__); \
+        if (has_blocks(pb)) SOCP_PLUGIN_LAUNCH_T(KERNEL, ADAPTIVE, true, GRID, LDS, ST, __VA_ARGS__);                  \
         else SOCP_PLUGIN_LAUNCH_T(KERNEL, ADAPTIVE, false, GRID, LDS, ST, __VA_ARGS__);                               \
     } while (0)
 #define SOCP_PLUGIN_LAUNCH_PB(KERNEL, GRID, ST, ...) SOCP_PLUGIN_LAUNCH_PB_LDS(KERNEL, true, GRID, 0, ST, __VA_ARGS__)
+// the same choice for a group kernel, which has ONE instantiation per PERPROB value (always one wave per SIMD): `shared` is its
+// <..., false>, `perprob` its <..., true>; one group of `lanes` neighbouring lanes per (row, segment), 64 / lanes groups per
+// single-wave workgroup (segment_views.hpp group_lane)
+template <class Kernel, class... Args>
+hipError_t launch_groups(hipStream_t st, const ProblemDev &pb, int B, int lanes, Kernel shared, Kernel perprob, Args... args)
+{
+    const int gpw = 64 / lanes;
+    const long slabs = (long)B * pb.M;
+    hipLaunchKernelGGL((has_blocks(pb) ? perprob : shared), dim3((unsigned)((slabs + gpw - 1) / gpw)), dim3(64), 0, st, args...);
+    return hipGetLastError();
+}
 
 template <class Mdl>
 hipError_t traj(hipStream_t st, const ModelParams &P, int B, const double *t0, const double *tf, const double *sw,
@@ -279,16 +291,8 @@ template <class Mdl, bool ALL>
 hipError_t fields_cols(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int skip, int cap,
                        double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi)
 {
-    constexpr int gpw = 64 / (ALL ? Mdl::S : Mdl::D);
-    const long slabs = (long)B * pb.M;
-    const unsigned grid = (unsigned)((slabs + gpw - 1) / gpw);
-    if (pb.pp_params || pb.pp_time || pb.pp_xnode)
-        hipLaunchKernelGGL((fields_group_kernel<Mdl, ALL, true>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, stride, skip, cap, tq, det, count,
-                           nchange, tconj, Phi);
-    else
-        hipLaunchKernelGGL((fields_group_kernel<Mdl, ALL, false>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, stride, skip, cap, tq, det, count,
-                           nchange, tconj, Phi);
-    return hipGetLastError();
+    return launch_groups(st, pb, B, ALL ? Mdl::S : Mdl::D, &fields_group_kernel<Mdl, ALL, false>, &fields_group_kernel<Mdl, ALL, true>, P, pb, B, Z,
+                         stride, skip, cap, tq, det, count, nchange, tconj, Phi);
 }
 template <class Mdl>
 hipError_t fields(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int cols, int stride, int skip, int cap,
@@ -312,8 +316,7 @@ struct has_exact_jacobian<M, std::void_t<decltype(M::template hamiltonian_t<Dual
     : std::bool_constant<has_fields<M>::value && !has_custom_traj<M>::value && !has_custom_final<M>::value && !has_switching_state<M>::value> {};
 
 // batched exact shooting Jacobian: fixed-step integrator only.  The matrices are zero-filled on the stream, then ONE launch: one group of
-// S + 1 neighbouring lanes per (row, segment), 64 / (S + 1) groups per single-wave workgroup (exact_jacobian.hpp); always one wave per
-// SIMD.  The translation unit must be built without contraction
+// S + 1 neighbouring lanes per (row, segment) (exact_jacobian.hpp).  The translation unit must be built without contraction
 template <class Mdl>
 hipError_t exact_jacobian(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F)
 {
@@ -321,14 +324,7 @@ hipError_t exact_jacobian(hipStream_t st, const ModelParams &P, const ProblemDev
     if (P.integrator != 0) return hipErrorInvalidValue;
     const hipError_t e = hipMemsetAsync(Fjac, 0, sizeof(double) * (size_t)B * pb.n * pb.n, st);
     if (e != hipSuccess) return e;
-    constexpr int gpw = 64 / (Mdl::S + 1);
-    const long slabs = (long)B * pb.M;
-    const unsigned grid = (unsigned)((slabs + gpw - 1) / gpw);
-    if (pb.pp_params || pb.pp_time || pb.pp_xnode)
-        hipLaunchKernelGGL((exact_jacobian_kernel<Mdl, true>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, Fjac, F);
-    else
-        hipLaunchKernelGGL((exact_jacobian_kernel<Mdl, false>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, Fjac, F);
-    return hipGetLastError();
+    return launch_groups(st, pb, B, Mdl::S + 1, &exact_jacobian_kernel<Mdl, false>, &exact_jacobian_kernel<Mdl, true>, P, pb, B, Z, Fjac, F);
 }
 
 // optional: rhs_t, hamiltonian_t and switching_fn_t are generic in the parameter view too (they take SeededParams, sensitivity.hpp)
@@ -351,14 +347,7 @@ template <class Mdl, int KIND>
 hipError_t sensitivity_kind(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, const SensDirs &dirs, int K,
                             double *G)
 {
-    const int gpw = 64 / dirs.n;
-    const long slabs = (long)B * pb.M;
-    const unsigned grid = (unsigned)((slabs + gpw - 1) / gpw);
-    if (pb.pp_params || pb.pp_time || pb.pp_xnode)
-        hipLaunchKernelGGL((sensitivity_kernel<Mdl, KIND, true>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, dirs, K, G);
-    else
-        hipLaunchKernelGGL((sensitivity_kernel<Mdl, KIND, false>), dim3(grid), dim3(64), 0, st, P, pb, B, Z, dirs, K, G);
-    return hipGetLastError();
+    return launch_groups(st, pb, B, dirs.n, &sensitivity_kernel<Mdl, KIND, false>, &sensitivity_kernel<Mdl, KIND, true>, P, pb, B, Z, dirs, K, G);
 }
 template <class Mdl>
 hipError_t sensitivity(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, const SensDirs &dirs, int K,

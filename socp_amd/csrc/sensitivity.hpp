@@ -2,18 +2,18 @@
 // entry points in include/socp_hip.h, tests/sensitivity_reference.py restates it in Python).
 //
 // One lane per (row, segment, direction); the nd directions of one kind of one (row, segment) take identical steps, so they sit in nd
-// NEIGHBOURING lanes of one wavefront, 64 / nd groups per wave (the remaining lanes idle), as the columns of exact_jacobian_kernel do.
+// NEIGHBOURING lanes of one wavefront (group_lane, segment_views.hpp), as the columns of exact_jacobian_kernel do.
 // Two kinds integrate, one launch each (a wave then runs ONE text):
 //   PARAM  the lane reads the row's parameter block through SeededParams: every slot a dual number (p_i, +0.0), the addressed one
 //          (p_i, 1.0).  The view forms the pair where a slot is read, so no dual block is kept: the parameters stay where the residual
 //          has them (kernel arguments, or the registers of the row's own block) and the seed is one compare per read.  The state starts
-//          from (z, +0.0), the step is fields_rk4's (plain t and h), the rows are segment_residual's on duals.
-//   TIME   the LENGTH lane of exact_jacobian_kernel unchanged: t2 = (t2, 1.0), exact_jacobian_rk4's dual step, plain parameters; the
+//          from (z, +0.0), the step is dual_rk4's with plain t and h (fields.hpp), the rows are segment_residual's on duals.
+//   TIME   the LENGTH lane of exact_jacobian_kernel unchanged: t2 = (t2, 1.0), dual_rk4's dual step, plain parameters; the
 //          lane stores w (d row / d L), w = c(i+1, f) - c(i, f), and nothing when w == 0.0.
 // XNODE directions do not integrate (kernels_sensitivity.hip).  G is zero-filled on the stream before the launches; every entry has one
 // writer: the lane of the segment that owns the row (the ROWS paragraph of socp_exact_jacobian_batch).  Every store site is ONE block
 // under ONE computed predicate; no register array is indexed by a run-time value -- the directions travel packed in kernel-argument
-// words, not in an array.  Idle and tail lanes integrate a copy of the launch's last slab and store nothing.
+// words, not in an array.
 #pragma once
 #include "dual.hpp"
 #include "exact_jacobian.hpp"
@@ -84,30 +84,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     static_assert(!has_custom_traj<Mdl>::value && !has_custom_final<Mdl>::value && !has_switching_state<Mdl>::value,
                   "the sensitivities of such a model need a definition of their own");
     constexpr int S = Mdl::S;
-    const int nd = dirs.n;
-    const int gpw = 64 / nd;                                          // groups per wavefront
-    const int lane = threadIdx.x;
-    const int g = lane / nd;
-    const int c = lane - g * nd;                                      // direction of this kind
-    const long total = (long)B * pb.M;
-    const long Tl = (long)blockIdx.x * gpw + g;
-    const bool live = g < gpw && Tl < total;
-    const long T = live ? Tl : total - 1;                             // = b * M + i
-    const long b = T / pb.M;
-    const int i = (int)(T - b * pb.M);
-    const double *zr = Z + b * pb.n;
+    const GroupLane L = group_lane(B, pb.M, dirs.n);
+    const double *zr = Z + L.b * pb.n;
     auto z = [=](int k) -> double { return zr[k]; };
     ModelParams Pq = P;
     ProblemDev pq = pb;
-    if constexpr (PERPROB) load_problem_block(pb, b, Pq, pq);
-
+    if constexpr (PERPROB) load_problem_block(pb, L.b, Pq, pq);
+    const int c = L.c, i = L.i;                                   // c: direction of this kind
+    const bool live = L.live;
+    // the prologue and the parameter arm's loop spelled out, not SegmentSpan / a shared loop: through them the direction launch ran 1.1 % longer
     const Timeline<decltype(z)> tl{pq, z};
     const double t1 = tl.nt(i), t2 = tl.nt(i + 1);
     const double sw0 = tl.template switching_time<Mdl>(Pq.sw0, pq.sw_node0), sw1 = tl.template switching_time<Mdl>(Pq.sw1, pq.sw_node1);
 
     const int slot = (int)((dirs.slot >> (4 * c)) & 0xfull);
     const int index = sens_index(dirs.index, c);
-    double *const Gr = G + ((b * K + slot) * (long)pq.n);
+    double *const Gr = G + ((L.b * K + slot) * (long)pq.n);
 
     Dual X[S];
     {
@@ -133,7 +125,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         int guard = Pq.step_nbr + 8;
         while (t < (t2 - dt / 2) && guard-- > 0) {
             const double step = (t + dt > t2) ? (t2 - t) : dt;
-            fields_rk4<Mdl>(Pv, sw0, sw1, t, X, step);
+            dual_rk4<Mdl>(Pv, sw0, sw1, t, X, step);
             t += dt;
         }
         auto emit = [&](int row, const Dual &e, bool on) {
@@ -145,17 +137,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         // node `index` is a FIXED junction: its weight in this segment's length
         const double w = time_weight(pq, i + 1, index) - time_weight(pq, i, index);
         const bool ws = live && w != 0.0;
-        if (!__any(ws)) return;                                       // wave-uniform: no lane of this wave has anything to store
-        // the loop of exact_jacobian_kernel's length lane
-        const Dual t2d(t2, 1.0);
-        const Dual dt = (t2d - Dual(t1, 0.0)) / (double)Pq.step_nbr;
-        Dual t(t1, 0.0);
-        int guard = Pq.step_nbr + 8;
-        while (t.v < (t2 - dt.v / 2) && guard-- > 0) {
-            const Dual step = (t.v + dt.v > t2) ? (t2d - t) : dt;
-            exact_jacobian_rk4<Mdl>(Pq, sw0, sw1, t, X, step);
-            t = t + dt;
-        }
+        if (!__any(ws)) return;                                   // wave-uniform: no lane of this wave has anything to store
+        fixed_steps_dual(Pq.step_nbr, t1, Dual(t2, 1.0),
+                         [&](const Dual &t, const Dual &step) { dual_rk4<Mdl>(Pq, sw0, sw1, t, X, step); });
         auto emit = [&](int row, const Dual &e, bool on) {
             const bool s0 = ws && on;
             if (s0) { Gr[row] = w * e.d; }

@@ -3,7 +3,7 @@
 A watch e looks at channel chan[e] of the model minus level[e] along the fixed RK4 steps the residual takes; a sign change over
 a step is an event, refined inside the step by R bracketed false-position steps, each ONE RK4 step of length th from the state
 before the step.  Every operation below is one IEEE double operation in the order the reference-order kernel performs it
-(Lane::integrate_events, socp_amd/csrc/integrator.hpp), the RK4 step is the CPU oracle's (Oracle.rk4_step), and the three channel
+(integrate_events, socp_amd/csrc/segment_views.hpp), the RK4 step is the CPU oracle's (Oracle.rk4_step), and the three channel
 expressions are restated from the reference's lines, so a result can be compared bit for bit."""
 import numpy as np
 

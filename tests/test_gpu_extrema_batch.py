@@ -208,7 +208,7 @@ def test_goddard_per_row_blocks_each_row_equal_to_the_row_alone():
     time[:, 0] = 1e-3 * np.sin(np.arange(B))
     xnode = np.tile(xnode0.ravel(), (B, 1)) * (1.0 + 1e-3 * np.arange(B))[:, None]
     blocks = (params, time, xnode)
-    refs = both_forms_bit_equal(ctx, Z, [ALL], "goddard", blocks=blocks, label="blocks")
+    refs = both_forms_bit_equal(ctx, Z, [ALL, 0], "goddard", blocks=blocks, label="blocks")     # 0: the state-only kernel under blocks
     got = run_host(ctx, Z, ALL, blocks=blocks)
     assert ctx.get_params().tolist() == base[:8].tolist(), "the context's own parameters are back in force"
     Cw, M = ctx.extrema_width(), 3
