@@ -1093,6 +1093,63 @@ int socp_hamiltonian_gradient_batch_dev(socp_ctx *ctx, int B, const double *d_t,
                                         double *d_G);
 int socp_hamiltonian_gradient_batch(socp_ctx *ctx, int B, const double *t, const double *sw /* or NULL */, const double *X, double *G);
 
+/* NESTED DUAL NUMBERS and the JACOBIAN OF THE HAMILTONIAN VECTOR FIELD: A = dG/dX of the gradient above at a batch of points -- the
+ * linearised dynamics of an extremal, A(t, X) = d/dX (dH/dp, -dH/dx), the matrix of the variational equations and of every
+ * neighbouring-extremal or Riccati computation on top of Phi -- and the number type that gives a model written from H alone its
+ * right-hand side over dual numbers (include/socp_plugin.h, "A MODEL FROM ITS HAMILTONIAN, WITH THE EXACT ENTRIES").
+ * THE NUMBER.  A nested number is (v; d[0 .. W)) whose parts are themselves DUAL NUMBERS (v, d) of socp_fields_batch: 2 (1 + W)
+ * doubles.  Part k of every rule is the rule of DUAL NUMBERS / HAMILTONIAN GRADIENT on (v, d[k]) with every listed operation carried
+ * out ON DUAL NUMBERS, each of those with its own listed roundings.  With a, b nested, c plain, all operations dual-number ones:
+ *     a + b = (a.v + b.v; a.d[k] + b.d[k])        a - b likewise        -a = (-a.v; -a.d[k])
+ *     a b   = (a.v b.v; l + m),  l = a.d[k] b.v,  m = a.v b.d[k]
+ *     a / b = (q; (a.d[k] - m) / b.v),  q = a.v / b.v,  m = q b.d[k]
+ *     c + a = (c + a.v; a.d[k])    a + c = (a.v + c; a.d[k])    c - a = (c - a.v; -a.d[k])    a - c = (a.v - c; a.d[k])
+ *     c a   = (c a.v; c a.d[k])    a c   = (a.v c; a.d[k] c)    a / c = (a.v / c; a.d[k] / c)
+ *     c / a = (q; (-m) / a.v),  q = c / a.v,  m = q a.d[k]
+ *     |a|   = (|a.v|; a.d[k] negated when the innermost value a.v.v < 0)
+ *     sqrt a = (s; q),  s = sqrt(a.v),  s2 = s + s,  q = a.d[k] / s2, and q = (0.0, +0.0) when the innermost value s.v == 0
+ *     exp a  = (e; e a.d[k]),  e = exp(a.v) (the dual-number exp: exp_glibc on the innermost value)
+ * The value part v and whatever reads value parts only (q, s2, e) is computed ONCE.  A plain c is a double -- its zero terms are
+ * dropped at both levels, by these rules and by DUAL NUMBERS' own mixed rules inside them -- or a plain DUAL NUMBER, a parameter read
+ * through the dual view of socp_sensitivity_batch: plain at the outer level (the outer zero terms dropped), a full dual number at the
+ * inner one.  A comparison reads the innermost value.  Seeds are the explicit dual numbers (1.0, +0.0) and (0.0, +0.0) and are
+ * computed with, not dropped.  Parts never meet, so part k does not depend on W.  CONSEQUENCE: the value part of every nested operation
+ * is the corresponding operation of HAMILTONIAN GRADIENT's numbers, step for step -- the value parts of a nested gradient are the
+ * gradient's bits.
+ * THE NESTED GRADIENT of dual numbers X[i] = (x_i, xd_i), i < S:
+ *   1. Y[i] = (X[i]; e_i): the nested number with value part X[i] and parts (1.0, +0.0) in part i, (0.0, +0.0) elsewhere; the S parts
+ *      cut into passes of W, a part at or beyond S dropped.
+ *   2. h = hamiltonian_t(P, sw0, sw1, t, Y) on nested numbers.
+ *   3. G[i] = h.d[i + d] and G[i + d] = -(h.d[i]) for i < d, the minus DUAL NUMBERS' (-v, -d).
+ * G[i].v is the HAMILTONIAN GRADIENT at x, bit for bit; G[i].d is the directional derivative of the gradient along xd.  This is the
+ * rhs_t of a model registered through SOCP_DEFINE_HAMILTONIAN_PLUGIN_EXACT, with the parameter view passed through.
+ * THE CALL.  t[B], sw[B][2] (or NULL), X[B][S] exactly as socp_hamiltonian_gradient_batch takes them -> A[B][S * S], column-major per
+ * point: A[b][S j + i] = dG_i/dX_j, and, unless G is NULL, G[B][S]: the value parts, bit-equal to socp_hamiltonian_gradient_batch.
+ * One lane per point, ONE launch, no LDS.  Per point, for j = 0 .. S-1 (a loop): X seeded with e_j -- X[i] = (x_i, 1.0 if i == j else
+ * +0.0) -- the nested gradient above, and column j = its derivative parts; G from j = 0.
+ * WHAT IT IS: the TOTAL second derivative of X -> H(X, u(X)), the control law inside: A = Omega Hess with Omega = [0 I; -I 0], so
+ * -Omega A is symmetric wherever the text is twice differentiable on the branch taken (to rounding in doubles; to 2^-200 in the 240-bit
+ * restatement).  It is the linearisation of Pontryagin's equations where the envelope argument of HAMILTONIAN GRADIENT holds on an open
+ * set: the double integrator on both arcs, Goddard mu2 > 0 on its three arcs, Goddard mu2 = 0 at full thrust and off agree with
+ * d rhs_t/dX in 240 bits.  On Goddard's closed-form singular arc and for covid19, where G itself is not rhs or agrees on a surface only,
+ * A is NOT d rhs/dX (tests/test_hamiltonian_exact_cpu.py records by how much).  At a kink it is the BRANCH TAKEN.
+ * ONE OBJECT, NO CONTRACTION: a throughput-flavour context returns the same bits.  Goddard takes the law from the context's mu2 as
+ * socp_eval_batch does.  tests/hamiltonian_exact_reference.py restates the definition; the tests compare whole buffers to it.
+ * socp_ctx_has_hamiltonian_jacobian: 1 when the model's launch table has the entry -- any model whose hamiltonian_t takes nested
+ * numbers: Goddard, the double integrator, covid19, a plugin with the hamiltonian_t trait -- else 0 (the interceptor, vtolUAV, a plugin
+ * without the trait).  socp_ctx_counters advances by one launch and no trajectory.  SOCP_ERR_ARG: B < 0, or t, X or A NULL with B > 0.
+ * SOCP_ERR_UNSUPPORTED: the launch table has no hamiltonian_jacobian entry (a plugin built before launch-table ABI 17 is refused when
+ * it registers: rebuild it).  B == 0: SOCP_OK without a launch.  An error writes nothing and leaves the context and its counters
+ * unchanged.  The _dev form takes device pointers, only enqueues on the context's stream and neither allocates, copies nor
+ * synchronises; the host form stages through that stream and the context's grow-only buffers.
+ * Not covered: per-row parameter blocks, a third nesting level, reverse mode, vtolUAV and the interceptor (their tanh and hooks need
+ * definitions of their own). */
+int socp_ctx_has_hamiltonian_jacobian(const socp_ctx *ctx);      /* 1 / 0; SOCP_ERR_ARG for a NULL context */
+int socp_hamiltonian_jacobian_batch_dev(socp_ctx *ctx, int B, const double *d_t, const double *d_sw /* or NULL */, const double *d_X,
+                                        double *d_A, double *d_G /* or NULL */);
+int socp_hamiltonian_jacobian_batch(socp_ctx *ctx, int B, const double *t, const double *sw /* or NULL */, const double *X, double *A,
+                                    double *G /* or NULL */);
+
 /* The distinct roots of a whole sweep: which distinct rows does a table hold, how many rows went to each, and which row went where.
  * Model-independent (no problem has to be set, no launch table is used).
  * Rows V[B][ld]; the first n <= ld entries of a row are compared.  Greedy leader grouping IN ROW ORDER:

@@ -84,6 +84,23 @@
  * optional hint `static constexpr int kGradientWidth = W;` cuts the S directions into passes of W (registers against time, never a
  * bit).  A plugin built against an older launch table (ABI <= 15) is refused at registration: rebuild it.
  *
+ * Launch-table ABI 17 adds the Hamiltonian-Jacobian launcher (socp_hamiltonian_jacobian_batch, socp_hip.h: A = dG/dX of that gradient,
+ * by NESTED dual numbers).  Its trait is a hamiltonian_t that instantiates on socp::DualN<W, socp::Dual> as well, which every text
+ * written as above does: + - * /, d_sqrt, d_abs, d_exp, d_val, plain doubles and parameters.  Any model that has it gets the entry.
+ *   A MODEL FROM ITS HAMILTONIAN, WITH THE EXACT ENTRIES.  The same struct becomes a model with exact fields, the exact shooting
+ * Jacobian (and socp_newton_batch with jac = 2 on it) through
+ *   SOCP_DEFINE_HAMILTONIAN_PLUGIN_EXACT(MODEL_ID, MDL, NPARAMS, STEP_NBR, {defaults})
+ * which registers socp::plugin::FromHamiltonianExact<MDL>: everything FromHamiltonian gives, plus rhs_t<T, PV> = the gradient taken on
+ * the carrier T (T = double: rhs itself; T = Dual: nested numbers, whose value parts are rhs's bits), hamiltonian_t = MDL's own text,
+ * and switching_fn_t = H(t, X-) - H(t, X+) with kSwitchingReadsXp = true unless MDL has a switching_fn of its own -- it then brings
+ * its switching_fn_t (and kSwitchingReadsXp) too, or has no exact-Jacobian entry.  With hamiltonian_t generic in the parameter view
+ * (template <class T, class PV>, ABI 15) the model has exact sensitivities too; with the one-argument form it has fields and the
+ * exact Jacobian only (tests/plugin/osc1d_hx_plugin.hip, dint_hx_plugin.hip).  It is opt-in because it costs: a right-hand side over
+ * dual numbers is (1 + S) evaluations of H on numbers of 2 (1 + W) doubles, and the exact kernels keep an RK4 step's states beside
+ * them -- choose `static constexpr int kNestedGradientWidth = W;` for registers (the pass width of the gradient on dual numbers;
+ * without it kGradientWidth, else S.  Every pass recomputes the value part, so the plain right-hand side is best left at one pass).  SOCP_DEFINE_HAMILTONIAN_PLUGIN keeps meaning what it meant.  A plugin built against
+ * an older launch table (ABI <= 16) is refused at registration: rebuild it.
+ *
  * Model ids below SOCP_PLUGIN_ID_MIN are reserved for in-tree models.
  */
 #ifndef SOCP_PLUGIN_H_

@@ -216,6 +216,9 @@ def lib():
         L.socp_ctx_has_hamiltonian_gradient.argtypes = [_vp]
         L.socp_hamiltonian_gradient_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_hamiltonian_gradient_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
+        L.socp_ctx_has_hamiltonian_jacobian.argtypes = [_vp]
+        L.socp_hamiltonian_jacobian_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]
+        L.socp_hamiltonian_jacobian_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]
         L.socp_linsolve_batch_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]
         L.socp_svd_batch_dev.argtypes = [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_branch_work_bytes.argtypes = [_vp, C.c_int]
@@ -596,6 +599,34 @@ class Context:
             swp = _d(sw)
         self._chk(self.L.socp_hamiltonian_gradient_batch(self.h, B, _d(t), swp, _d(X), _d(G)))
         return G
+
+    # -- Jacobian of the Hamiltonian vector field
+    def has_hamiltonian_jacobian(self):
+        """Whether this model has the Hamiltonian-Jacobian kernel (socp_ctx_has_hamiltonian_jacobian): any model whose hamiltonian_t
+        takes nested dual numbers -- the in-tree Goddard, double integrator and covid19, a plugin that brings such a text."""
+        return self.L.socp_ctx_has_hamiltonian_jacobian(self.h) == 1
+
+    def hamiltonian_jacobian_batch_dev(self, B, d_t, d_sw, d_X, d_A, d_G=None):
+        """Device pointers (ints; d_sw and d_G may be None): t[B], sw[B][2], X[B][S] -> A[B][S * S] column-major and G[B][S]; one
+        launch, enqueue only, no allocation, no copy, no synchronise (socp_hamiltonian_jacobian_batch_dev)."""
+        self._chk(self.L.socp_hamiltonian_jacobian_batch_dev(self.h, int(B), _vp(d_t), _vp(d_sw), _vp(d_X), _vp(d_A), _vp(d_G)))
+
+    def hamiltonian_jacobian_batch(self, t, X, sw=None, gradient=False):
+        """A[B][S][S] with A[b, i, j] = dG_i/dX_j, G = hamiltonian_gradient_batch's gradient of the model's Hamiltonian text: the
+        TOTAL second derivative of X -> H(X, u(X)) by nested dual numbers (include/socp_hip.h, "NESTED DUAL NUMBERS").  Takes t, X
+        and sw as hamiltonian_gradient_batch does.  gradient=True: returns (A, G), G[B][S] the value parts."""
+        X = _f64(X).reshape(-1, self.s)
+        B = X.shape[0]
+        t = _f64(np.broadcast_to(t, (B,)))
+        A = np.full((B, self.s * self.s), np.nan)
+        G = np.full((B, self.s), np.nan) if gradient else None
+        swp = None
+        if sw is not None:
+            sw = _f64(sw)
+            swp = _d(sw)
+        self._chk(self.L.socp_hamiltonian_jacobian_batch(self.h, B, _d(t), swp, _d(X), _d(A), _d(G) if gradient else None))
+        A = A.reshape(B, self.s, self.s).transpose(0, 2, 1).copy()        # column-major per point -> [row i][column j]
+        return (A, G) if gradient else A
 
     def var_jacobian(self, z):
         """Analytic (variational) shooting Jacobian J[row, col] (hybrj path)."""

@@ -45,6 +45,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.exact_jacobian = &exact_jacobian_goddard;  // kernels_exact_jacobian.hip: likewise
         t.sensitivity = &sensitivity_goddard;        // kernels_sensitivity.hip: likewise
         t.hamiltonian_gradient = &hamiltonian_gradient_goddard;      // kernels_hamiltonian.hip: likewise
+        t.hamiltonian_jacobian = &hamiltonian_jacobian_goddard;      // kernels_hamiltonian_jacobian.hip: likewise
         t.traj = &goddard_by_params<&plugin::traj<GodSmooth>, &plugin::traj<God>>;
         t.eval = &goddard_by_params<&plugin::eval<GodSmooth>, &plugin::eval<God>>;
         t.residual = &goddard_by_problem<&plugin::residual<GodSmooth>, &plugin::residual<God>>;
@@ -67,6 +68,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.exact_jacobian = &exact_jacobian_dint;
         t.sensitivity = &sensitivity_dint;
         t.hamiltonian_gradient = &hamiltonian_gradient_dint;
+        t.hamiltonian_jacobian = &hamiltonian_jacobian_dint;
         return t;
     }();
     // covid19.cpp:25-38 defaults; its ModelInt integrates with its own stepNbr = 1000
@@ -76,6 +78,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.exact_jacobian = &exact_jacobian_covid;
         t.sensitivity = &sensitivity_covid;
         t.hamiltonian_gradient = &hamiltonian_gradient_covid;
+        t.hamiltonian_jacobian = &hamiltonian_jacobian_covid;
         return t;
     }();
     switch (model_id) {

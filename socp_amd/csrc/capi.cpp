@@ -702,6 +702,54 @@ int socp_hamiltonian_gradient_batch(socp_ctx *c, int B, const double *t, const d
     return SOCP_OK;
 }
 
+/* ---- Jacobian of the Hamiltonian vector field: dG/dX of the gradient above by nested dual numbers ------ */
+
+int socp_ctx_has_hamiltonian_jacobian(const socp_ctx *c) { return c ? (table_of(c)->hamiltonian_jacobian ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+// every refusal comes before anything is counted, reserved or enqueued
+int hamiltonian_jacobian_args(socp_ctx *c, int B, const void *t, const void *X, const void *A)
+{
+    if (B < 0 || (B > 0 && (!t || !X || !A))) return fail(c, SOCP_ERR_ARG, "hamiltonian_jacobian_batch: B >= 0 and non-null t, X, A are required");
+    if (!table_of(c)->hamiltonian_jacobian)
+        return fail(c, SOCP_ERR_UNSUPPORTED, "hamiltonian_jacobian_batch: this model's launch table has no hamiltonian_jacobian entry (a model "
+                                             "whose hamiltonian_t does not take nested dual numbers, or without the trait)");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_hamiltonian_jacobian_batch_dev(socp_ctx *c, int B, const double *d_t, const double *d_sw, const double *d_X, double *d_A, double *d_G)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = hamiltonian_jacobian_args(c, B, d_t, d_X, d_A)) return rc;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->hamiltonian_jacobian(c->stream, c->P, B, d_t, d_sw, d_X, d_A, d_G));
+    return SOCP_OK;
+}
+
+int socp_hamiltonian_jacobian_batch(socp_ctx *c, int B, const double *t, const double *sw, const double *X, double *A, double *G)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = hamiltonian_jacobian_args(c, B, t, X, A)) return rc;
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nX = (size_t)B * c->S, nA = nX * c->S;
+    double *d_t, *d_X, *d_sw = nullptr;
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (nA + nX)));      // A, then G
+    HIP_TRY(c, stage_up(c, c->s_t0, t, B, d_t));
+    HIP_TRY(c, stage_up(c, c->s_in, X, nX, d_X));
+    if (sw) HIP_TRY(c, stage_up(c, c->s_sw, sw, (size_t)2 * B, d_sw));
+    double *const d_A = c->s_out.as<double>();
+    const int rc = socp_hamiltonian_jacobian_batch_dev(c, B, d_t, d_sw, d_X, d_A, G ? d_A + nA : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, A, d_A, nA));
+    if (G) HIP_TRY(c, copy_down(c, G, d_A + nA, nX));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
 /* ---- shooting problem --------------------------------------------------------------------- */
 
 int socp_problem_set(socp_ctx *c, int M, const int *mode_t, const int *mode_x, const double *time, const double *xnode)

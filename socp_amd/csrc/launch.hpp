@@ -39,7 +39,7 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 16;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 17;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
@@ -48,6 +48,7 @@ constexpr int kPluginAbi = 16;     // 3: ProblemDev carries per-problem blocks; 
                                    // kPluginAbi = 14: batched observables launcher
                                    // kPluginAbi = 15: batched exact-sensitivities launcher
                                    // kPluginAbi = 16: Hamiltonian-gradient launcher
+                                   // kPluginAbi = 17: Hamiltonian-Jacobian launcher
 // the integrating directions of one kind of socp_sensitivity_batch as they travel to the kernel (sensitivity.hpp): 16 bits per
 // direction, four to a word.  slot: the direction's place k in the call's table (4 bits each); index: the parameter or the node
 constexpr int kSensParam = 0, kSensTime = 1;
@@ -121,6 +122,12 @@ struct ModelLaunchers {
     // hamiltonian_t trait (plugin_impl.hpp).  The in-tree models' entries live in kernels_hamiltonian.hip, one object without
     // contraction that both flavours' tables point to
     hipError_t (*hamiltonian_gradient)(hipStream_t, const ModelParams &, int, const double *, const double *, const double *, double *);
+    // Jacobian of the Hamiltonian vector field (socp_hamiltonian_jacobian_batch): t[B], sw[B][2] or null, X[B][S] -> A[B][S * S]
+    // column-major, A[S j + i] = dG_i/dX_j of the gradient above by nested dual numbers, and its value parts into G[B][S] unless null;
+    // ONE launch.  Null: the model's hamiltonian_t does not instantiate on the nested number (plugin_impl.hpp).  The in-tree models'
+    // entries live in kernels_hamiltonian_jacobian.hip, one object without contraction that both flavours' tables point to
+    hipError_t (*hamiltonian_jacobian)(hipStream_t, const ModelParams &, int, const double *, const double *, const double *, double *,
+                                       double *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
@@ -291,6 +298,15 @@ hipError_t hamiltonian_gradient_goddard(hipStream_t st, const ModelParams &P, in
                                         double *G);
 hipError_t hamiltonian_gradient_dint(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X, double *G);
 hipError_t hamiltonian_gradient_covid(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X, double *G);
+
+// socp_hamiltonian_jacobian_batch of the in-tree models (kernels_hamiltonian_jacobian.hip: one object without contraction, for both
+// flavours); Goddard's picks the law from the context's mu2 like its eval entry
+hipError_t hamiltonian_jacobian_goddard(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X,
+                                        double *A, double *G);
+hipError_t hamiltonian_jacobian_dint(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X, double *A,
+                                     double *G);
+hipError_t hamiltonian_jacobian_covid(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X, double *A,
+                                      double *G);
 
 // the in-tree models' tables, one translation unit each
 // Goddard, double integrator, covid19 by SOCP_MODEL_* id (builtin_tables.hpp); null for any other id

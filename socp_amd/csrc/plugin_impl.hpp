@@ -64,7 +64,9 @@
 //       template <class T, class PV> __device__ static void rhs_t(const PV &P, double sw0, double sw1, double t, const T (&X)[S], T (&dX)[S]);
 //       // hamiltonian_t ALONE already gives the model socp_hamiltonian_gradient_batch: (dH/dp, -dH/dx) of that text by dual numbers,
 //       // the check of rhs against it (hamiltonian_model.hpp).  And a struct with control_only and hamiltonian_t and NO rhs at all is
-//       // a whole model through SOCP_DEFINE_HAMILTONIAN_PLUGIN below (tests/plugin/dint_h_plugin.hip).
+//       // a whole model through SOCP_DEFINE_HAMILTONIAN_PLUGIN below (tests/plugin/dint_h_plugin.hip).  A hamiltonian_t that also
+//       // instantiates on the nested number socp::DualN<W, socp::Dual> gives the model socp_hamiltonian_jacobian_batch, and through
+//       // SOCP_DEFINE_HAMILTONIAN_PLUGIN_EXACT the exact fields, Jacobian and sensitivities (tests/plugin/dint_hx_plugin.hip).
 //   };
 //   SOCP_DEFINE_MODEL_PLUGIN(1001, MyModel, 3 /*nparams*/, 30 /*stepNbr*/, {1.0, 2.0, 3.0})
 //
@@ -377,6 +379,25 @@ hipError_t hamiltonian_gradient(hipStream_t st, const ModelParams &P, int B, con
     return hipGetLastError();
 }
 
+// hamiltonian_t instantiates on the nested number too -> the model has the Jacobian of the Hamiltonian vector field
+// (socp_hamiltonian_jacobian_batch)
+template <class M, class = void> struct has_hamiltonian_jacobian : std::false_type {};
+template <class M>
+struct has_hamiltonian_jacobian<M, std::void_t<decltype(M::template hamiltonian_t<DualN<1, Dual>>(std::declval<const ModelParams &>(), 0.0, 0.0, 0.0,
+                                                                                                  std::declval<const DualN<1, Dual> (&)[M::S]>()))>>
+    : std::true_type {};
+
+// one lane per point, one launch, like hamiltonian_gradient.  W: the inner pass width (the model's kNestedGradientWidth, else its
+// kGradientWidth, unless the caller chooses one for registers).  The translation unit must be built without contraction
+template <class Mdl, int W = nested_gradient_width<Mdl>::value>
+hipError_t hamiltonian_jacobian(hipStream_t st, const ModelParams &P, int B, const double *t, const double *sw, const double *X, double *A,
+                                double *G)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL((hamiltonian_jacobian_kernel<Mdl, W>), dim3(blocks_for(B)), dim3(64), 0, st, P, B, t, sw, X, A, G);
+    return hipGetLastError();
+}
+
 // optional trait: the model integrates its variational equations (aug_rhs + dhamiltonian) -> the hybrj path works for it
 template <class M, class = void> struct has_variational : std::false_type {};
 template <class M>
@@ -384,9 +405,9 @@ struct has_variational<M, std::void_t<decltype(M::aug_rhs(std::declval<const Mod
                                       decltype(M::dhamiltonian(std::declval<const ModelParams &>(), 0.0, (const double *)nullptr,
                                                                std::declval<double (&)[M::S + 1]>()))>> : std::true_type {};
 
-// FIELDS = false: leave the fields, exact_jacobian, sensitivity and hamiltonian_gradient entries to the caller (the in-tree models'
-// entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip and kernels_hamiltonian.hip,
-// builtin_tables.hpp)
+// FIELDS = false: leave the fields, exact_jacobian, sensitivity, hamiltonian_gradient and hamiltonian_jacobian entries to the caller
+// (the in-tree models' entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip, kernels_hamiltonian.hip
+// and kernels_hamiltonian_jacobian.hip, builtin_tables.hpp)
 template <class Mdl, bool FIELDS = true>
 ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> defaults)
 {
@@ -414,6 +435,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     if constexpr (FIELDS && has_exact_jacobian<Mdl>::value) t.exact_jacobian = &exact_jacobian<Mdl>;
     if constexpr (FIELDS && has_sensitivity<Mdl>::value) t.sensitivity = &sensitivity<Mdl>;
     if constexpr (FIELDS && has_hamiltonian_gradient<Mdl>::value) t.hamiltonian_gradient = &hamiltonian_gradient<Mdl>;
+    if constexpr (FIELDS && has_hamiltonian_jacobian<Mdl>::value) t.hamiltonian_jacobian = &hamiltonian_jacobian<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }
@@ -435,3 +457,9 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
 // symplectic_gradient (hamiltonian_model.hpp: plugin::FromHamiltonian).  Build the plugin with -ffp-contract=off
 #define SOCP_DEFINE_HAMILTONIAN_PLUGIN(MODEL_ID, MDL, NPARAMS, STEP_NBR, ...)                             \
     SOCP_DEFINE_MODEL_PLUGIN(MODEL_ID, socp::plugin::FromHamiltonian<MDL>, NPARAMS, STEP_NBR, __VA_ARGS__)
+
+// the same with the three texts over a number type as well (plugin::FromHamiltonianExact): exact fields, the exact shooting Jacobian
+// and, when MDL's hamiltonian_t is generic in the parameter view, exact sensitivities.  MDL's hamiltonian_t must instantiate on
+// socp::DualN<W, socp::Dual>
+#define SOCP_DEFINE_HAMILTONIAN_PLUGIN_EXACT(MODEL_ID, MDL, NPARAMS, STEP_NBR, ...)                       \
+    SOCP_DEFINE_MODEL_PLUGIN(MODEL_ID, socp::plugin::FromHamiltonianExact<MDL>, NPARAMS, STEP_NBR, __VA_ARGS__)
