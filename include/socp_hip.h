@@ -1050,6 +1050,64 @@ int socp_sensitivity_batch_blocks(socp_ctx *ctx, int B, const double *Z, const d
                                   const double *xnode, int K, const int *dir_kind, const int *dir_index, double *dZ, int *info,
                                   double *Gp);
 
+/* NEIGHBOURING-EXTREMAL FEEDBACK GAINS along every row of a batch (the backward sweep of Bryson-Ho / Breakwell-Speyer-Bryson on the
+ * DISCRETE flow): for a measured state deviation dx at the sample time t_q, the costate correction dp = K(t_q) dx that keeps the final
+ * boundary rows satisfied to first order.  The caller applies the model's own control law at (x, p_nom + K dx), saturations
+ * included.  socp_tangent_batch / socp_sensitivity_batch with SOCP_DIR_XNODE directions give dp0/dx0, the gain at the first instant
+ * only; this call gives it along the flight.  [ext] The reference has no such call.
+ * Z[B][n] -> tq[B][M][cap], Kp[B][M][cap][d*d], info[B][M][cap], count[B][M] and, each unless NULL, Xq[B][M][cap][s],
+ * Wq[B][M][cap][d*s], Psi[B][M][cap][s*s];  s = 2d.
+ * SETUP, timeline, switching times and per-row blocks are those of socp_fields_batch; every node time is FIXED (or interpolated
+ * between FIXED ones), every interior node CONTINUOUS.  DUAL NUMBERS as in socp_fields_batch.  Fixed-step integrator only.
+ * SAMPLES.  Segment i of row b takes the nst steps of the residual's loop (dt = (t2 - t1) / step_nbr; t accumulated by t += dt; the last
+ *   step clamped).  Q = max(1, ceil(nst / stride)), count[b][i] = Q.  Sample q sits at the START of step q stride: tq[b][i][q] is the
+ *   loop's own t there, Xq[b][i][q][s] the value state there -- bit for bit the rows socp_trace_batch keeps with the same stride in the
+ *   reference-order flavour.  Sample 0 is the segment's start node; the segment's end is not a sample.
+ * BLOCKS.  Psi_q = dX(after step min((q + 1) stride, nst)) / dX(sample q), s x s, stored ROW-major (row r of X, column c: the layout
+ *   of Phi): column c is carried as the derivative parts of a state that takes the residual's RK4 steps on dual numbers exactly as a
+ *   column of socp_fields_batch does (association order of odeTools.cpp:89-98, t and the step plain).  At every sample each column
+ *   RE-SEEDS: its state becomes (X[j].v, j == c ? 1.0 : +0.0).  The value parts are never touched: the value trajectory is the
+ *   reference-order residual's, bit for bit.  A segment that takes no step has Q = 1 and Psi_0 = I.  With one block per segment
+ *   (stride >= nst) Psi_0 equals Phi of socp_fields_batch(cols = SOCP_FIELDS_ALL) bit for bit.
+ * BACKWARD SWEEP.  E is the d x s selector of the final boundary rows: row j is e_{d+j} when final component j is FREE, else e_j.
+ *   W after the last block is E; then downward over (i, q), across segment boundaries, W_{i,q} = W_next Psi_{i,q}:
+ *     W'[r][j] = sum_m W[r][m] Psi[m][j],  m ascending, every product rounded, the sum sequential and started from the first product,
+ *     nothing contracted.
+ *   Wq[b][i][q] = W_{i,q}, ROW-major (row r, column j): the sensitivity of the terminal rows to the state at the sample, a
+ *   miss-distance table in its own right.
+ * GAIN.  W_{i,q} = [A_x | A_p].  Kp[b][i][q] is d x d COLUMN-major, entry (r, c) at [c d + r] = dp_r/dx_c, the solution of
+ *   A_p K = -A_x by the elimination of socp_linsolve_batch_dev in REFERENCE ORDER in both flavours (as socp_newton_batch and
+ *   socp_sensitivity_batch use it); info[b][i][q] is that elimination's code (0: solved; k + 1: no pivot in step k, Kp = NaN; d + 1: a
+ *   solution entry is not finite).  A singular A_p means that no costate correction reaches the target from there -- on the nominal
+ *   Goddard flight, every sample after the thrust has gone off for good.
+ * SLOTS q >= count keep what the buffers held, in every output.  A segment whose loop counted more blocks than cap (rounding gave
+ *   it a step beyond step_nbr) stores the first cap and leaves the chain of products incomplete: the row's W starts from NaN and
+ *   every sample of the row reports a failed elimination.
+ * WORKSPACE.  The elimination's matrices (B M cap d^2 doubles) and, when Psi is NULL, the blocks (B M cap s^2 8 bytes) live in a
+ *   grow-only workspace arena of the context: the first use and every growth is a hipMalloc, which synchronises the device.
+ * ONE OBJECT, NO CONTRACTION, as socp_fields_batch: a throughput-flavour context returns the same bits.
+ * WHAT IT IS NOT.  The gain of the continuous problem (it is exact for the DISCRETE flow, to rounding, with no step size); the far
+ *   side of a kink (the branch taken is differentiated); a control gain (the caller applies the control law); more than one GPU.
+ * socp_ctx_has_gain: 1 when the model's launch table has the entry -- the rhs_t trait, no switching_state hook, no custom final rows,
+ * no ComputeTraj of its own (Goddard in both laws, the double integrator, covid19, every plugin with rhs_t, FromHamiltonianExact ones
+ * included) -- else 0; SOCP_ERR_ARG for a NULL context.
+ * SOCP_ERR_ARG: no problem set, B < 0, stride < 1, cap < ceil(step_nbr / stride), a NULL required pointer (Z, tq, Kp, info, count) with
+ * B > 0, _blocks with params and param_stride != nparams + 2; B == 0: SOCP_OK without a launch.  SOCP_ERR_UNSUPPORTED (the message
+ * says which): the context's integrator is SOCP_INT_DOPRI5; the model's launch table has no gain entry (the interceptor, vtolUAV,
+ * lqr1d; a plugin built before launch-table ABI 18 is refused when it registers: rebuild it); a problem with any FREE time, interior
+ * or final; an interior node with a FIXED or FREE component -- those structures need a bordered sweep.  An error writes nothing,
+ * launches nothing and leaves the counters unchanged.
+ * Three launches (the blocks, the backward sweep, the elimination); socp_ctx_counters advances by B M s trajectories.  The _dev, host
+ * and _blocks forms as for socp_fields_batch; in the host forms every output travels both ways. */
+int socp_ctx_has_gain(const socp_ctx *ctx);             /* 1 / 0; SOCP_ERR_ARG for a NULL context */
+int socp_gain_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int stride, int cap, double *d_tq, double *d_Kp, int *d_info,
+                        int *d_count, double *d_Xq /* or NULL */, double *d_Wq /* or NULL */, double *d_Psi /* or NULL */);
+int socp_gain_batch(socp_ctx *ctx, int B, const double *Z, int stride, int cap, double *tq, double *Kp, int *info, int *count,
+                    double *Xq, double *Wq, double *Psi);
+int socp_gain_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                           const double *xnode, int stride, int cap, double *tq, double *Kp, int *info, int *count, double *Xq,
+                           double *Wq, double *Psi);
+
 /* HAMILTONIAN GRADIENT: the costate equations a model's Hamiltonian text implies, G = (dH/dp, -dH/dx), at a batch of points -- the
  * check of a hand-written right-hand side against its Hamiltonian, and the right-hand side of a model that brings no dynamics at all
  * (include/socp_plugin.h, "A MODEL FROM ITS HAMILTONIAN").  A model-authoring instrument: no problem has to be set, there is no sweep

@@ -101,6 +101,11 @@
  * without it kGradientWidth, else S.  Every pass recomputes the value part, so the plain right-hand side is best left at one pass).  SOCP_DEFINE_HAMILTONIAN_PLUGIN keeps meaning what it meant.  A plugin built against
  * an older launch table (ABI <= 16) is refused at registration: rebuild it.
  *
+ * Launch-table ABI 18 adds the neighbouring-extremal gain launcher (socp_gain_batch, socp_hip.h: the feedback gains dp/dx along every
+ * row).  It needs no new trait: a model with rhs_t and none of switching_state, custom final rows or its own ComputeTraj gets the
+ * entry with no source change, FromHamiltonianExact models included.  A plugin built against an older launch table (ABI <= 17) is
+ * refused at registration: rebuild it.
+ *
  * Model ids below SOCP_PLUGIN_ID_MIN are reserved for in-tree models.
  */
 #ifndef SOCP_PLUGIN_H_

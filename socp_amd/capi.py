@@ -213,6 +213,10 @@ def lib():
         L.socp_sensitivity_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, _ip, _ip, _vp, C.c_size_t, _vp, _vp, _vp]
         L.socp_sensitivity_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, _ip, _ip, _dp, _ip, _dp]
         L.socp_sensitivity_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, _dp, _ip, _dp]
+        L.socp_ctx_has_gain.argtypes = [_vp]
+        L.socp_gain_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.socp_gain_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp]
+        L.socp_gain_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp]
         L.socp_ctx_has_hamiltonian_gradient.argtypes = [_vp]
         L.socp_hamiltonian_gradient_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_hamiltonian_gradient_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
@@ -975,6 +979,59 @@ class Context:
             return _call_with_enough_cap(call, cap)
         finally:
             self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
+
+    # -- batched neighbouring-extremal gains
+    def has_gain(self):
+        """Whether this model has the gain kernels (socp_ctx_has_gain): the in-tree Goddard, double integrator and covid19, and a plugin
+        with the rhs_t trait and no switching_state hook, custom final rows or ComputeTraj of its own; not the interceptor, not vtolUAV."""
+        return self.L.socp_ctx_has_gain(self.h) == 1
+
+    def gain_batch_dev(self, B, d_Z, stride, cap, d_tq, d_Kp, d_info, d_count, d_Xq=None, d_Wq=None, d_Psi=None):
+        """Device pointers (ints; d_Xq, d_Wq, d_Psi may be None); enqueue only, no copy, no synchronise (socp_gain_batch_dev)."""
+        self._chk(self.L.socp_gain_batch_dev(self.h, int(B), _vp(d_Z), int(stride), int(cap), _vp(d_tq), _vp(d_Kp), _vp(d_info), _vp(d_count),
+                                             _vp(d_Xq), _vp(d_Wq), _vp(d_Psi)))
+
+    def gain_batch(self, Z, stride=1, cap=None, xq=True, wq=False, psi=False, blocks=None):
+        """The neighbouring-extremal feedback gains along every row of Z (include/socp_hip.h): at sample q of segment i, the start of
+        step q * stride, kp[b][i][q] is the d x d matrix dp/dx (COLUMN-major: kp[b][i][q][c][r] = dp_r/dx_c, so kp[b][i][q].T is K) with
+        which the costate correction dp = K dx keeps the final boundary rows satisfied to first order -- exact for the discrete flow.
+        Returns a dict of DEVICE tensors: tq[B][M][cap], kp[B][M][cap][d][d], info[B][M][cap] (the elimination's code, 0 = solved),
+        count[B][M] and, when asked for, xq[B][M][cap][s], wq[B][M][cap][d][s] (the final rows' sensitivity to the state at the sample)
+        and psi[B][M][cap][s][s] (the blocks, row-major).  cap defaults to ceil(step_nbr / stride); the slots at or beyond count keep
+        NaN (info -1).  blocks = (params, time, xnode) as in fields_batch.  The same bits on a throughput-flavour context."""
+        import torch
+        dev = torch.device("cuda")
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        Zd = up(Z).reshape(-1, self.n)
+        B, M, d = Zd.shape[0], self.M, self.dim
+        stride = int(stride)
+        step_nbr = C.c_int()
+        self._chk(self.L.socp_ctx_get_integrator(self.h, C.byref(step_nbr), None, None))
+        c = int(cap) if cap is not None else max(1, -(-step_nbr.value // max(1, stride)))
+        held = [up(a).reshape(B, -1) if a is not None else None for a in (blocks if blocks is not None else ())]
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        nan = float("nan")
+        out = dict(tq=torch.full((B, M, c), nan, dtype=torch.float64, device=dev),
+                   kp=torch.full((B, M, c, d, d), nan, dtype=torch.float64, device=dev),
+                   info=torch.full((B, M, c), -1, dtype=torch.int32, device=dev), count=torch.zeros((B, M), dtype=torch.int32, device=dev))
+        if xq:
+            out["xq"] = torch.full((B, M, c, 2 * d), nan, dtype=torch.float64, device=dev)
+        if wq:
+            out["wq"] = torch.full((B, M, c, d, 2 * d), nan, dtype=torch.float64, device=dev)
+        if psi:
+            out["psi"] = torch.full((B, M, c, 2 * d, 2 * d), nan, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        if held:
+            pp, tt, xx = held
+            self._chk(self.L.socp_problem_set_blocks_dev(self.h, ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx)))
+        try:
+            self.gain_batch_dev(B, Zd.data_ptr(), stride, c, out["tq"].data_ptr(), out["kp"].data_ptr(), out["info"].data_ptr(),
+                                out["count"].data_ptr(), ptr(out.get("xq")), ptr(out.get("wq")), ptr(out.get("psi")))
+            self.synchronize()
+        finally:
+            if held:
+                self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
+        return out
 
     # -- batched exact shooting Jacobian
     def has_exact_jacobian(self):

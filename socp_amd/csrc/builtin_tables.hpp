@@ -46,6 +46,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.sensitivity = &sensitivity_goddard;        // kernels_sensitivity.hip: likewise
         t.hamiltonian_gradient = &hamiltonian_gradient_goddard;      // kernels_hamiltonian.hip: likewise
         t.hamiltonian_jacobian = &hamiltonian_jacobian_goddard;      // kernels_hamiltonian_jacobian.hip: likewise
+        t.gain = &gain_goddard;                      // kernels_gain.hip: likewise
         t.traj = &goddard_by_params<&plugin::traj<GodSmooth>, &plugin::traj<God>>;
         t.eval = &goddard_by_params<&plugin::eval<GodSmooth>, &plugin::eval<God>>;
         t.residual = &goddard_by_problem<&plugin::residual<GodSmooth>, &plugin::residual<God>>;
@@ -69,6 +70,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.sensitivity = &sensitivity_dint;
         t.hamiltonian_gradient = &hamiltonian_gradient_dint;
         t.hamiltonian_jacobian = &hamiltonian_jacobian_dint;
+        t.gain = &gain_dint;
         return t;
     }();
     // covid19.cpp:25-38 defaults; its ModelInt integrates with its own stepNbr = 1000
@@ -79,6 +81,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.sensitivity = &sensitivity_covid;
         t.hamiltonian_gradient = &hamiltonian_gradient_covid;
         t.hamiltonian_jacobian = &hamiltonian_jacobian_covid;
+        t.gain = &gain_covid;
         return t;
     }();
     switch (model_id) {

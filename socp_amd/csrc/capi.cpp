@@ -76,6 +76,7 @@ struct socp_ctx {
 
     // grow-only staging for the host-pointer entry points
     DevBuf s_t0, s_tf, s_sw, s_in, s_out, s_aux, s_var;
+    DevBuf s_gain;                    // workspace arena of socp_gain_batch_dev: the blocks (unless the caller takes them) and the elimination's matrices
 
     hipStream_t aux_stream = nullptr; // socp_ctx_aux_stream: created on first use
     bool blocks_smooth_hint = false;  // socp_problem_blocks_all_smooth: every per-problem parameter block has mu2 > 0
@@ -335,7 +336,7 @@ int socp_ctx_destroy(socp_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     c->d_tables.release(); c->d_pairs_full.release(); c->d_pairs_dedup.release(); c->d_map.release();
-    c->s_t0.release(); c->s_tf.release(); c->s_sw.release(); c->s_in.release(); c->s_out.release(); c->s_aux.release(); c->s_var.release();
+    c->s_t0.release(); c->s_tf.release(); c->s_sw.release(); c->s_in.release(); c->s_out.release(); c->s_aux.release(); c->s_var.release(); c->s_gain.release();
     if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -2669,6 +2670,108 @@ int socp_sensitivity_batch_blocks(socp_ctx *c, int B, const double *Z, const dou
     if (B == 0) return SOCP_OK;
     return with_blocks(c, B, params, pstride, time, xnode,
                        [&] { return socp_sensitivity_batch(c, B, Z, K, dir_kind, dir_index, dZ, info, Gp); });
+}
+
+/* ---- batched neighbouring-extremal gains ---------------------------------------------------- */
+
+int socp_ctx_has_gain(const socp_ctx *c) { return c ? (table_of(c)->gain ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+// the refusals all three forms share
+int gain_args(socp_ctx *c, const char *who, int B, int stride, int cap)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (stride < 1) return fail(c, SOCP_ERR_ARG, w + ": stride >= 1 is required");
+    if (cap < (c->P.step_nbr + stride - 1) / stride)
+        return fail(c, SOCP_ERR_ARG, w + ": cap >= ceil(step_nbr / stride) is required (every block of a segment must be stored)");
+    if (const int rc = args_tail(c, w, table_of(c)->gain != nullptr,
+                                 "gain entry (a model without the rhs_t trait, or one with a switching_state hook, custom final rows or its own "
+                                 "ComputeTraj; rebuild a plugin written for an older launch table)",
+                                 "the gains follow"))
+        return rc;
+    // the structures that need a bordered sweep
+    for (int k = 0; k <= c->M; k++)
+        if (c->mode_t[k] == SOCP_FREE)
+            return fail(c, SOCP_ERR_UNSUPPORTED, w + ": a free time (node " + std::to_string(k) + ") is not covered");
+    for (int k = 1; k < c->M; k++)
+        for (int j = 0; j < c->dim; j++)
+            if (c->mode_x[(size_t)k * c->dim + j] != SOCP_CONTINUOUS)
+                return fail(c, SOCP_ERR_UNSUPPORTED, w + ": a FIXED or FREE state component on an interior node (node " + std::to_string(k) +
+                                                         ", component " + std::to_string(j) + ") is not covered");
+    if (!linsolve_fits(c->dim, c->dim))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": too many states for the batched linear solve (3 d doubles must fit 64 KiB of LDS)");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_gain_batch_dev(socp_ctx *c, int B, const double *d_Z, int stride, int cap, double *d_tq, double *d_Kp, int *d_info, int *d_count,
+                        double *d_Xq, double *d_Wq, double *d_Psi)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = gain_args(c, "gain_batch", B, stride, cap)) return rc;
+    if (B > 0 && (!d_Z || !d_tq || !d_Kp || !d_info || !d_count)) return fail(c, SOCP_ERR_ARG, "gain_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the workspace: the elimination's matrices and, unless the caller takes them, the blocks (grow-only: the first use and every
+    // growth is a hipMalloc, which synchronises the device -- the header says so)
+    const size_t d = (size_t)c->dim, s = (size_t)c->S, slots = (size_t)B * c->M * cap;
+    HIP_TRY(c, c->s_gain.reserve(sizeof(double) * slots * (d * d + (d_Psi ? 0 : s * s))));
+    double *wA = c->s_gain.as<double>(), *psi = d_Psi ? d_Psi : wA + slots * d * d;
+    // launches 1 and 2: the blocks, then the backward sweep, which leaves -A_x in Kp and A_p in the workspace
+    c->n_traj += (long long)B * c->M * c->S; c->n_launch += 2;
+    HIP_TRY(c, table_of(c)->gain(c->stream, c->P, c->pb, B, d_Z, stride, cap, d_tq, d_Xq, d_count, psi, d_Wq, wA, d_Kp));
+    // launch 3: A_p K = -A_x in place, in reference order in both flavours; the slots at or beyond count are not touched
+    c->n_launch += 1;
+    HIP_TRY(c, linsolve_slots(c->stream, B * c->M, cap, d_count, c->dim, c->dim, wA, d_Kp, d_info));
+    return SOCP_OK;
+}
+
+int socp_gain_batch(socp_ctx *c, int B, const double *Z, int stride, int cap, double *tq, double *Kp, int *info, int *count, double *Xq,
+                    double *Wq, double *Psi)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = gain_args(c, "gain_batch", B, stride, cap)) return rc;
+    if (B > 0 && (!Z || !tq || !Kp || !info || !count)) return fail(c, SOCP_ERR_ARG, "gain_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t d = (size_t)c->dim, s = (size_t)c->S, segs = (size_t)B * c->M, slots = segs * cap, nZ = (size_t)B * c->n;
+    const size_t nK = slots * d * d, nX = Xq ? slots * s : 0, nW = Wq ? slots * d * s : 0, nP = Psi ? slots * s * s : 0;
+    double *dZ, *dT;
+    int *dI;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, dZ));
+    // every slab travels both ways: what the kernels leave untouched (slots at or beyond count) comes back as it went
+    HIP_TRY(c, stage_up(c, c->s_out, tq, slots, dT, slots + nK + nX + nW + nP));
+    double *dK = dT + slots, *dX = dK + nK, *dW = dX + nX, *dP = dW + nW;
+    HIP_TRY(c, copy_up(c, dK, Kp, nK));
+    if (Xq) HIP_TRY(c, copy_up(c, dX, Xq, nX));
+    if (Wq) HIP_TRY(c, copy_up(c, dW, Wq, nW));
+    if (Psi) HIP_TRY(c, copy_up(c, dP, Psi, nP));
+    HIP_TRY(c, stage_up(c, c->s_var, info, slots, dI, slots + segs));
+    int *dC = dI + slots;
+    const int rc = socp_gain_batch_dev(c, B, dZ, stride, cap, dT, dK, dI, dC, Xq ? dX : nullptr, Wq ? dW : nullptr, Psi ? dP : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, tq, dT, slots));
+    HIP_TRY(c, copy_down(c, Kp, dK, nK));
+    HIP_TRY(c, copy_down(c, info, dI, slots));
+    HIP_TRY(c, copy_down(c, count, dC, segs));
+    if (Xq) HIP_TRY(c, copy_down(c, Xq, dX, nX));
+    if (Wq) HIP_TRY(c, copy_down(c, Wq, dW, nW));
+    if (Psi) HIP_TRY(c, copy_down(c, Psi, dP, nP));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_gain_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time, const double *xnode,
+                           int stride, int cap, double *tq, double *Kp, int *info, int *count, double *Xq, double *Wq, double *Psi)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = gain_args(c, "gain_batch_blocks", B, stride, cap)) return rc;
+    if (const int rc = blocks_stride(c, "gain_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !tq || !Kp || !info || !count)) return fail(c, SOCP_ERR_ARG, "gain_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_gain_batch(c, B, Z, stride, cap, tq, Kp, info, count, Xq, Wq, Psi); });
 }
 
 /* ---- row grouping --------------------------------------------------------------------------- */

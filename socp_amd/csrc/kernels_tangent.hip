@@ -94,14 +94,13 @@ __device__ __forceinline__ void wave_pivot_max(double &a, int &i)
 // Threads of a team: tt = 0 .. 64 W - 1; for the updates row slot r = tt % RL and column worker cw = tt / RL (RL = 16 when n <= 16
 // -- four such teams share a workgroup -- else 64).  Every barrier is reached by every thread of the workgroup: a team that has
 // failed, or has no problem, skips the work between them.
+// b: the team's problem, live: whether it has one
 template <bool IN_LDS>
-__global__ __launch_bounds__(256) void linsolve_kernel(long B, int n, int K, int W, int T, int RL, int lda, double *A, double *Y, int *info)
+__device__ __forceinline__ void linsolve_team(long b, bool live, int n, int K, int W, int RL, int lda, double *A, double *Y, int *info)
 {
     extern __shared__ double sm[];
     const int NT = W * 64, team = threadIdx.x / NT, tt = threadIdx.x - team * NT, lane = tt & 63, wave = tt >> 6;
     const int r = tt % RL, cw = tt / RL, NCW = NT / RL, nc = n + K;
-    const long b = (long)blockIdx.x * T + team;
-    const bool live = b < B;
     double *Ab = A + (live ? b : 0) * (long)n * n, *Yb = Y + (live ? b : 0) * (long)K * n;
     const int team_doubles = (IN_LDS ? lda * nc : nc + n) + kLinsolveScratch;
     double *mat = sm + (long)team * team_doubles;                 // IN_LDS: the array; else prow[nc] then lcol[n]
@@ -207,6 +206,26 @@ __global__ __launch_bounds__(256) void linsolve_kernel(long B, int n, int K, int
     if (live && tt == 0) info[b] = failed ? failed : (*flag ? n + 1 : 0);
 }
 
+template <bool IN_LDS>
+__global__ __launch_bounds__(256) void linsolve_kernel(long B, int n, int K, int W, int T, int RL, int lda, double *A, double *Y, int *info)
+{
+    const long b = (long)blockIdx.x * T + threadIdx.x / (W * 64);
+    linsolve_team<IN_LDS>(b, b < B, n, K, W, RL, lda, A, Y, info);
+}
+
+#ifndef SOCP_TANGENT_FAST
+// the problems are the slots [B][cap]; slot q of b holds one iff q < count[b], the others are neither read nor written
+template <bool IN_LDS>
+__global__ __launch_bounds__(256) void linsolve_slots_kernel(long B, int cap, const int *__restrict__ count, int n, int K, int W, int T, int RL,
+                                                             int lda, double *A, double *Y, int *info)
+{
+    const long b = (long)blockIdx.x * T + threadIdx.x / (W * 64);
+    const bool in = b < B * cap;
+    const long seg = in ? b / cap : 0;
+    linsolve_team<IN_LDS>(b, in && b - seg * cap < count[seg], n, K, W, RL, lda, A, Y, info);
+}
+#endif
+
 }  // namespace
 
 #ifdef SOCP_TANGENT_FAST
@@ -249,5 +268,24 @@ hipError_t SOCP_TANGENT_NAME(linsolve)(hipStream_t st, int B, int n, int K, doub
     }
     return hipGetLastError();
 }
+
+#ifndef SOCP_TANGENT_FAST
+hipError_t linsolve_slots(hipStream_t st, int B, int cap, const int *count, int n, int K, double *A, double *Y, int *info)
+{
+    if (B <= 0 || cap <= 0) return hipSuccess;
+    const int W = linsolve_waves(n), T = linsolve_teams(n), RL = n <= 16 ? 16 : 64, lda = n | 1;
+    const long slots = (long)B * cap;
+    const unsigned grid = (unsigned)((slots + T - 1) / T), block = (unsigned)(T * W * 64);
+    const size_t lds_in = sizeof(double) * T * ((size_t)lda * (n + K) + kLinsolveScratch);
+    if (lds_in <= (size_t)kLinsolveLdsBytes) {
+        hipLaunchKernelGGL(linsolve_slots_kernel<true>, dim3(grid), dim3(block), lds_in, st, (long)B, cap, count, n, K, W, T, RL, lda, A, Y, info);
+    } else {
+        if (!linsolve_fits(n, K)) return hipErrorInvalidValue;
+        const size_t lds = sizeof(double) * T * ((size_t)2 * n + K + kLinsolveScratch);
+        hipLaunchKernelGGL(linsolve_slots_kernel<false>, dim3(grid), dim3(block), lds, st, (long)B, cap, count, n, K, W, T, RL, lda, A, Y, info);
+    }
+    return hipGetLastError();
+}
+#endif
 
 }  // namespace socp

@@ -39,7 +39,7 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 17;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 18;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
@@ -49,6 +49,7 @@ constexpr int kPluginAbi = 17;     // 3: ProblemDev carries per-problem blocks; 
                                    // kPluginAbi = 15: batched exact-sensitivities launcher
                                    // kPluginAbi = 16: Hamiltonian-gradient launcher
                                    // kPluginAbi = 17: Hamiltonian-Jacobian launcher
+                                   // kPluginAbi = 18: batched neighbouring-extremal gain launcher
 // the integrating directions of one kind of socp_sensitivity_batch as they travel to the kernel (sensitivity.hpp): 16 bits per
 // direction, four to a word.  slot: the direction's place k in the call's table (4 bits each); index: the parameter or the node
 constexpr int kSensParam = 0, kSensTime = 1;
@@ -128,6 +129,14 @@ struct ModelLaunchers {
     // entries live in kernels_hamiltonian_jacobian.hip, one object without contraction that both flavours' tables point to
     hipError_t (*hamiltonian_jacobian)(hipStream_t, const ModelParams &, int, const double *, const double *, const double *, double *,
                                        double *);
+    // batched neighbouring-extremal gains (socp_gain_batch): Z[B][n], stride, cap -> tq[B][M][cap], Xq[B][M][cap][s] (may be null),
+    // count[B][M], the blocks Psi[B][M][cap][s][s], then Wq[B][M][cap][d][s] (may be null), the elimination's matrices
+    // A[B][M][cap][d*d] column-major and its right-hand sides in Kp[B][M][cap][d*d]; fixed-step integrator only.  TWO launches (the
+    // blocks, the backward sweep); the caller runs the elimination.  Null: the model has no rhs_t trait, or has a switching_state hook,
+    // custom final rows or its own ComputeTraj (plugin_impl.hpp).  The in-tree models' entries live in kernels_gain.hip, one object
+    // without contraction that both flavours' tables point to
+    hipError_t (*gain)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, int, double *, double *, int *, double *,
+                       double *, double *, double *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
@@ -158,6 +167,9 @@ hipError_t tangent_diff_fast(hipStream_t st, int B, int K, int n, const double *
 // A[B][n*n] column-major, Y[B][K][n] -> the solutions in Y, info[B]; hipErrorInvalidValue unless linsolve_fits(n, K)
 hipError_t linsolve(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
 hipError_t linsolve_fast(hipStream_t st, int B, int n, int K, double *A, double *Y, int *info);
+// the same elimination over the slots [B][cap] of which only the first min(count[b], cap) of each b hold a problem: the others are
+// neither read nor written (socp_gain_batch).  Reference order only
+hipError_t linsolve_slots(hipStream_t st, int B, int cap, const int *count, int n, int K, double *A, double *Y, int *info);
 // socp_branch_batch (kernels_branch.hip: one object without contraction, for both flavours).  The direction and the options travel as
 // a kernel argument; the row state lives in the caller's workspace.
 struct BranchArgs {
@@ -274,6 +286,14 @@ hipError_t fields_dint(hipStream_t st, const ModelParams &P, const ProblemDev &p
                        int cap, double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi);
 hipError_t fields_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int cols, int stride, int skip,
                         int cap, double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi);
+
+// socp_gain_batch of the in-tree models (kernels_gain.hip: one object without contraction, for both flavours)
+hipError_t gain_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
+                        double *Xq, int *count, double *Psi, double *Wq, double *A, double *Kp);
+hipError_t gain_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
+                     double *Xq, int *count, double *Psi, double *Wq, double *A, double *Kp);
+hipError_t gain_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
+                      double *Xq, int *count, double *Psi, double *Wq, double *A, double *Kp);
 
 // socp_exact_jacobian_batch of the in-tree models (kernels_exact_jacobian.hip: one object without contraction, for both flavours)
 hipError_t exact_jacobian_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);

@@ -80,6 +80,7 @@
 #include "fields.hpp"
 #include "exact_jacobian.hpp"
 #include "sensitivity.hpp"
+#include "gain.hpp"
 #include "hamiltonian_model.hpp"
 #include "jacobi.hpp"
 #include "launch.hpp"
@@ -362,6 +363,29 @@ hipError_t sensitivity(hipStream_t st, const ModelParams &P, const ProblemDev &p
     return hipErrorInvalidValue;
 }
 
+// rhs_t and none of the hooks the definition does not cover -> the model has the neighbouring-extremal gains (socp_gain_batch):
+// has_exact_jacobian's condition without the Hamiltonian traits
+template <class M>
+struct has_gain : std::bool_constant<has_fields<M>::value && !has_custom_traj<M>::value && !has_custom_final<M>::value &&
+                                     !has_switching_state<M>::value> {};
+
+// batched neighbouring-extremal gains: fixed-step integrator only.  Launch 1: the blocks, one group of S neighbouring lanes per (row,
+// segment), always one wave per SIMD; launch 2: the backward sweep, one group of D neighbouring lanes per row (gain.hpp).  The
+// translation unit must be built without contraction
+template <class Mdl>
+hipError_t gain(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq, double *Xq,
+                int *count, double *Psi, double *Wq, double *A, double *Kp)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0 || stride < 1 || cap < 1 || !Psi || !A) return hipErrorInvalidValue;
+    const hipError_t e = launch_groups(st, pb, B, Mdl::S, &gain_blocks_kernel<Mdl, false>, &gain_blocks_kernel<Mdl, true>, P, pb, B, Z, stride,
+                                       cap, tq, Xq, count, Psi);
+    if (e != hipSuccess) return e;
+    constexpr int gpw = 64 / Mdl::D;
+    hipLaunchKernelGGL(gain_sweep_kernel<Mdl>, dim3((unsigned)(((long)B + gpw - 1) / gpw)), dim3(64), 0, st, pb, B, cap, count, Psi, Wq, A, Kp);
+    return hipGetLastError();
+}
+
 // optional trait hamiltonian_t alone -> the model has the Hamiltonian gradient (socp_hamiltonian_gradient_batch): the check of a
 // hand-written rhs against its Hamiltonian text (hamiltonian_model.hpp)
 template <class M, class = void> struct has_hamiltonian_gradient : std::false_type {};
@@ -405,9 +429,9 @@ struct has_variational<M, std::void_t<decltype(M::aug_rhs(std::declval<const Mod
                                       decltype(M::dhamiltonian(std::declval<const ModelParams &>(), 0.0, (const double *)nullptr,
                                                                std::declval<double (&)[M::S + 1]>()))>> : std::true_type {};
 
-// FIELDS = false: leave the fields, exact_jacobian, sensitivity, hamiltonian_gradient and hamiltonian_jacobian entries to the caller
-// (the in-tree models' entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip, kernels_hamiltonian.hip
-// and kernels_hamiltonian_jacobian.hip, builtin_tables.hpp)
+// FIELDS = false: leave the fields, exact_jacobian, sensitivity, hamiltonian_gradient, hamiltonian_jacobian and gain entries to the
+// caller (the in-tree models' entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip,
+// kernels_hamiltonian.hip, kernels_hamiltonian_jacobian.hip and kernels_gain.hip, builtin_tables.hpp)
 template <class Mdl, bool FIELDS = true>
 ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> defaults)
 {
@@ -436,6 +460,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     if constexpr (FIELDS && has_sensitivity<Mdl>::value) t.sensitivity = &sensitivity<Mdl>;
     if constexpr (FIELDS && has_hamiltonian_gradient<Mdl>::value) t.hamiltonian_gradient = &hamiltonian_gradient<Mdl>;
     if constexpr (FIELDS && has_hamiltonian_jacobian<Mdl>::value) t.hamiltonian_jacobian = &hamiltonian_jacobian<Mdl>;
+    if constexpr (FIELDS && has_gain<Mdl>::value) t.gain = &gain<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

@@ -405,6 +405,25 @@ def exactjac_local(ctx, args, local, lo, rank, params=None):
             "sigma_min_min": float(sigma[:, -1].min()) if some and sigma.shape[1] else None, "wall_s": wall, "file": path}
 
 
+def gain_local(ctx, args, local, lo, rank, params=None):
+    """--gain-out: the neighbouring-extremal feedback gains (socp_gain_batch) of this rank's CONVERGED chains, each with its own
+    parameter block when the chains have one: at the start of every --gain-stride-th step of every segment, the d x d matrix dp/dx with
+    which a costate correction keeps the final boundary rows satisfied to first order -- exact for the discrete flow.  Written to
+    PATH.rank<r>.npz: index [k], tq [k][M][cap], xq [k][M][cap][s], kp [k][M][cap][d][d] (column-major: kp[..., c, r] = dp_r/dx_c), info
+    [k][M][cap] (the elimination's code; -1: no sample), count [k][M].  Runs after the timed solve.  Needs fixed times and CONTINUOUS
+    interior nodes (the call refuses the rest).  Returns the record entry of this rank."""
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.gain_out)
+    t0 = time.perf_counter()
+    r = ctx.gain_batch(z, stride=args.gain_stride, blocks=None if own is None else (own, None, None))
+    r = {k: v.cpu().numpy() for k, v in r.items()}
+    wall = time.perf_counter() - t0
+    np.savez(path, index=index, tq=r["tq"], xq=r["xq"], kp=r["kp"], info=r["info"], count=r["count"])
+    solved = r["info"] == 0
+    norms = np.abs(r["kp"][solved]).reshape(-1, r["kp"].shape[-1] ** 2).max(axis=1) if solved.any() else np.zeros(0)
+    return {"rows": int(len(conv)), "singular_samples": int((r["info"] > 0).sum()), "kp_norm_median": float(np.median(norms)) if len(norms) else None,
+            "stride": args.gain_stride, "wall_s": wall, "file": path}
+
+
 def fields_local(ctx, args, local, lo, rank, params=None):
     """--fields-out: the conjugate-time test with EXACT Jacobi fields (socp_fields_batch) of this rank's CONVERGED chains, each with
     its own parameter block when the chains have one: det of J(t) = dx(t)/dp(t0), carried through the residual's RK4 steps on dual
@@ -808,6 +827,13 @@ def main():
                          "timed wall and the printed record are unchanged")
     ap.add_argument("--extrema-what", type=int, default=7, metavar="N",
                     help="with --extrema-out: 0 .. 7, the sum of 1 (controls), 2 (Hamiltonian), 4 (event channels); the states always")
+    ap.add_argument("--gain-out", default=None, metavar="PATH",
+                    help="after the solve, compute the neighbouring-extremal feedback gains of this rank's converged chains as one batch "
+                         "(socp_gain_batch): dp/dx along the flight, exact for the discrete flow; writes PATH.rank<r>.npz (index, tq, xq, kp, "
+                         "info, count) and adds gain {rows, singular_samples, kp_norm_median, stride, wall_s, file} to the record.  Fixed "
+                         "times and CONTINUOUS interior nodes only; not with --model interceptor.  Absent: the timed wall and the printed "
+                         "record are unchanged")
+    ap.add_argument("--gain-stride", type=int, default=100, metavar="K", help="with --gain-out: a gain at the start of every K-th step")
     ap.add_argument("--fields-stride", type=int, default=100, metavar="K", help="with --fields-out: sample every K-th step (and the last)")
     ap.add_argument("--fields-skip", type=int, default=0, metavar="S", help="with --fields-out: compare the samples from the S-th on")
     ap.add_argument("--fields-phi", action="store_true",
@@ -860,6 +886,10 @@ def main():
         ap.error("--jacobi-out: the interceptor has no Jacobi-field kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
     if args.fields_out and args.model == "interceptor":
         ap.error("--fields-out: the interceptor has no exact-fields kernel (its own ComputeTraj rewrites the costate in mid-trajectory)")
+    if args.gain_out and args.model == "interceptor":
+        ap.error("--gain-out: the interceptor has no gain entry (its own ComputeTraj and final rows)")
+    if args.gain_stride < 1:
+        ap.error("--gain-stride must be >= 1")
     if args.exactjac_out and args.model == "interceptor":
         ap.error("--exactjac-out: the interceptor has no exact-Jacobian kernel (its own ComputeTraj and final rows)")
     if args.extrema_out and args.model == "interceptor":
@@ -1025,6 +1055,8 @@ def main():
         extra["jacobi" if rank == 0 else "jacobi_rank%d" % rank] = jacobi_local(ctx, args, local, lo_w, rank, blocks)
     if args.fields_out:
         extra["fields" if rank == 0 else "fields_rank%d" % rank] = fields_local(ctx, args, local, lo_w, rank, blocks)
+    if args.gain_out:
+        extra["gain" if rank == 0 else "gain_rank%d" % rank] = gain_local(ctx, args, local, lo_w, rank, blocks)
     if args.exactjac_out:
         extra["exact_jacobian" if rank == 0 else "exact_jacobian_rank%d" % rank] = exactjac_local(ctx, args, local, lo_w, rank, blocks)
     if args.extrema_out:
