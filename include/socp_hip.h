@@ -1108,6 +1108,65 @@ int socp_gain_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *
                            const double *xnode, int stride, int cap, double *tq, double *Kp, int *info, int *count, double *Xq,
                            double *Wq, double *Psi);
 
+/* NEIGHBOURING-EXTREMAL FEEDBACK GAINS WITH A FREE FINAL TIME (Bryson-Ho 6, free terminal time, on the DISCRETE flow): for a measured
+ * state deviation dx at sample q, the costate correction dp = K_p dx AND the correction dt_f = k_t . dx of the final time that keep
+ * the d final boundary rows and the transversality row H(t_f, X_f) = 0 satisfied to first order -- time-to-go feedback.
+ * socp_gain_batch refuses a free time; this call is the bordered sweep it names.  [ext] The reference has no such call.
+ * Z[B][n] -> tq[B][M][cap], Ke[B][M][cap][(d+1)*d], info[B][M][cap], count[B][M] and, each unless NULL, Xq[B][M][cap][s],
+ * Wq[B][M][cap][(d+1)*(s+1)], Psi[B][M][cap][s*s], Len[B][M][cap][s];  s = 2d.
+ * STRUCTURE.  Node M's time is FREE (the last unknown of a row); every other time is FIXED or interpolated; every interior node has
+ *   all components CONTINUOUS; fixed-step integrator.  SETUP, switching times and per-row blocks as in socp_fields_batch.
+ * SAMPLES, tq, Xq, count, cap and the slots >= count are exactly socp_gain_batch's; t2 of a segment comes from the row's own z
+ *   through the timeline.
+ * BLOCKS.  S + 1 columns per (row, segment): S state columns and the LENGTH column.  The loop is the exact Jacobian's dual loop
+ *   (socp_exact_jacobian_batch), cut into blocks of `stride` steps:
+ *     t2 = (t2, delta), delta = 1.0 in the length column and +0.0 in the others;  dt = (t2 - (t1, 0)) / step_nbr;  t = (t1, 0);
+ *     while t.v < t2.v - dt.v / 2 (and the guard):  h = t.v + dt.v > t2.v ? t2 - t : dt;  X = rk4(t, X, h);  t = t + dt
+ *   with t, dt and h dual numbers in EVERY column and h F the full dual product (dual x dual), the right-hand side given the value
+ *   part of the stage time.  At a sample state column c re-seeds to (X[j].v, j == c ? 1.0 : +0.0) and the length column to
+ *   (X[j].v, +0.0).  The derivative parts of t and dt are NOT re-seeded: the clamped last step t2 - t needs dt/dL.  The value parts
+ *   are never touched.  Psi_q as in socp_gain_batch, row-major s x s -- as NUMBERS equal to socp_gain_batch's on the twin problem with
+ *   t_f FIXED at the row's value (a dual step with a zero derivative part adds products with zero), not always as bits (-0.0).
+ *   Len[b][i][q][r] = the length column's derivative part of component r after the block: dX(after the block)/dL with the state at
+ *   the sample held.  A segment that takes no step has Q = 1, Psi_0 = I, l_0 = 0.  With one block per segment and M = 1, Psi_0 and l_0
+ *   equal the state block and the t_f column (rows d .. 2d-1 through the selector) of socp_exact_jacobian_batch bit for bit.
+ *   After the last block of segment M - 1 the state columns re-seed once more and hamiltonian_t is evaluated on them at (t2, X_f):
+ *   grad H[c] is column c's derivative part (an explicit t is not differentiated).
+ * BACKWARD SWEEP.  d + 1 rows: rows r < d start from socp_gain_batch's selector E, row d from grad H(X_f); the border entry wtau of
+ *   every row starts from +0.0.  Downward over (i, q), across segment boundaries, two updates in this order:
+ *     1. wtau' = wtau + w_i (sum_m W[m] l_q[m]):  m ascending, every product rounded, the sum sequential and started from the first
+ *        product; then the product with w_i, then the addition.  w_i = c(i+1, M) - c(i, M), the weight the exact Jacobian gives the
+ *        t_f column of segment i (c(j, M) = 1 for j == M, (double)(j - a) / (double)(b - a) for a node j interpolated between the
+ *        junctions a and b = M, else 0).  When w_i == 0 the update is skipped.
+ *     2. W' = W Psi_q, as in socp_gain_batch.
+ *   Wq[b][i][q] is ROW-major (d+1) x (s+1): row r, its s state columns, then wtau.
+ * GAIN.  W = [A_x | A_p], both (d+1) x d.  The (d+1) x (d+1) system [A_p | wtau] [K_p; k_t] = -A_x, d right-hand sides, by the
+ *   elimination of socp_linsolve_batch_dev in REFERENCE ORDER in both flavours (n = d + 1, K = d).  Ke[b][i][q] is COLUMN-major with
+ *   leading dimension d + 1: column c is (dp_0/dx_c .. dp_{d-1}/dx_c, dt_f/dx_c).  info is the elimination's code (0: solved; k + 1:
+ *   no pivot in step k, Ke = NaN; d + 2: a solution entry is not finite).
+ * MEANING.  dx is measured at the sample INDEX: the guidance clock is the normalised time of the timeline, not t.  The remaining
+ *   steps of the row are re-timed with t_f + dt_f, so the remaining flight time changes by dt_f times the share of the timeline
+ *   still to fly.  For an autonomous model K_p does not depend on that convention.  An explicit t and the mu2 = 0 comparisons are not
+ *   differentiated, as everywhere.
+ * WORKSPACE.  The bordered matrices (B M cap (d+1)^2 doubles), grad H (B s) and, when NULL, Psi and Len live in socp_gain_batch's
+ *   grow-only arena.  ONE OBJECT, NO CONTRACTION: a throughput-flavour context returns the same bits.
+ * socp_ctx_has_gain_free: 1 when the model's launch table has the entry -- socp_ctx_has_gain's condition and the hamiltonian_t trait
+ * (Goddard in both laws, the double integrator, covid19, every plugin with both traits) -- else 0; SOCP_ERR_ARG for a NULL context.
+ * SOCP_ERR_ARG: as for socp_gain_batch (required pointers: Z, tq, Ke, info, count).  SOCP_ERR_UNSUPPORTED (the message says which):
+ * SOCP_INT_DOPRI5; no gain_free entry in the launch table (a plugin built before launch-table ABI 19 is refused when it registers);
+ * node M's time not FREE (use socp_gain_batch); a free time on a node k < M; an interior node with a FIXED or FREE component; too many
+ * states for the batched linear solve.  An error writes nothing, launches nothing and leaves the counters unchanged.
+ * Three launches; socp_ctx_counters advances by B M (s + 1) trajectories.  The _dev, host and _blocks forms as for socp_gain_batch. */
+int socp_ctx_has_gain_free(const socp_ctx *ctx);        /* 1 / 0; SOCP_ERR_ARG for a NULL context */
+int socp_gain_free_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int stride, int cap, double *d_tq, double *d_Ke, int *d_info,
+                             int *d_count, double *d_Xq /* or NULL */, double *d_Wq /* or NULL */, double *d_Psi /* or NULL */,
+                             double *d_Len /* or NULL */);
+int socp_gain_free_batch(socp_ctx *ctx, int B, const double *Z, int stride, int cap, double *tq, double *Ke, int *info, int *count,
+                         double *Xq, double *Wq, double *Psi, double *Len);
+int socp_gain_free_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                                const double *xnode, int stride, int cap, double *tq, double *Ke, int *info, int *count, double *Xq,
+                                double *Wq, double *Psi, double *Len);
+
 /* HAMILTONIAN GRADIENT: the costate equations a model's Hamiltonian text implies, G = (dH/dp, -dH/dx), at a batch of points -- the
  * check of a hand-written right-hand side against its Hamiltonian, and the right-hand side of a model that brings no dynamics at all
  * (include/socp_plugin.h, "A MODEL FROM ITS HAMILTONIAN").  A model-authoring instrument: no problem has to be set, there is no sweep

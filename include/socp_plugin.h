@@ -106,6 +106,10 @@
  * entry with no source change, FromHamiltonianExact models included.  A plugin built against an older launch table (ABI <= 17) is
  * refused at registration: rebuild it.
  *
+ * Launch-table ABI 19 adds the launcher of the same gains with a FREE final time (socp_gain_free_batch, socp_hip.h: dp/dx and dt_f/dx
+ * by a bordered sweep).  It needs no new trait either: a model that has the gain entry and the hamiltonian_t trait gets it with no
+ * source change.  A plugin built against an older launch table (ABI <= 18) is refused at registration: rebuild it.
+ *
  * Model ids below SOCP_PLUGIN_ID_MIN are reserved for in-tree models.
  */
 #ifndef SOCP_PLUGIN_H_

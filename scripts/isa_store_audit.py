@@ -39,6 +39,7 @@ UNITS = {
     "kernels_solver": ("socp_amd/csrc/kernels_solver.hip", ["-ffp-contract=off"]),
     "kernels_factor_fast": ("socp_amd/csrc/kernels_factor_fast.hip", ["-ffp-contract=fast"]),
     "kernels_gain": ("socp_amd/csrc/kernels_gain.hip", ["-ffp-contract=off"]),
+    "kernels_gain_free": ("socp_amd/csrc/kernels_gain_free.hip", ["-ffp-contract=off"]),
     "capi": ("socp_amd/csrc/capi.cpp", ["-ffp-contract=off", "-x", "hip"]),
     "plugin": ("tests/plugin/lqr1d_plugin.hip", ["-ffp-contract=off"]),
 }

@@ -217,6 +217,10 @@ def lib():
         L.socp_gain_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         L.socp_gain_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp]
         L.socp_gain_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp]
+        L.socp_ctx_has_gain_free.argtypes = [_vp]
+        L.socp_gain_free_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.socp_gain_free_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]
+        L.socp_gain_free_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]
         L.socp_ctx_has_hamiltonian_gradient.argtypes = [_vp]
         L.socp_hamiltonian_gradient_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_hamiltonian_gradient_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
@@ -1031,6 +1035,63 @@ class Context:
         finally:
             if held:
                 self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
+        return out
+
+    # -- batched neighbouring-extremal gains with a free final time
+    def has_gain_free(self):
+        """Whether this model has the free-final-time gain kernels (socp_ctx_has_gain_free): has_gain()'s condition and the hamiltonian_t
+        trait -- the in-tree Goddard, double integrator and covid19, and a plugin with both traits."""
+        return self.L.socp_ctx_has_gain_free(self.h) == 1
+
+    def gain_free_batch_dev(self, B, d_Z, stride, cap, d_tq, d_Ke, d_info, d_count, d_Xq=None, d_Wq=None, d_Psi=None, d_Len=None):
+        """Device pointers (ints; d_Xq, d_Wq, d_Psi, d_Len may be None); enqueue only, no copy, no synchronise (socp_gain_free_batch_dev)."""
+        self._chk(self.L.socp_gain_free_batch_dev(self.h, int(B), _vp(d_Z), int(stride), int(cap), _vp(d_tq), _vp(d_Ke), _vp(d_info),
+                                                  _vp(d_count), _vp(d_Xq), _vp(d_Wq), _vp(d_Psi), _vp(d_Len)))
+
+    def gain_free_batch(self, Z, stride=1, cap=None, xq=True, wq=False, psi=False, length=False, blocks=None):
+        """The neighbouring-extremal feedback gains along every row of Z of a problem whose FINAL TIME IS FREE (include/socp_hip.h): at
+        sample q of segment i, kp[b][i][q] is the d x d matrix dp/dx in gain_batch's layout (kp[b][i][q][c][r] = dp_r/dx_c) and
+        kt[b][i][q][c] = dt_f/dx_c, with which dp = K_p dx and dt_f = k_t . dx keep the final boundary rows AND H(t_f) = 0 satisfied to
+        first order -- exact for the discrete flow; dx is measured at the sample index and the remaining steps are re-timed with the
+        new t_f.  Returns a dict of DEVICE tensors: tq, kp, kt[B][M][cap][d], ke[B][M][cap][d][d+1] (the call's own layout, of which kp
+        and kt are views), info, count and, when asked for, xq[B][M][cap][s], wq[B][M][cap][d+1][s+1], psi[B][M][cap][s][s],
+        len[B][M][cap][s].  cap, the slots at or beyond count and blocks as in gain_batch.  The same bits on a throughput-flavour context."""
+        import torch
+        dev = torch.device("cuda")
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        Zd = up(Z).reshape(-1, self.n)
+        B, M, d = Zd.shape[0], self.M, self.dim
+        stride = int(stride)
+        step_nbr = C.c_int()
+        self._chk(self.L.socp_ctx_get_integrator(self.h, C.byref(step_nbr), None, None))
+        c = int(cap) if cap is not None else max(1, -(-step_nbr.value // max(1, stride)))
+        held = [up(a).reshape(B, -1) if a is not None else None for a in (blocks if blocks is not None else ())]
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        nan = float("nan")
+        out = dict(tq=torch.full((B, M, c), nan, dtype=torch.float64, device=dev),
+                   ke=torch.full((B, M, c, d, d + 1), nan, dtype=torch.float64, device=dev),
+                   info=torch.full((B, M, c), -1, dtype=torch.int32, device=dev), count=torch.zeros((B, M), dtype=torch.int32, device=dev))
+        if xq:
+            out["xq"] = torch.full((B, M, c, 2 * d), nan, dtype=torch.float64, device=dev)
+        if wq:
+            out["wq"] = torch.full((B, M, c, d + 1, 2 * d + 1), nan, dtype=torch.float64, device=dev)
+        if psi:
+            out["psi"] = torch.full((B, M, c, 2 * d, 2 * d), nan, dtype=torch.float64, device=dev)
+        if length:
+            out["len"] = torch.full((B, M, c, 2 * d), nan, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        if held:
+            pp, tt, xx = held
+            self._chk(self.L.socp_problem_set_blocks_dev(self.h, ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx)))
+        try:
+            self.gain_free_batch_dev(B, Zd.data_ptr(), stride, c, out["tq"].data_ptr(), out["ke"].data_ptr(), out["info"].data_ptr(),
+                                     out["count"].data_ptr(), ptr(out.get("xq")), ptr(out.get("wq")), ptr(out.get("psi")), ptr(out.get("len")))
+            self.synchronize()
+        finally:
+            if held:
+                self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
+        out["kp"] = out["ke"][..., :d]
+        out["kt"] = out["ke"][..., d]
         return out
 
     # -- batched exact shooting Jacobian

@@ -47,6 +47,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.hamiltonian_gradient = &hamiltonian_gradient_goddard;      // kernels_hamiltonian.hip: likewise
         t.hamiltonian_jacobian = &hamiltonian_jacobian_goddard;      // kernels_hamiltonian_jacobian.hip: likewise
         t.gain = &gain_goddard;                      // kernels_gain.hip: likewise
+        t.gain_free = &gain_free_goddard;            // kernels_gain_free.hip: likewise
         t.traj = &goddard_by_params<&plugin::traj<GodSmooth>, &plugin::traj<God>>;
         t.eval = &goddard_by_params<&plugin::eval<GodSmooth>, &plugin::eval<God>>;
         t.residual = &goddard_by_problem<&plugin::residual<GodSmooth>, &plugin::residual<God>>;
@@ -71,6 +72,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.hamiltonian_gradient = &hamiltonian_gradient_dint;
         t.hamiltonian_jacobian = &hamiltonian_jacobian_dint;
         t.gain = &gain_dint;
+        t.gain_free = &gain_free_dint;
         return t;
     }();
     // covid19.cpp:25-38 defaults; its ModelInt integrates with its own stepNbr = 1000
@@ -82,6 +84,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.hamiltonian_gradient = &hamiltonian_gradient_covid;
         t.hamiltonian_jacobian = &hamiltonian_jacobian_covid;
         t.gain = &gain_covid;
+        t.gain_free = &gain_free_covid;
         return t;
     }();
     switch (model_id) {

@@ -76,7 +76,7 @@ struct socp_ctx {
 
     // grow-only staging for the host-pointer entry points
     DevBuf s_t0, s_tf, s_sw, s_in, s_out, s_aux, s_var;
-    DevBuf s_gain;                    // workspace arena of socp_gain_batch_dev: the blocks (unless the caller takes them) and the elimination's matrices
+    DevBuf s_gain;                    // workspace arena of socp_gain_batch_dev and socp_gain_free_batch_dev: the blocks (unless the caller takes them) and the elimination's matrices
 
     hipStream_t aux_stream = nullptr; // socp_ctx_aux_stream: created on first use
     bool blocks_smooth_hint = false;  // socp_problem_blocks_all_smooth: every per-problem parameter block has mu2 > 0
@@ -2772,6 +2772,117 @@ int socp_gain_batch_blocks(socp_ctx *c, int B, const double *Z, const double *pa
     if (B == 0) return SOCP_OK;
     return with_blocks(c, B, params, pstride, time, xnode,
                        [&] { return socp_gain_batch(c, B, Z, stride, cap, tq, Kp, info, count, Xq, Wq, Psi); });
+}
+
+/* ---- batched neighbouring-extremal gains with a free final time ------------------------------ */
+
+int socp_ctx_has_gain_free(const socp_ctx *c) { return c ? (table_of(c)->gain_free ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+// the refusals all three forms share
+int gain_free_args(socp_ctx *c, const char *who, int B, int stride, int cap)
+{
+    const std::string w(who);
+    if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
+    if (stride < 1) return fail(c, SOCP_ERR_ARG, w + ": stride >= 1 is required");
+    if (cap < (c->P.step_nbr + stride - 1) / stride)
+        return fail(c, SOCP_ERR_ARG, w + ": cap >= ceil(step_nbr / stride) is required (every block of a segment must be stored)");
+    if (const int rc = args_tail(c, w, table_of(c)->gain_free != nullptr,
+                                 "gain_free entry (a model without the rhs_t or the hamiltonian_t trait, or one with a switching_state hook, "
+                                 "custom final rows or its own ComputeTraj; rebuild a plugin written for an older launch table)",
+                                 "the gains follow"))
+        return rc;
+    // the structure the bordered sweep covers: t_f free, every other time fixed or interpolated, interior nodes CONTINUOUS
+    if (c->mode_t[c->M] != SOCP_FREE)
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": the final time (node " + std::to_string(c->M) + ") is not FREE: use socp_gain_batch");
+    for (int k = 0; k < c->M; k++)
+        if (c->mode_t[k] == SOCP_FREE)
+            return fail(c, SOCP_ERR_UNSUPPORTED, w + ": a free time before the final node (node " + std::to_string(k) + ") is not covered");
+    for (int k = 1; k < c->M; k++)
+        for (int j = 0; j < c->dim; j++)
+            if (c->mode_x[(size_t)k * c->dim + j] != SOCP_CONTINUOUS)
+                return fail(c, SOCP_ERR_UNSUPPORTED, w + ": a FIXED or FREE state component on an interior node (node " + std::to_string(k) +
+                                                         ", component " + std::to_string(j) + ") is not covered");
+    if (!linsolve_fits(c->dim + 1, c->dim))
+        return fail(c, SOCP_ERR_UNSUPPORTED, w + ": too many states for the batched linear solve (3 d + 2 doubles must fit 64 KiB of LDS)");
+    return SOCP_OK;
+}
+}  // namespace
+
+int socp_gain_free_batch_dev(socp_ctx *c, int B, const double *d_Z, int stride, int cap, double *d_tq, double *d_Ke, int *d_info, int *d_count,
+                             double *d_Xq, double *d_Wq, double *d_Psi, double *d_Len)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = gain_free_args(c, "gain_free_batch", B, stride, cap)) return rc;
+    if (B > 0 && (!d_Z || !d_tq || !d_Ke || !d_info || !d_count)) return fail(c, SOCP_ERR_ARG, "gain_free_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the workspace: the elimination's bordered matrices, grad H of every row and, unless the caller takes them, the blocks and their
+    // length columns (grow-only: the first use and every growth is a hipMalloc, which synchronises the device -- the header says so)
+    const size_t d1 = (size_t)c->dim + 1, s = (size_t)c->S, slots = (size_t)B * c->M * cap;
+    HIP_TRY(c, c->s_gain.reserve(sizeof(double) * (slots * (d1 * d1 + (d_Psi ? 0 : s * s) + (d_Len ? 0 : s)) + (size_t)B * s)));
+    double *wA = c->s_gain.as<double>(), *gh = wA + slots * d1 * d1, *next = gh + (size_t)B * s;
+    double *psi = d_Psi ? d_Psi : next;
+    double *len = d_Len ? d_Len : next + (d_Psi ? 0 : slots * s * s);
+    // launches 1 and 2: the blocks, then the bordered backward sweep, which leaves -A_x in Ke and [A_p | wtau] in the workspace
+    c->n_traj += (long long)B * c->M * (c->S + 1); c->n_launch += 2;
+    HIP_TRY(c, table_of(c)->gain_free(c->stream, c->P, c->pb, B, d_Z, stride, cap, d_tq, d_Xq, d_count, psi, len, gh, d_Wq, wA, d_Ke));
+    // launch 3: [A_p | wtau] [K_p; k_t] = -A_x in place, in reference order in both flavours; the slots at or beyond count are not touched
+    c->n_launch += 1;
+    HIP_TRY(c, linsolve_slots(c->stream, B * c->M, cap, d_count, c->dim + 1, c->dim, wA, d_Ke, d_info));
+    return SOCP_OK;
+}
+
+int socp_gain_free_batch(socp_ctx *c, int B, const double *Z, int stride, int cap, double *tq, double *Ke, int *info, int *count, double *Xq,
+                         double *Wq, double *Psi, double *Len)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = gain_free_args(c, "gain_free_batch", B, stride, cap)) return rc;
+    if (B > 0 && (!Z || !tq || !Ke || !info || !count)) return fail(c, SOCP_ERR_ARG, "gain_free_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t d = (size_t)c->dim, s = (size_t)c->S, segs = (size_t)B * c->M, slots = segs * cap, nZ = (size_t)B * c->n;
+    const size_t nK = slots * (d + 1) * d, nX = Xq ? slots * s : 0, nW = Wq ? slots * (d + 1) * (s + 1) : 0, nP = Psi ? slots * s * s : 0,
+                 nL = Len ? slots * s : 0;
+    double *dZ, *dT;
+    int *dI;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, nZ, dZ));
+    // every slab travels both ways: what the kernels leave untouched (slots at or beyond count) comes back as it went
+    HIP_TRY(c, stage_up(c, c->s_out, tq, slots, dT, slots + nK + nX + nW + nP + nL));
+    double *dK = dT + slots, *dX = dK + nK, *dW = dX + nX, *dP = dW + nW, *dL = dP + nP;
+    HIP_TRY(c, copy_up(c, dK, Ke, nK));
+    if (Xq) HIP_TRY(c, copy_up(c, dX, Xq, nX));
+    if (Wq) HIP_TRY(c, copy_up(c, dW, Wq, nW));
+    if (Psi) HIP_TRY(c, copy_up(c, dP, Psi, nP));
+    if (Len) HIP_TRY(c, copy_up(c, dL, Len, nL));
+    HIP_TRY(c, stage_up(c, c->s_var, info, slots, dI, slots + segs));
+    int *dC = dI + slots;
+    const int rc = socp_gain_free_batch_dev(c, B, dZ, stride, cap, dT, dK, dI, dC, Xq ? dX : nullptr, Wq ? dW : nullptr, Psi ? dP : nullptr,
+                                            Len ? dL : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, tq, dT, slots));
+    HIP_TRY(c, copy_down(c, Ke, dK, nK));
+    HIP_TRY(c, copy_down(c, info, dI, slots));
+    HIP_TRY(c, copy_down(c, count, dC, segs));
+    if (Xq) HIP_TRY(c, copy_down(c, Xq, dX, nX));
+    if (Wq) HIP_TRY(c, copy_down(c, Wq, dW, nW));
+    if (Psi) HIP_TRY(c, copy_down(c, Psi, dP, nP));
+    if (Len) HIP_TRY(c, copy_down(c, Len, dL, nL));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_gain_free_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time,
+                                const double *xnode, int stride, int cap, double *tq, double *Ke, int *info, int *count, double *Xq,
+                                double *Wq, double *Psi, double *Len)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (const int rc = gain_free_args(c, "gain_free_batch_blocks", B, stride, cap)) return rc;
+    if (const int rc = blocks_stride(c, "gain_free_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !tq || !Ke || !info || !count)) return fail(c, SOCP_ERR_ARG, "gain_free_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode,
+                       [&] { return socp_gain_free_batch(c, B, Z, stride, cap, tq, Ke, info, count, Xq, Wq, Psi, Len); });
 }
 
 /* ---- row grouping --------------------------------------------------------------------------- */

@@ -39,7 +39,7 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 18;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 19;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
@@ -50,6 +50,7 @@ constexpr int kPluginAbi = 18;     // 3: ProblemDev carries per-problem blocks; 
                                    // kPluginAbi = 16: Hamiltonian-gradient launcher
                                    // kPluginAbi = 17: Hamiltonian-Jacobian launcher
                                    // kPluginAbi = 18: batched neighbouring-extremal gain launcher
+                                   // kPluginAbi = 19: the same with a free final time (bordered sweep)
 // the integrating directions of one kind of socp_sensitivity_batch as they travel to the kernel (sensitivity.hpp): 16 bits per
 // direction, four to a word.  slot: the direction's place k in the call's table (4 bits each); index: the parameter or the node
 constexpr int kSensParam = 0, kSensTime = 1;
@@ -137,6 +138,14 @@ struct ModelLaunchers {
     // without contraction that both flavours' tables point to
     hipError_t (*gain)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, int, double *, double *, int *, double *,
                        double *, double *, double *);
+    // the same with a FREE final time (socp_gain_free_batch): Z[B][n], stride, cap -> tq, Xq (may be null), count, the blocks
+    // Psi[B][M][cap][s][s] and their length columns Len[B][M][cap][s], grad H at the final state gradH[B][s], then
+    // Wq[B][M][cap][(d+1)(s+1)] (may be null), the elimination's bordered matrices A[B][M][cap][(d+1)(d+1)] column-major and its
+    // right-hand sides in Ke[B][M][cap][d][d+1]; fixed-step integrator only.  TWO launches; the caller runs the elimination.  Null: the
+    // model has no gain entry or no hamiltonian_t trait.  The in-tree models' entries live in kernels_gain_free.hip, one object without
+    // contraction that both flavours' tables point to
+    hipError_t (*gain_free)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, int, double *, double *, int *,
+                            double *, double *, double *, double *, double *, double *);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
@@ -294,6 +303,14 @@ hipError_t gain_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb,
                      double *Xq, int *count, double *Psi, double *Wq, double *A, double *Kp);
 hipError_t gain_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
                       double *Xq, int *count, double *Psi, double *Wq, double *A, double *Kp);
+
+// socp_gain_free_batch of the in-tree models (kernels_gain_free.hip: one object without contraction, for both flavours)
+hipError_t gain_free_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
+                             double *Xq, int *count, double *Psi, double *Len, double *gradH, double *Wq, double *A, double *Ke);
+hipError_t gain_free_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
+                          double *Xq, int *count, double *Psi, double *Len, double *gradH, double *Wq, double *A, double *Ke);
+hipError_t gain_free_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
+                           double *Xq, int *count, double *Psi, double *Len, double *gradH, double *Wq, double *A, double *Ke);
 
 // socp_exact_jacobian_batch of the in-tree models (kernels_exact_jacobian.hip: one object without contraction, for both flavours)
 hipError_t exact_jacobian_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);

@@ -81,6 +81,7 @@
 #include "exact_jacobian.hpp"
 #include "sensitivity.hpp"
 #include "gain.hpp"
+#include "gain_free.hpp"
 #include "hamiltonian_model.hpp"
 #include "jacobi.hpp"
 #include "launch.hpp"
@@ -386,6 +387,32 @@ hipError_t gain(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int 
     return hipGetLastError();
 }
 
+// has_gain's condition and the hamiltonian_t trait -> the model has the gains with a free final time (socp_gain_free_batch): the H row
+// of the bordered sweep is the gradient of the model's own Hamiltonian text
+template <class M, class = void> struct has_gain_free : std::false_type {};
+template <class M>
+struct has_gain_free<M, std::void_t<decltype(M::template hamiltonian_t<Dual>(std::declval<const ModelParams &>(), 0.0, 0.0, 0.0,
+                                                                              std::declval<const Dual (&)[M::S]>()))>>
+    : std::bool_constant<has_gain<M>::value> {};
+
+// batched neighbouring-extremal gains with a free final time: fixed-step integrator only.  Launch 1: the blocks, one group of S + 1
+// neighbouring lanes per (row, segment), always one wave per SIMD; launch 2: the bordered backward sweep, one group of D + 1
+// neighbouring lanes per row (gain_free.hpp).  The translation unit must be built without contraction
+template <class Mdl>
+hipError_t gain_free(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
+                     double *Xq, int *count, double *Psi, double *Len, double *gradH, double *Wq, double *A, double *Ke)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0 || stride < 1 || cap < 1 || !Psi || !Len || !gradH || !A) return hipErrorInvalidValue;
+    const hipError_t e = launch_groups(st, pb, B, Mdl::S + 1, &gain_free_blocks_kernel<Mdl, false>, &gain_free_blocks_kernel<Mdl, true>, P, pb, B,
+                                       Z, stride, cap, tq, Xq, count, Psi, Len, gradH);
+    if (e != hipSuccess) return e;
+    constexpr int gpw = 64 / (Mdl::D + 1);
+    hipLaunchKernelGGL(gain_free_sweep_kernel<Mdl>, dim3((unsigned)(((long)B + gpw - 1) / gpw)), dim3(64), 0, st, pb, B, cap, count, Psi, Len,
+                       gradH, Wq, A, Ke);
+    return hipGetLastError();
+}
+
 // optional trait hamiltonian_t alone -> the model has the Hamiltonian gradient (socp_hamiltonian_gradient_batch): the check of a
 // hand-written rhs against its Hamiltonian text (hamiltonian_model.hpp)
 template <class M, class = void> struct has_hamiltonian_gradient : std::false_type {};
@@ -429,9 +456,9 @@ struct has_variational<M, std::void_t<decltype(M::aug_rhs(std::declval<const Mod
                                       decltype(M::dhamiltonian(std::declval<const ModelParams &>(), 0.0, (const double *)nullptr,
                                                                std::declval<double (&)[M::S + 1]>()))>> : std::true_type {};
 
-// FIELDS = false: leave the fields, exact_jacobian, sensitivity, hamiltonian_gradient, hamiltonian_jacobian and gain entries to the
-// caller (the in-tree models' entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip,
-// kernels_hamiltonian.hip, kernels_hamiltonian_jacobian.hip and kernels_gain.hip, builtin_tables.hpp)
+// FIELDS = false: leave the fields, exact_jacobian, sensitivity, hamiltonian_gradient, hamiltonian_jacobian, gain and gain_free entries
+// to the caller (the in-tree models' entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip,
+// kernels_hamiltonian.hip, kernels_hamiltonian_jacobian.hip, kernels_gain.hip and kernels_gain_free.hip, builtin_tables.hpp)
 template <class Mdl, bool FIELDS = true>
 ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> defaults)
 {
@@ -461,6 +488,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     if constexpr (FIELDS && has_hamiltonian_gradient<Mdl>::value) t.hamiltonian_gradient = &hamiltonian_gradient<Mdl>;
     if constexpr (FIELDS && has_hamiltonian_jacobian<Mdl>::value) t.hamiltonian_jacobian = &hamiltonian_jacobian<Mdl>;
     if constexpr (FIELDS && has_gain<Mdl>::value) t.gain = &gain<Mdl>;
+    if constexpr (FIELDS && has_gain_free<Mdl>::value) t.gain_free = &gain_free<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

@@ -410,18 +410,27 @@ def gain_local(ctx, args, local, lo, rank, params=None):
     parameter block when the chains have one: at the start of every --gain-stride-th step of every segment, the d x d matrix dp/dx with
     which a costate correction keeps the final boundary rows satisfied to first order -- exact for the discrete flow.  Written to
     PATH.rank<r>.npz: index [k], tq [k][M][cap], xq [k][M][cap][s], kp [k][M][cap][d][d] (column-major: kp[..., c, r] = dp_r/dx_c), info
-    [k][M][cap] (the elimination's code; -1: no sample), count [k][M].  Runs after the timed solve.  Needs fixed times and CONTINUOUS
-    interior nodes (the call refuses the rest).  Returns the record entry of this rank."""
+    [k][M][cap] (the elimination's code; -1: no sample), count [k][M].  Runs after the timed solve.  With --segments > 1 the final time is
+    FREE: the gains come from socp_gain_free_batch, the file also holds kt [k][M][cap][d] (dt_f/dx_c, the time-to-go feedback) and the
+    record entry says with_free_tf.  Needs CONTINUOUS interior nodes (the calls refuse the rest).  Returns the record entry of this rank."""
     conv, z, own, index, path = converged_rows(local, lo, rank, params, args.gain_out)
+    free_tf = args.segments > 1                  # the multiple-shooting layout frees the final time: the bordered sweep (socp_gain_free_batch)
     t0 = time.perf_counter()
-    r = ctx.gain_batch(z, stride=args.gain_stride, blocks=None if own is None else (own, None, None))
-    r = {k: v.cpu().numpy() for k, v in r.items()}
+    call = ctx.gain_free_batch if free_tf else ctx.gain_batch
+    r = call(z, stride=args.gain_stride, blocks=None if own is None else (own, None, None))
+    r = {k: np.ascontiguousarray(v.cpu().numpy()) for k, v in r.items()}
     wall = time.perf_counter() - t0
-    np.savez(path, index=index, tq=r["tq"], xq=r["xq"], kp=r["kp"], info=r["info"], count=r["count"])
+    if free_tf:
+        np.savez(path, index=index, tq=r["tq"], xq=r["xq"], kp=r["kp"], kt=r["kt"], info=r["info"], count=r["count"])
+    else:
+        np.savez(path, index=index, tq=r["tq"], xq=r["xq"], kp=r["kp"], info=r["info"], count=r["count"])
     solved = r["info"] == 0
     norms = np.abs(r["kp"][solved]).reshape(-1, r["kp"].shape[-1] ** 2).max(axis=1) if solved.any() else np.zeros(0)
-    return {"rows": int(len(conv)), "singular_samples": int((r["info"] > 0).sum()), "kp_norm_median": float(np.median(norms)) if len(norms) else None,
-            "stride": args.gain_stride, "wall_s": wall, "file": path}
+    out = {"rows": int(len(conv)), "singular_samples": int((r["info"] > 0).sum()), "kp_norm_median": float(np.median(norms)) if len(norms) else None,
+           "stride": args.gain_stride, "wall_s": wall, "file": path}
+    if free_tf:
+        out["with_free_tf"] = True
+    return out
 
 
 def fields_local(ctx, args, local, lo, rank, params=None):
@@ -830,8 +839,9 @@ def main():
     ap.add_argument("--gain-out", default=None, metavar="PATH",
                     help="after the solve, compute the neighbouring-extremal feedback gains of this rank's converged chains as one batch "
                          "(socp_gain_batch): dp/dx along the flight, exact for the discrete flow; writes PATH.rank<r>.npz (index, tq, xq, kp, "
-                         "info, count) and adds gain {rows, singular_samples, kp_norm_median, stride, wall_s, file} to the record.  Fixed "
-                         "times and CONTINUOUS interior nodes only; not with --model interceptor.  Absent: the timed wall and the printed "
+                         "info, count) and adds gain {rows, singular_samples, kp_norm_median, stride, wall_s, file} to the record.  With "
+                         "--segments > 1 the final time is free: socp_gain_free_batch, kt in the file and with_free_tf in the record.  "
+                         "CONTINUOUS interior nodes only; not with --model interceptor.  Absent: the timed wall and the printed "
                          "record are unchanged")
     ap.add_argument("--gain-stride", type=int, default=100, metavar="K", help="with --gain-out: a gain at the start of every K-th step")
     ap.add_argument("--fields-stride", type=int, default=100, metavar="K", help="with --fields-out: sample every K-th step (and the last)")
