@@ -1167,6 +1167,79 @@ int socp_gain_free_batch_blocks(socp_ctx *ctx, int B, const double *Z, const dou
                                 const double *xnode, int stride, int cap, double *tq, double *Ke, int *info, int *count, double *Xq,
                                 double *Wq, double *Psi, double *Len);
 
+/* CLOSED-LOOP FLIGHT UNDER THE SAMPLED NEIGHBOURING-EXTREMAL LAW: K dispersed cases per row of a batch, each flown from the first sample
+ * to the last with the costate RESET to p_nom + K_p dx at the samples of socp_gain_batch / socp_gain_free_batch -- what the two gain
+ * calls leave to the caller ("the caller applies the model's own control law at (x, p_nom + K dx), saturations included"), for a whole
+ * Monte-Carlo set in ONE launch.  The model's rhs forms its control from (x, p) inside, saturations included.  [ext] The reference has
+ * no such call.
+ * STRUCTURE.  Exactly the two the gain calls accept, and the context's problem decides which tables are expected:
+ *   every time FIXED or interpolated, interior nodes CONTINUOUS: Kg is socp_gain_batch's Kp, ldk = d;
+ *   node M's time FREE (other times FIXED or interpolated, interior nodes CONTINUOUS): Kg is socp_gain_free_batch's Ke, ldk = d + 1,
+ *   column c = (dp_0/dx_c .. dp_{d-1}/dx_c, dt_f/dx_c).
+ *   Fixed-step integrator only.  SETUP, switching times and per-row blocks as in socp_gain_batch.
+ * INPUTS.  Z[B][n], the nominal rows; stride, cap and Xq[B][M][cap][s], Kg[B][M][cap][ldk*d], info[B][M][cap], count[B][M] exactly as the
+ *   gain call with the same stride and cap left them; K >= 1 cases per row; dX0[B][K][d], the state deviation at the first sample;
+ *   every >= 0.  The tables are INPUTS, never written.  The caller may DISABLE samples by writing a nonzero info: a cut-off before the
+ *   gains blow up near the target is done that way.
+ * START.  Case (b, k) starts segment 0 from x_c = z[c] + dX0[b][k][c] (one addition per component) and p = z[d .. 2d).
+ * LOOP.  Segment after segment; across an interior node the flight goes on FROM ITS OWN STATE (it does not restart from z).  In segment i
+ *   with t1, t2 from the timeline (the final time in force in place of z[n-1] when it is FREE):
+ *     dt = (t2 - t1) / step_nbr;  t = t1;  k = 0 (the steps this segment has taken);  q = 0
+ *     act = t < t2 - dt / 2  &&  k < step_nbr + 8                      (the residual's condition and guard)
+ *     repeat:  SAMPLE q (below; it may re-time t1, t2, dt, t and then re-evaluates act)
+ *              up to `stride` times while act:  h = t + dt > t2 ? t2 - t : dt;  X = rk4(t, X, h);  t = t + dt;  k = k + 1;  act as above
+ *              q = q + 1
+ *     while act
+ *   rk4 is the residual's step on the full 2d state (Lane::rk4 in the context's flavour).  A segment that takes no step has sample 0.
+ * SAMPLE q of segment i, the start of step q stride.  g = the row-global sample index, counted over the flight's own samples in flight
+ *   order, sample (0, 0) being 0.  The sample is DUE when every > 0 and g is a multiple of `every`.  A due sample with a table slot
+ *   (q < min(count[b][i], cap)) forms dx_c = x_c - Xq[b][i][q][c] and updates dxmax = |dx_c| > dxmax ? |dx_c| : dxmax, c ascending,
+ *   from +0.0 (strict: a NaN never displaces a value, as in socp_extrema_batch).  When moreover info[b][i][q] == 0 the correction is
+ *   APPLIED (nupd + 1); every other due sample leaves the costate flowing (nskip + 1).  The correction:
+ *     p_r = Xq[b][i][q][d + r] + (Kg[r] dx_0 + Kg[ldk + r] dx_1 + ... + Kg[(d-1) ldk + r] dx_{d-1}),  r = 0 .. d-1:
+ *     c ascending, every product rounded, the sum sequential and started from the first product, then the ONE addition to the nominal
+ *     costate (reference order: nothing contracted; the throughput flavour contracts).  The costate is RESET, not incremented.
+ *   FREE final time, at an applied correction: tf' = z[n-1] + (Kg[d] dx_0 + ... + Kg[(d-1) ldk + d] dx_{d-1}), the same sum rule.  Only
+ *     when tf' != the final time in force:  it becomes tf'; t1', t2' of segment i and the switching times are re-evaluated from the
+ *     timeline with tf' as the last unknown (later segments read it when they start);  dt = (t2' - t1') / step_nbr;
+ *     t = t1' + (double)k dt;  act is re-evaluated.  Samples stay tied to the step INDEX (socp_gain_free_batch, MEANING).
+ *   Then Xs[b][k][i][q] = the state AFTER the correction, when the slot exists (q < min(count, cap)).
+ *   every = 0 is the open-loop flight; an `every` beyond the number of samples corrects once, at the first sample: dp0/dx0 alone.
+ *   With dX0 = 0 every dx is +0.0, p_nom + (a sum of zeros) is p_nom and tf' is z[n-1]: the flight is the nominal one bit for bit.
+ * OUTPUTS per case.  Xf[B][K][s]: the state as the last segment leaves it.  miss[B][K][d] ([d + 1] with a FREE final time): row j is
+ *   p_j(t_f) when final component j is FREE, else x_j(t_f) - xnode[M][j] -- the gain selector's rows as the residual forms them -- and
+ *   with a FREE final time row d = hamiltonian(t2 of the last segment, X_f).  nupd[B][K], nskip[B][K] (int32).  Each unless NULL:
+ *   tf[B][K], t2 of the last segment as in force at the end; dxmax[B][K]; Xs[B][K][M][cap][s], slots >= min(count, cap) keep what the
+ *   buffer held.
+ * FLAVOURS.  UNLIKE the gain calls each flavour flies its own arithmetic: a reference-order context the reference-order residual's
+ *   steps (every output is tests/guide_reference.py's bit for bit), a throughput context the throughput residual's, at its speed.
+ *   The double integrator is one text in both flavours and flies the reference-order arithmetic in both.
+ *   The tables are the gain calls' and hold the REFERENCE-order nominal states in both flavours: a throughput flight sees the flavours'
+ *   own deviation (rounding level) as part of dx and corrects it like any other.
+ * socp_ctx_has_guide: 1 when the model's launch table has the entry -- rhs, no switching_state hook, no custom final rows, no
+ * ComputeTraj of its own (rhs_t is not needed) -- else 0; SOCP_ERR_ARG for a NULL context.  The call itself also needs the gain entry
+ * of the structure at hand (socp_ctx_has_gain / socp_ctx_has_gain_free).
+ * SOCP_ERR_ARG: no problem set, K < 1, every < 0, B < 0, stride < 1, cap < ceil(step_nbr / stride), a NULL required pointer (Z, Xq, Kg,
+ * info, count, dX0, Xf, miss, nupd, nskip) with B > 0, _blocks with params and param_stride != nparams + 2; B == 0: SOCP_OK without a
+ * launch.  SOCP_ERR_UNSUPPORTED with the gain calls' messages: SOCP_INT_DOPRI5; no gain / gain_free entry; a free time before the final
+ * node; an interior node with a FIXED or FREE component; too many states for the batched linear solve; and: no guide entry in the launch
+ * table (the interceptor, vtolUAV, lqr1d; a plugin built before launch-table ABI 20 is refused when it registers).  An error writes
+ * nothing, launches nothing and leaves the counters unchanged.
+ * ONE launch; socp_ctx_counters advances by B K M trajectories.  _dev: device pointers, enqueue only, no allocation, no
+ * synchronisation.  Host form: stages through the context's buffers and synchronises once; Xs travels both ways.  _blocks: per-row
+ * parameter / time / xnode blocks as for socp_gain_batch_blocks. */
+int socp_ctx_has_guide(const socp_ctx *ctx);            /* 1 / 0; SOCP_ERR_ARG for a NULL context */
+int socp_guide_batch_dev(socp_ctx *ctx, int B, const double *d_Z, int stride, int cap, const double *d_Xq, const double *d_Kg,
+                         const int *d_info, const int *d_count, int K, const double *d_dX0, int every, double *d_Xf, double *d_miss,
+                         int *d_nupd, int *d_nskip, double *d_tf /* or NULL */, double *d_dxmax /* or NULL */, double *d_Xs /* or NULL */);
+int socp_guide_batch(socp_ctx *ctx, int B, const double *Z, int stride, int cap, const double *Xq, const double *Kg, const int *info,
+                     const int *count, int K, const double *dX0, int every, double *Xf, double *miss, int *nupd, int *nskip, double *tf,
+                     double *dxmax, double *Xs);
+int socp_guide_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double *params, int param_stride, const double *time,
+                            const double *xnode, int stride, int cap, const double *Xq, const double *Kg, const int *info,
+                            const int *count, int K, const double *dX0, int every, double *Xf, double *miss, int *nupd, int *nskip,
+                            double *tf, double *dxmax, double *Xs);
+
 /* HAMILTONIAN GRADIENT: the costate equations a model's Hamiltonian text implies, G = (dH/dp, -dH/dx), at a batch of points -- the
  * check of a hand-written right-hand side against its Hamiltonian, and the right-hand side of a model that brings no dynamics at all
  * (include/socp_plugin.h, "A MODEL FROM ITS HAMILTONIAN").  A model-authoring instrument: no problem has to be set, there is no sweep

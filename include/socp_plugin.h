@@ -110,6 +110,12 @@
  * by a bordered sweep).  It needs no new trait either: a model that has the gain entry and the hamiltonian_t trait gets it with no
  * source change.  A plugin built against an older launch table (ABI <= 18) is refused at registration: rebuild it.
  *
+ * Launch-table ABI 20 adds the closed-loop guidance launcher, entry `guide` (socp_guide_batch, socp_hip.h: K dispersed cases per row
+ * flown under the sampled neighbouring-extremal law).  It needs no trait at all beside rhs: every model without a switching_state hook,
+ * custom final rows or its own ComputeTraj gets the entry with no source change, and the plugin's own build flags decide its
+ * arithmetic.  The call asks for the gain entry of the problem's structure as well, so that its tables can exist.  A plugin built
+ * against an older launch table (ABI <= 19) is refused at registration: rebuild it.
+ *
  * Model ids below SOCP_PLUGIN_ID_MIN are reserved for in-tree models.
  */
 #ifndef SOCP_PLUGIN_H_

@@ -221,6 +221,11 @@ def lib():
         L.socp_gain_free_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         L.socp_gain_free_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]
         L.socp_gain_free_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]
+        L.socp_ctx_has_guide.argtypes = [_vp]
+        L.socp_guide_batch_dev.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.socp_guide_batch.argtypes = [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, C.c_int, _dp, C.c_int, _dp, _dp, _ip, _ip, _dp, _dp, _dp]
+        L.socp_guide_batch_blocks.argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip, _ip, C.c_int, _dp, C.c_int,
+                                              _dp, _dp, _ip, _ip, _dp, _dp, _dp]
         L.socp_ctx_has_hamiltonian_gradient.argtypes = [_vp]
         L.socp_hamiltonian_gradient_batch_dev.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
         L.socp_hamiltonian_gradient_batch.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp]
@@ -1092,6 +1097,68 @@ class Context:
                 self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
         out["kp"] = out["ke"][..., :d]
         out["kt"] = out["ke"][..., d]
+        return out
+
+    # -- closed-loop flight under the sampled neighbouring-extremal law
+    def has_guide(self):
+        """Whether this model has the closed-loop flight kernel (socp_ctx_has_guide): every model without a switching_state hook, custom
+        final rows or ComputeTraj of its own -- the in-tree Goddard, double integrator and covid19, and such plugins; not the interceptor,
+        not vtolUAV.  guide_batch also needs the gain entry of the problem's structure (has_gain / has_gain_free)."""
+        return self.L.socp_ctx_has_guide(self.h) == 1
+
+    def guide_batch_dev(self, B, d_Z, stride, cap, d_Xq, d_Kg, d_info, d_count, K, d_dX0, every, d_Xf, d_miss, d_nupd, d_nskip, d_tf=None,
+                        d_dxmax=None, d_Xs=None):
+        """Device pointers (ints; d_tf, d_dxmax, d_Xs may be None); enqueue only, no copy, no synchronise (socp_guide_batch_dev)."""
+        self._chk(self.L.socp_guide_batch_dev(self.h, int(B), _vp(d_Z), int(stride), int(cap), _vp(d_Xq), _vp(d_Kg), _vp(d_info), _vp(d_count),
+                                              int(K), _vp(d_dX0), int(every), _vp(d_Xf), _vp(d_miss), _vp(d_nupd), _vp(d_nskip), _vp(d_tf),
+                                              _vp(d_dxmax), _vp(d_Xs)))
+
+    def guide_batch(self, Z, dx0, stride=1, every=1, tables=None, blocks=None, xs=False):
+        """K dispersed cases per row of Z flown in closed loop under the sampled neighbouring-extremal law (include/socp_hip.h): case
+        (b, k) starts from x = z_x + dx0[b][k] with the nominal costate, takes the residual's steps through all M segments and, at every
+        `every`-th sample whose table entry has info == 0, RESETS its costate to p_nom + K_p (x - x_nom) -- and re-times the rest of the
+        flight with t_f + k_t . (x - x_nom) when the final time is FREE.  every = 0: open loop.  dx0: [B][K][d].  tables: the dict
+        gain_batch / gain_free_batch returned for the same Z, stride and blocks (with xq); None: that call is made here.  A caller may
+        disable samples by writing a nonzero info into the tables.  Returns a dict of DEVICE tensors: xf[B][K][s], miss[B][K][d]
+        ([d + 1] with a free final time: the final rows, then H), nupd, nskip[B][K] (int32), tf[B][K], dxmax[B][K], the tables, and with
+        xs=True xs[B][K][M][cap][s], the state at every sample after its correction (NaN where there is no sample)."""
+        import torch
+        dev = torch.device("cuda")
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a, dtype=np.float64))).to(device=dev, dtype=torch.float64).contiguous()  # noqa: E731
+        Zd = up(Z).reshape(-1, self.n)
+        B, M, d = Zd.shape[0], self.M, self.dim
+        free = self.n > 2 * d * M
+        stride = int(stride)
+        if tables is None:
+            tables = (self.gain_free_batch if free else self.gain_batch)(Zd, stride=stride, xq=True, blocks=blocks)
+        kg = tables["ke" if free else "kp"].contiguous()
+        xq, info, count = tables["xq"].contiguous(), tables["info"].contiguous(), tables["count"].contiguous()
+        c = int(info.shape[2])
+        D0 = up(dx0)
+        K = int(D0.shape[1]) if D0.dim() == 3 else int(D0.numel() // max(1, B * d))
+        D0 = D0.reshape(B, K, d)
+        held = [up(a).reshape(B, -1) if a is not None else None for a in (blocks if blocks is not None else ())]
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        nan = float("nan")
+        out = dict(xf=torch.full((B, K, 2 * d), nan, dtype=torch.float64, device=dev),
+                   miss=torch.full((B, K, d + 1 if free else d), nan, dtype=torch.float64, device=dev),
+                   nupd=torch.zeros((B, K), dtype=torch.int32, device=dev), nskip=torch.zeros((B, K), dtype=torch.int32, device=dev),
+                   tf=torch.full((B, K), nan, dtype=torch.float64, device=dev), dxmax=torch.full((B, K), nan, dtype=torch.float64, device=dev))
+        if xs:
+            out["xs"] = torch.full((B, K, M, c, 2 * d), nan, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        if held:
+            pp, tt, xx = held
+            self._chk(self.L.socp_problem_set_blocks_dev(self.h, ptr(pp), pp.shape[1] if pp is not None else 0, ptr(tt), ptr(xx)))
+        try:
+            self.guide_batch_dev(B, Zd.data_ptr(), stride, c, xq.data_ptr(), kg.data_ptr(), info.data_ptr(), count.data_ptr(), K, D0.data_ptr(),
+                                 int(every), out["xf"].data_ptr(), out["miss"].data_ptr(), out["nupd"].data_ptr(), out["nskip"].data_ptr(),
+                                 out["tf"].data_ptr(), out["dxmax"].data_ptr(), ptr(out.get("xs")))
+            self.synchronize()
+        finally:
+            if held:
+                self.L.socp_problem_set_blocks_dev(self.h, None, 0, None, None)
+        out["tables"] = tables
         return out
 
     # -- batched exact shooting Jacobian

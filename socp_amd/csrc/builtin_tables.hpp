@@ -38,6 +38,8 @@ hipError_t goddard_trace_fill(hipStream_t st, const ModelParams &P, const Proble
 template <class God, class GodSmooth, class Covid, class DInt>
 const ModelLaunchers *builtin_tables(int model_id)
 {
+    // the flavour this translation unit is built for: Goddard's and covid19's guide entries differ by it
+    constexpr bool kRef = God::kRefOrder;
     // goddard.cpp:23-40 defaults.  Dense output always takes the general law.
     static const ModelLaunchers goddard = [] {
         ModelLaunchers t = plugin::table<God, false>(SOCP_GODDARD_NPARAMS, 10, {3.5, 7.0, 310.0, 500.0, 1.0, 1.0, 0.0, -1.0});
@@ -48,6 +50,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.hamiltonian_jacobian = &hamiltonian_jacobian_goddard;      // kernels_hamiltonian_jacobian.hip: likewise
         t.gain = &gain_goddard;                      // kernels_gain.hip: likewise
         t.gain_free = &gain_free_goddard;            // kernels_gain_free.hip: likewise
+        t.guide = kRef ? &guide_goddard : &guide_goddard_fast;   // kernels_guide.hip / kernels_guide_fast.hip: each flavour its own
         t.traj = &goddard_by_params<&plugin::traj<GodSmooth>, &plugin::traj<God>>;
         t.eval = &goddard_by_params<&plugin::eval<GodSmooth>, &plugin::eval<God>>;
         t.residual = &goddard_by_problem<&plugin::residual<GodSmooth>, &plugin::residual<God>>;
@@ -73,6 +76,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.hamiltonian_jacobian = &hamiltonian_jacobian_dint;
         t.gain = &gain_dint;
         t.gain_free = &gain_free_dint;
+        t.guide = &guide_dint;                       // DIntFast = DIntExact: one struct, one launcher, reference order in both flavours
         return t;
     }();
     // covid19.cpp:25-38 defaults; its ModelInt integrates with its own stepNbr = 1000
@@ -85,6 +89,7 @@ const ModelLaunchers *builtin_tables(int model_id)
         t.hamiltonian_jacobian = &hamiltonian_jacobian_covid;
         t.gain = &gain_covid;
         t.gain_free = &gain_free_covid;
+        t.guide = kRef ? &guide_covid : &guide_covid_fast;
         return t;
     }();
     switch (model_id) {

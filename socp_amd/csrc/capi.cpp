@@ -2885,6 +2885,125 @@ int socp_gain_free_batch_blocks(socp_ctx *c, int B, const double *Z, const doubl
                        [&] { return socp_gain_free_batch(c, B, Z, stride, cap, tq, Ke, info, count, Xq, Wq, Psi, Len); });
 }
 
+/* ---- closed-loop flight under the sampled neighbouring-extremal law ------------------------------ */
+
+int socp_ctx_has_guide(const socp_ctx *c) { return c ? (table_of(c)->guide ? 1 : 0) : SOCP_ERR_ARG; }
+
+namespace {
+// the refusals all three forms share: those of the gain call whose tables the problem's structure expects, then the entry itself
+int guide_args(socp_ctx *c, const char *who, int B, int stride, int cap, int K, int every, bool *free_tf)
+{
+    const std::string w(who);
+    if (!c->has_problem) return fail(c, SOCP_ERR_ARG, w + ": no problem set");
+    if (K < 1 || every < 0) return fail(c, SOCP_ERR_ARG, w + ": K >= 1 and every >= 0 are required");
+    *free_tf = c->mode_t[c->M] == SOCP_FREE;
+    if (const int rc = *free_tf ? gain_free_args(c, who, B, stride, cap) : gain_args(c, who, B, stride, cap)) return rc;
+    return args_tail(c, w, table_of(c)->guide != nullptr,
+                     "guide entry (a model with a switching_state hook, custom final rows or its own ComputeTraj; rebuild a plugin written "
+                     "for an older launch table)",
+                     "the flight follows");
+}
+
+struct GuideSizes {
+    size_t nZ, slots, segs, nXq, nKg, nD0, cases, nXf, nMiss, nXs;
+};
+GuideSizes guide_sizes(const socp_ctx *c, int B, int cap, int K, bool free_tf, bool xs)
+{
+    GuideSizes g;
+    const size_t d = (size_t)c->dim, s = (size_t)c->S;
+    g.nZ = (size_t)B * c->n;
+    g.segs = (size_t)B * c->M;
+    g.slots = g.segs * cap;
+    g.nXq = g.slots * s;
+    g.nKg = g.slots * (free_tf ? d + 1 : d) * d;
+    g.cases = (size_t)B * K;
+    g.nD0 = g.cases * d;
+    g.nXf = g.cases * s;
+    g.nMiss = g.cases * (free_tf ? d + 1 : d);
+    g.nXs = xs ? g.cases * c->M * cap * s : 0;
+    return g;
+}
+}  // namespace
+
+int socp_guide_batch_dev(socp_ctx *c, int B, const double *d_Z, int stride, int cap, const double *d_Xq, const double *d_Kg, const int *d_info,
+                         const int *d_count, int K, const double *d_dX0, int every, double *d_Xf, double *d_miss, int *d_nupd, int *d_nskip,
+                         double *d_tf, double *d_dxmax, double *d_Xs)
+{
+    if (!c) return SOCP_ERR_ARG;
+    bool free_tf = false;
+    if (const int rc = guide_args(c, "guide_batch", B, stride, cap, K, every, &free_tf)) return rc;
+    if (B > 0 && (!d_Z || !d_Xq || !d_Kg || !d_info || !d_count || !d_dX0 || !d_Xf || !d_miss || !d_nupd || !d_nskip))
+        return fail(c, SOCP_ERR_ARG, "guide_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    GuideArgs A;
+    A.K = K; A.stride = stride; A.cap = cap; A.every = every;
+    A.Xq = d_Xq; A.Kg = d_Kg; A.dX0 = d_dX0; A.info = d_info; A.count = d_count;
+    A.Xf = d_Xf; A.miss = d_miss; A.tf = d_tf; A.dxmax = d_dxmax; A.Xs = d_Xs; A.nupd = d_nupd; A.nskip = d_nskip;
+    // ONE launch: every case flies its M segments
+    c->n_traj += (long long)B * K * c->M; c->n_launch += 1;
+    HIP_TRY(c, table_of(c)->guide(c->stream, c->P, c->pb, B, d_Z, free_tf ? 1 : 0, A));
+    return SOCP_OK;
+}
+
+int socp_guide_batch(socp_ctx *c, int B, const double *Z, int stride, int cap, const double *Xq, const double *Kg, const int *info,
+                     const int *count, int K, const double *dX0, int every, double *Xf, double *miss, int *nupd, int *nskip, double *tf,
+                     double *dxmax, double *Xs)
+{
+    if (!c) return SOCP_ERR_ARG;
+    bool free_tf = false;
+    if (const int rc = guide_args(c, "guide_batch", B, stride, cap, K, every, &free_tf)) return rc;
+    if (B > 0 && (!Z || !Xq || !Kg || !info || !count || !dX0 || !Xf || !miss || !nupd || !nskip))
+        return fail(c, SOCP_ERR_ARG, "guide_batch: null argument");
+    if (B == 0) return SOCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const GuideSizes g = guide_sizes(c, B, cap, K, free_tf, Xs != nullptr);
+    // the inputs: Z, the tables and the deviations; the integer tables behind the doubles
+    double *dZ;
+    int *dI;
+    HIP_TRY(c, stage_up(c, c->s_in, Z, g.nZ, dZ, g.nZ + g.nXq + g.nKg + g.nD0));
+    double *dQ = dZ + g.nZ, *dK = dQ + g.nXq, *dD = dK + g.nKg;
+    HIP_TRY(c, copy_up(c, dQ, Xq, g.nXq));
+    HIP_TRY(c, copy_up(c, dK, Kg, g.nKg));
+    HIP_TRY(c, copy_up(c, dD, dX0, g.nD0));
+    HIP_TRY(c, stage_up(c, c->s_var, info, g.slots, dI, g.slots + g.segs + 2 * g.cases));
+    int *dC = dI + g.slots, *dU = dC + g.segs, *dS = dU + g.cases;
+    HIP_TRY(c, copy_up(c, dC, count, g.segs));
+    // the outputs; Xs travels both ways: the slots at or beyond count come back as they went
+    HIP_TRY(c, c->s_out.reserve(sizeof(double) * (g.nXf + g.nMiss + 2 * g.cases + g.nXs)));
+    double *dF = c->s_out.as<double>(), *dM = dF + g.nXf, *dT = dM + g.nMiss, *dX = dT + g.cases, *dXs = dX + g.cases;
+    if (Xs) HIP_TRY(c, copy_up(c, dXs, Xs, g.nXs));
+    const int rc = socp_guide_batch_dev(c, B, dZ, stride, cap, dQ, dK, dI, dC, K, dD, every, dF, dM, dU, dS, tf ? dT : nullptr,
+                                        dxmax ? dX : nullptr, Xs ? dXs : nullptr);
+    if (rc != SOCP_OK) return rc;
+    HIP_TRY(c, copy_down(c, Xf, dF, g.nXf));
+    HIP_TRY(c, copy_down(c, miss, dM, g.nMiss));
+    HIP_TRY(c, copy_down(c, nupd, dU, g.cases));
+    HIP_TRY(c, copy_down(c, nskip, dS, g.cases));
+    if (tf) HIP_TRY(c, copy_down(c, tf, dT, g.cases));
+    if (dxmax) HIP_TRY(c, copy_down(c, dxmax, dX, g.cases));
+    if (Xs) HIP_TRY(c, copy_down(c, Xs, dXs, g.nXs));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SOCP_OK;
+}
+
+int socp_guide_batch_blocks(socp_ctx *c, int B, const double *Z, const double *params, int pstride, const double *time, const double *xnode,
+                            int stride, int cap, const double *Xq, const double *Kg, const int *info, const int *count, int K,
+                            const double *dX0, int every, double *Xf, double *miss, int *nupd, int *nskip, double *tf, double *dxmax,
+                            double *Xs)
+{
+    if (!c) return SOCP_ERR_ARG;
+    bool free_tf = false;
+    if (const int rc = guide_args(c, "guide_batch_blocks", B, stride, cap, K, every, &free_tf)) return rc;
+    if (const int rc = blocks_stride(c, "guide_batch_blocks: the parameter stride", params, pstride)) return rc;
+    if (B > 0 && (!Z || !Xq || !Kg || !info || !count || !dX0 || !Xf || !miss || !nupd || !nskip))
+        return fail(c, SOCP_ERR_ARG, "guide_batch_blocks: null argument");
+    if (B == 0) return SOCP_OK;
+    return with_blocks(c, B, params, pstride, time, xnode, [&] {
+        return socp_guide_batch(c, B, Z, stride, cap, Xq, Kg, info, count, K, dX0, every, Xf, miss, nupd, nskip, tf, dxmax, Xs);
+    });
+}
+
 /* ---- row grouping --------------------------------------------------------------------------- */
 
 namespace {

@@ -39,7 +39,7 @@ inline int rows_per_block(int M, int n)
 
 // Launch table of a model (plugin_impl.hpp): what the C-ABI layer calls.  In-tree models bring theirs below (the Goddard table
 // picks the control law per launch, builtin_tables.hpp); an out-of-tree model registers one (include/socp_plugin.h).
-constexpr int kPluginAbi = 19;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
+constexpr int kPluginAbi = 20;     // 3: ProblemDev carries per-problem blocks; 4: optional variational launchers; 5: ModelParams carries the map table;
                                    // 6: batched trace launchers; 7: batched cost launcher; 8: batched move launcher;
                                    // kPluginAbi = 9: batched events launcher; kPluginAbi = 10: batched Jacobi-field launcher;
                                    // kPluginAbi = 11: batched exact-fields launcher
@@ -51,12 +51,24 @@ constexpr int kPluginAbi = 19;     // 3: ProblemDev carries per-problem blocks; 
                                    // kPluginAbi = 17: Hamiltonian-Jacobian launcher
                                    // kPluginAbi = 18: batched neighbouring-extremal gain launcher
                                    // kPluginAbi = 19: the same with a free final time (bordered sweep)
+                                   // kPluginAbi = 20: closed-loop guidance launcher (until then `constexpr int kPluginAbi = 19;`)
 // the integrating directions of one kind of socp_sensitivity_batch as they travel to the kernel (sensitivity.hpp): 16 bits per
 // direction, four to a word.  slot: the direction's place k in the call's table (4 bits each); index: the parameter or the node
 constexpr int kSensParam = 0, kSensTime = 1;
 struct SensDirs {
     int kind, n;                                     // kSensParam / kSensTime; 1 <= n <= 16
     unsigned long long slot, index[4];
+};
+
+// socp_guide_batch as it travels to the kernel (guide.hpp): K cases per row, the tables of the gain call with the same stride and cap
+// (Xq[B][M][cap][s], Kg[B][M][cap][ldk d], info[B][M][cap], count[B][M]), the deviations dX0[B][K][d], `every`; the outputs per case,
+// tf, dxmax and Xs null when not wanted
+struct GuideArgs {
+    int K, stride, cap, every;
+    const double *Xq, *Kg, *dX0;
+    const int *info, *count;
+    double *Xf, *miss, *tf, *dxmax, *Xs;
+    int *nupd, *nskip;
 };
 
 struct ModelLaunchers {
@@ -146,6 +158,13 @@ struct ModelLaunchers {
     // contraction that both flavours' tables point to
     hipError_t (*gain_free)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, int, double *, double *, int *,
                             double *, double *, double *, double *, double *, double *);
+    // closed-loop flight under the sampled neighbouring-extremal law (socp_guide_batch): Z[B][n], free_tf (0: the tables are
+    // socp_gain_batch's, ldk = d; 1: socp_gain_free_batch's, ldk = d + 1, and the final time is re-timed), the tables and the outputs
+    // of GuideArgs; fixed-step integrator only.  ONE launch, one lane per (row, case).  Null: the model has a switching_state hook,
+    // custom final rows or its own ComputeTraj (plugin_impl.hpp).  UNLIKE the gain entries the two flavours' tables point to their OWN
+    // launcher: the in-tree models' entries live in kernels_guide.hip (no contraction) and kernels_guide_fast.hip (contraction on; the
+    // double integrator, one struct in both flavours, has the reference-order launcher in both tables)
+    hipError_t (*guide)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, int, const GuideArgs &);
 };
 
 // flavour-independent: Jacobian from the rows of fdrows (differences and one division per entry)
@@ -311,6 +330,17 @@ hipError_t gain_free_dint(hipStream_t st, const ModelParams &P, const ProblemDev
                           double *Xq, int *count, double *Psi, double *Len, double *gradH, double *Wq, double *A, double *Ke);
 hipError_t gain_free_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int stride, int cap, double *tq,
                            double *Xq, int *count, double *Psi, double *Len, double *gradH, double *Wq, double *A, double *Ke);
+
+// socp_guide_batch of the in-tree models (kernels_guide.hip: the reference-order models without contraction; kernels_guide_fast.hip:
+// the throughput flavour's models with contraction on -- a throughput context flies at throughput speed); Goddard's pick the law per
+// launch as its trace entry does.  The double integrator is one struct in both flavours (DIntFast = DIntExact): ONE launcher, guide_dint,
+// for both tables
+hipError_t guide_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int free_tf, const GuideArgs &A);
+hipError_t guide_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int free_tf, const GuideArgs &A);
+hipError_t guide_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int free_tf, const GuideArgs &A);
+hipError_t guide_goddard_fast(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int free_tf,
+                              const GuideArgs &A);
+hipError_t guide_covid_fast(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int free_tf, const GuideArgs &A);
 
 // socp_exact_jacobian_batch of the in-tree models (kernels_exact_jacobian.hip: one object without contraction, for both flavours)
 hipError_t exact_jacobian_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);

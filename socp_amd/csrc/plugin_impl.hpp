@@ -82,6 +82,7 @@
 #include "sensitivity.hpp"
 #include "gain.hpp"
 #include "gain_free.hpp"
+#include "guide.hpp"
 #include "hamiltonian_model.hpp"
 #include "jacobi.hpp"
 #include "launch.hpp"
@@ -413,6 +414,25 @@ hipError_t gain_free(hipStream_t st, const ModelParams &P, const ProblemDev &pb,
     return hipGetLastError();
 }
 
+// rhs and none of the hooks has_gain excludes -> the model has the closed-loop flight (socp_guide_batch).  rhs_t is NOT needed: the
+// flight is a plain trajectory; the entry points ask for the gain entry of the structure at hand, so that the tables can exist
+template <class M>
+struct has_guide : std::bool_constant<!has_custom_traj<M>::value && !has_custom_final<M>::value && !has_switching_state<M>::value> {};
+
+// closed-loop flight of K cases per row: fixed-step integrator only.  ONE launch, one lane per (row, case) (guide.hpp); the occupancy
+// cap follows the number of waves like every other hot kernel.  Reference order: the translation unit must be built without contraction
+template <class Mdl>
+hipError_t guide(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int free_tf, const GuideArgs &A)
+{
+    if (B <= 0) return hipSuccess;
+    if (P.integrator != 0 || A.K < 1 || A.stride < 1 || A.cap < 1 || A.every < 0 || !A.Xq || !A.Kg || !A.dX0 || !A.info || !A.count || !A.Xf ||
+        !A.miss || !A.nupd || !A.nskip)
+        return hipErrorInvalidValue;
+    if (free_tf) SOCP_PLUGIN_LAUNCH_PB_LDS(guide_free_kernel, false, blocks_for((long)B * A.K), 0, st, P, pb, B, Z, A);
+    else SOCP_PLUGIN_LAUNCH_PB_LDS(guide_kernel, false, blocks_for((long)B * A.K), 0, st, P, pb, B, Z, A);
+    return hipGetLastError();
+}
+
 // optional trait hamiltonian_t alone -> the model has the Hamiltonian gradient (socp_hamiltonian_gradient_batch): the check of a
 // hand-written rhs against its Hamiltonian text (hamiltonian_model.hpp)
 template <class M, class = void> struct has_hamiltonian_gradient : std::false_type {};
@@ -456,9 +476,10 @@ struct has_variational<M, std::void_t<decltype(M::aug_rhs(std::declval<const Mod
                                       decltype(M::dhamiltonian(std::declval<const ModelParams &>(), 0.0, (const double *)nullptr,
                                                                std::declval<double (&)[M::S + 1]>()))>> : std::true_type {};
 
-// FIELDS = false: leave the fields, exact_jacobian, sensitivity, hamiltonian_gradient, hamiltonian_jacobian, gain and gain_free entries
-// to the caller (the in-tree models' entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip,
-// kernels_hamiltonian.hip, kernels_hamiltonian_jacobian.hip, kernels_gain.hip and kernels_gain_free.hip, builtin_tables.hpp)
+// FIELDS = false: leave the fields, exact_jacobian, sensitivity, hamiltonian_gradient, hamiltonian_jacobian, gain, gain_free and guide
+// entries to the caller (the in-tree models' entries live in kernels_fields.hip, kernels_exact_jacobian.hip, kernels_sensitivity.hip,
+// kernels_hamiltonian.hip, kernels_hamiltonian_jacobian.hip, kernels_gain.hip, kernels_gain_free.hip and kernels_guide[_fast].hip,
+// builtin_tables.hpp)
 template <class Mdl, bool FIELDS = true>
 ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> defaults)
 {
@@ -489,6 +510,7 @@ ModelLaunchers table(int nparams, int step_nbr, std::initializer_list<double> de
     if constexpr (FIELDS && has_hamiltonian_jacobian<Mdl>::value) t.hamiltonian_jacobian = &hamiltonian_jacobian<Mdl>;
     if constexpr (FIELDS && has_gain<Mdl>::value) t.gain = &gain<Mdl>;
     if constexpr (FIELDS && has_gain_free<Mdl>::value) t.gain_free = &gain_free<Mdl>;
+    if constexpr (FIELDS && has_guide<Mdl>::value) t.guide = &guide<Mdl>;
     if constexpr (has_variational<Mdl>::value) {
         t.var_traj = &varimpl::traj<Mdl>; t.var_jacobian = &varimpl::jacobian<Mdl>; t.var_eval = &varimpl::eval<Mdl>;
     }

@@ -405,6 +405,33 @@ def exactjac_local(ctx, args, local, lo, rank, params=None):
             "sigma_min_min": float(sigma[:, -1].min()) if some and sigma.shape[1] else None, "wall_s": wall, "file": path}
 
 
+def guide_local(ctx, args, local, lo, rank, params=None):
+    """--guide-out: this rank's CONVERGED chains flown in closed loop under the sampled neighbouring-extremal law (socp_guide_batch),
+    --guide-cases dispersed cases per chain: dX0 = --guide-sigma max(1, |x0_c|) N(0, 1) from a numpy generator seeded with --guide-seed
+    (+ rank), once with a correction at every --guide-every-th sample of the gains at stride --gain-stride and once open loop.  Written to
+    PATH.rank<r>.npz: index [k], dx0 [k][K][d], miss and miss_open [k][K][d (+ 1 with a free final time: the H row)], nupd, nskip [k][K],
+    tf [k][K].  Runs after the timed solve.  With --segments > 1 the final time is FREE and the flight is re-timed.  Returns the record
+    entry of this rank: the median and the 95th percentile of ||miss||inf over all cases, closed loop and open."""
+    conv, z, own, index, path = converged_rows(local, lo, rank, params, args.guide_out)
+    K, d = args.guide_cases, ctx.dim
+    rng = np.random.default_rng(args.guide_seed + rank)
+    dx0 = args.guide_sigma * np.maximum(1.0, np.abs(np.asarray(z)[:, None, :d])) * rng.standard_normal((len(conv), K, d))
+    blocks = None if own is None else (own, None, None)
+    t0 = time.perf_counter()
+    closed = ctx.guide_batch(z, dx0, stride=args.gain_stride, every=args.guide_every, blocks=blocks)
+    opened = ctx.guide_batch(z, dx0, stride=args.gain_stride, every=0, tables=closed["tables"], blocks=blocks)
+    wall = time.perf_counter() - t0
+    host = lambda t: np.ascontiguousarray(t.cpu().numpy())                                          # noqa: E731
+    miss, miss_open, nupd, nskip, tf = host(closed["miss"]), host(opened["miss"]), host(closed["nupd"]), host(closed["nskip"]), host(closed["tf"])
+    np.savez(path, index=index, dx0=dx0, miss=miss, miss_open=miss_open, nupd=nupd, nskip=nskip, tf=tf)
+    norm = lambda m: np.abs(m).reshape(-1, m.shape[-1]).max(axis=1) if m.size else np.zeros(0)      # noqa: E731
+    pct = lambda v, p: float(np.nanpercentile(v, p)) if len(v) and not np.all(np.isnan(v)) else None    # noqa: E731
+    a, b = norm(miss), norm(miss_open)
+    return {"rows": int(len(conv)), "cases": K, "miss_median": pct(a, 50), "miss_p95": pct(a, 95), "miss_open_median": pct(b, 50),
+            "miss_open_p95": pct(b, 95), "skipped_samples": int(nskip.sum()), "every": args.guide_every, "stride": args.gain_stride,
+            "sigma": args.guide_sigma, "wall_s": wall, "file": path}
+
+
 def gain_local(ctx, args, local, lo, rank, params=None):
     """--gain-out: the neighbouring-extremal feedback gains (socp_gain_batch) of this rank's CONVERGED chains, each with its own
     parameter block when the chains have one: at the start of every --gain-stride-th step of every segment, the d x d matrix dp/dx with
@@ -843,7 +870,19 @@ def main():
                          "--segments > 1 the final time is free: socp_gain_free_batch, kt in the file and with_free_tf in the record.  "
                          "CONTINUOUS interior nodes only; not with --model interceptor.  Absent: the timed wall and the printed "
                          "record are unchanged")
-    ap.add_argument("--gain-stride", type=int, default=100, metavar="K", help="with --gain-out: a gain at the start of every K-th step")
+    ap.add_argument("--gain-stride", type=int, default=100, metavar="K",
+                    help="with --gain-out and --guide-out: a gain at the start of every K-th step")
+    ap.add_argument("--guide-out", default=None, metavar="PATH",
+                    help="after the solve, fly --guide-cases dispersed cases per converged chain in closed loop under the sampled "
+                         "neighbouring-extremal law (socp_guide_batch), and once more open loop; writes PATH.rank<r>.npz (index, dx0, miss, "
+                         "miss_open, nupd, nskip, tf) and adds guide {rows, cases, miss_median, miss_p95, miss_open_median, miss_open_p95, "
+                         "skipped_samples, ...} to the record.  The gains are those of --gain-stride.  CONTINUOUS interior nodes only; not "
+                         "with --model interceptor.  Absent: the timed wall and the printed record are unchanged")
+    ap.add_argument("--guide-cases", type=int, default=16, metavar="K", help="with --guide-out: dispersed cases per chain")
+    ap.add_argument("--guide-sigma", type=float, default=1e-3, metavar="S",
+                    help="with --guide-out: dX0 = S max(1, |x0_c|) N(0, 1) at the first sample")
+    ap.add_argument("--guide-every", type=int, default=1, metavar="E", help="with --guide-out: a correction at every E-th sample")
+    ap.add_argument("--guide-seed", type=int, default=0, metavar="N", help="with --guide-out: the seed of the deviations (+ the rank)")
     ap.add_argument("--fields-stride", type=int, default=100, metavar="K", help="with --fields-out: sample every K-th step (and the last)")
     ap.add_argument("--fields-skip", type=int, default=0, metavar="S", help="with --fields-out: compare the samples from the S-th on")
     ap.add_argument("--fields-phi", action="store_true",
@@ -900,6 +939,10 @@ def main():
         ap.error("--gain-out: the interceptor has no gain entry (its own ComputeTraj and final rows)")
     if args.gain_stride < 1:
         ap.error("--gain-stride must be >= 1")
+    if args.guide_out and args.model == "interceptor":
+        ap.error("--guide-out: the interceptor has no guide entry (its own ComputeTraj and final rows)")
+    if args.guide_cases < 1 or args.guide_every < 0 or not args.guide_sigma >= 0:
+        ap.error("--guide-cases must be >= 1, --guide-every >= 0 and --guide-sigma >= 0")
     if args.exactjac_out and args.model == "interceptor":
         ap.error("--exactjac-out: the interceptor has no exact-Jacobian kernel (its own ComputeTraj and final rows)")
     if args.extrema_out and args.model == "interceptor":
@@ -1067,6 +1110,8 @@ def main():
         extra["fields" if rank == 0 else "fields_rank%d" % rank] = fields_local(ctx, args, local, lo_w, rank, blocks)
     if args.gain_out:
         extra["gain" if rank == 0 else "gain_rank%d" % rank] = gain_local(ctx, args, local, lo_w, rank, blocks)
+    if args.guide_out:
+        extra["guide" if rank == 0 else "guide_rank%d" % rank] = guide_local(ctx, args, local, lo_w, rank, blocks)
     if args.exactjac_out:
         extra["exact_jacobian" if rank == 0 else "exact_jacobian_rank%d" % rank] = exactjac_local(ctx, args, local, lo_w, rank, blocks)
     if args.extrema_out:
