@@ -117,6 +117,12 @@ int socp_ctx_get_integrator(const socp_ctx *ctx, int *step_nbr, int *kind, doubl
 int socp_ctx_set_switching_times(socp_ctx *ctx, const double *sw, int nsw);  /* goddard.cpp:373-377 */
 int socp_ctx_get_switching_times(const socp_ctx *ctx, double *sw2);          /* the two values the control law reads */
 int socp_ctx_set_variant(socp_ctx *ctx, int variant);
+/* vtolUAV's entries of the exact-derivative stack (socp_fields_batch, socp_exact_jacobian_batch, socp_newton_batch with jac = 2) are
+ * switched per context and are OFF in a new one: until socp_ctx_set_exact_hooks(ctx, 1) the context answers as it did before the model
+ * had them -- socp_ctx_has_fields and socp_ctx_has_exact_jacobian 0, the calls SOCP_ERR_UNSUPPORTED ("no fields entry", "no
+ * exact_jacobian entry").  on = 0 switches them off again; socp_ctx_clone copies the setting.  SOCP_ERR_UNSUPPORTED for any other
+ * model: theirs are not switched. */
+int socp_ctx_set_exact_hooks(socp_ctx *ctx, int on);
 int socp_ctx_get_variant(const socp_ctx *ctx);      /* SOCP_VARIANT_* as set (AUTO = reference order) */
 /* enqueue on the caller's hipStream_t (NULL is the device's default stream); use_own != 0 switches
  * back to the context's private non-blocking stream */
@@ -516,6 +522,8 @@ int socp_jacobi_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
  *   -a and |a| act on both parts, |a| flips d when v < 0;
  *   sqrt a: s = sqrt(a.v), (s, a.d / (s + s)), the derivative +0.0 when s == 0 (Goddard's norm_u with the thrust off);
  *   exp a: e = the model's exp (exp_glibc for Goddard), (e, e a.d);
+ *   tanh a: th = tanh(a.v), the device library's tanh (vtolUAV's map), (th, (1.0 - th th) a.d) -- the product th th, the difference
+ *   from 1.0, the product with a.d, in that order (d_tanh, dual.hpp; dual numbers only, the nested and wide numbers have no such rule);
  *   comparisons read v; a branch's derivative is that of the branch taken;
  *   a plain double c (a parameter, a literal, t, h, and a control or penalty that the law makes a constant: thrust off or full, a
  *   clamped control, an inactive penalty) takes part with its zero derivative terms DROPPED, not computed:
@@ -534,13 +542,17 @@ int socp_jacobi_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
  * WHAT IT IS AND IS NOT.  The caveats of the Jacobi test stand: the classical statement is for M = 1 with a fixed initial state, and
  * with a free final time the plain determinant is not the right test (use Phi).  The result is exact for the DISCRETE flow, to
  * rounding -- not for the differential equation.  A determinant that is zero to rounding (table above) has no sign to read.  A
- * state-dependent kink (Switch < 0, a saturation) differentiates the branch taken.  Out of scope: the adaptive integrator, the
- * interceptor, vtolUAV, a jac = 2 for socp_tangent_batch / socp_singular_batch / socp_branch_batch, hybrj for Goddard
+ * state-dependent kink (Switch < 0, a saturation) differentiates the branch taken.  vtolUAV: rhs_t is the reference-order text of
+ * both flavours' contexts (control_t, map_exact_t on T: the table read as the residual reads it, the NaN reset testing the VALUE
+ * part and zeroing the whole number, the upstream quirks kept); tanh is the device library's, so wherever the map is live the bits
+ * are the kernel's own and the test holds Phi to a 240-bit evaluation, with an EMPTY map every bit is the restatement's
+ * (tests/vtol_exact_reference.py).  Out of scope: the adaptive integrator, the
+ * interceptor, a jac = 2 for socp_tangent_batch / socp_singular_batch / socp_branch_batch, hybrj for Goddard
  * (socp_ctx_has_variational stays 0 for it), more than one GPU.
- * socp_ctx_has_fields: 1 when the context's model has the entry, else 0.
+ * socp_ctx_has_fields: 1 when the context's model has the entry (vtolUAV: after socp_ctx_set_exact_hooks(ctx, 1)), else 0.
  * SOCP_ERR_ARG: as socp_jacobi_batch, and cols outside 0 .. 1; B == 0: SOCP_OK without a launch; SOCP_ERR_UNSUPPORTED (the message
  * says which): the context's integrator is SOCP_INT_DOPRI5, or the model's launch table has no fields entry (the interceptor,
- * vtolUAV, a plugin without the rhs_t trait).  An error writes nothing and leaves the context unchanged.
+ * vtolUAV before socp_ctx_set_exact_hooks, a plugin without the rhs_t trait).  An error writes nothing and leaves the context unchanged.
  * One launch; socp_ctx_counters advances by B M C trajectories.  The _dev, host and _blocks forms as for socp_jacobi_batch. */
 #define SOCP_FIELDS_COSTATE 0   /* C = d columns: the unit vectors of p(t_i)                 */
 #define SOCP_FIELDS_ALL     1   /* C = s = 2d columns: the unit vectors of X(t_i), x first    */
@@ -592,6 +604,18 @@ int socp_fields_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
  *   it is FIXED; and, where the model's free-time row is H(t, X) - H(t, Xp) (trait kSwitchingReadsXp: the double integrator,
  *   covid19; not Goddard, whose row is H(t, X)), the derivative part of -hamiltonian_t(t1, (X0, e_c)) at (ft_row[i], S i + c).
  *   Every entry then has exactly one writer.
+ * CUSTOM FINAL ROWS AND THE SWITCHING_STATE HOOK (vtolUAV; a plugin through the traits of plugin_impl.hpp).  A model whose last node
+ *   has rows of its own (kCustomFinal) brings final_row_t, the text of final_row over a number type: rows d + j of segment M - 1 are
+ *   final_row_t(j, mode, X, xd) on the dual END state in either mode -- vtolUAV: X[j + d] - invSigmaXwp (nWP_tot - nWP) (X[j] - xd[j])
+ *   - 0.02 (X[j] - xd[j]) where component j is FREE, X[j] - xd[j] otherwise -- and row ft_row[M] is hamiltonian_t(t2, X) +
+ *   final_h_offset, the offset a plain double.  A model with a switching_state hook brings switching_state_t, the hook with X over a
+ *   number type and Xp as the plain doubles they are: where component j of interior node i + 1 is FREE, rows S (i + 1) + j and
+ *   S (i + 1) + d + j are its f_state and f_costate on the dual END state of segment i -- vtolUAV: X[j] - Xp[j] and
+ *   (X[j + d] - Xp[j + d]) - invSigmaXwp (X[j] - xd[j]) -- stored by the lanes of the segment that ENDS there, its length lane
+ *   included.  The model must also declare kSwitchingStateXpContinuous = true: the PROMISE that the hook reads Xp only as -Xp[j] in
+ *   f_state and -Xp[j + d] in f_costate.  The state lanes of segment i + 1 then store -1.0 at (S (i + 1) + c, S (i + 1) + c) for
+ *   these components exactly as for a CONTINUOUS one: every entry keeps one writer.  Without final_row_t, or without switching_state_t
+ *   and the promise, such a model has no entry.
  * FREE-TIME COLUMNS.  The segment lies between the junctions A <= i and Bn >= i + 1 (A = i or lo[i], Bn = i + 1 or hi[i + 1]).  For
  * f in {A, Bn} with node f FREE and unknown index k, the length lane stores w (d row / d L) -- one product -- at (row, k) for every
  * END-state row above, w = c(i + 1, f) - c(i, f), where c(j, f) is 1.0 for j == f, (double)(j - a) / (double)(b - a) for a node j
@@ -603,15 +627,20 @@ int socp_fields_batch_blocks(socp_ctx *ctx, int B, const double *Z, const double
  * WHAT IT IS AND IS NOT.  Exact for the DISCRETE flow, to rounding, apart from what is listed as not differentiated; the forward
  * difference sees those dependences (and noise).  tests/exact_jacobian_reference.py restates the definition; the tests compare whole
  * buffers to it.  Out of scope: jac = 2 in socp_tangent_batch / socp_singular_batch / socp_branch_batch (they keep 0 .. 1), hybrj
- * for Goddard inside socp_chains_solve, the adaptive integrator, the interceptor, vtolUAV, derivatives with respect to parameters,
- * more than one GPU.
+ * for Goddard inside socp_chains_solve, the adaptive integrator, the interceptor, derivatives with respect to parameters,
+ * more than one GPU.  vtolUAV has the entry in both flavours once the context asked for it (socp_ctx_set_exact_hooks; one reference-order object, kernels_vtol_exact.hip; 13 lanes, 4 groups):
+ * with an EMPTY map every bit is the restatement's, with a live map tanh is the device library's and the matrix is held to a 240-bit
+ * evaluation (tests/vtol_exact_reference.py, tests/test_gpu_vtol_exact.py); its sensitivities, gains, guidance and Hamiltonian
+ * point calls stay refused.
  * socp_ctx_has_exact_jacobian: 1 when the context's model has the entry -- the traits rhs_t, hamiltonian_t and switching_fn_t, no
- * switching_state hook, no custom final rows, no ComputeTraj of its own -- else 0; SOCP_ERR_ARG for a NULL context (as
+ * ComputeTraj of its own, final_row_t if it has custom final rows, switching_state_t with kSwitchingStateXpContinuous if it has a
+ * switching_state hook; vtolUAV: after socp_ctx_set_exact_hooks(ctx, 1) -- else 0; SOCP_ERR_ARG for a NULL context (as
  * socp_ctx_has_fields).
  * SOCP_ERR_ARG: no problem set, B < 0, a NULL Z or Fjac with B > 0, a wrong parameter stride (_blocks); B == 0: SOCP_OK without a
  * launch; SOCP_ERR_UNSUPPORTED (the message says which): the context's integrator is SOCP_INT_DOPRI5, the model's launch table has no
- * exact_jacobian entry (the interceptor, vtolUAV, a plugin without the traits), or the problem has a FREE state component on an
- * interior node (its rows are the model's SwitchingStateFunction).  An error writes nothing and leaves the context unchanged.
+ * exact_jacobian entry (the interceptor, vtolUAV before socp_ctx_set_exact_hooks, a plugin without the traits), or the problem has a FREE state component on an
+ * interior node of a model other than vtolUAV (its rows are the model's SwitchingStateFunction; the launch table does not say
+ * whether a plugin's entry covers them).  An error writes nothing and leaves the context unchanged.
  * socp_ctx_counters advances by B M (S + 1) trajectories and one launch.  The _dev, host and _blocks forms as for socp_fields_batch. */
 int socp_ctx_has_exact_jacobian(const socp_ctx *ctx);   /* 1 / 0; SOCP_ERR_ARG for a NULL context */
 int socp_exact_jacobian_batch_dev(socp_ctx *ctx, int B, const double *d_Z, double *d_Fjac, double *d_F /* or NULL */);

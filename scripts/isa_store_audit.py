@@ -36,6 +36,7 @@ UNITS = {
     "kernels_interceptor_fast": ("socp_amd/csrc/kernels_interceptor_fast.hip", ["-ffp-contract=fast"]),
     "kernels_vtol": ("socp_amd/csrc/kernels_vtol.hip", ["-ffp-contract=off"]),
     "kernels_vtol_fast": ("socp_amd/csrc/kernels_vtol_fast.hip", ["-ffp-contract=fast"]),
+    "kernels_vtol_exact": ("socp_amd/csrc/kernels_vtol_exact.hip", ["-ffp-contract=off"]),
     "kernels_solver": ("socp_amd/csrc/kernels_solver.hip", ["-ffp-contract=off"]),
     "kernels_factor_fast": ("socp_amd/csrc/kernels_factor_fast.hip", ["-ffp-contract=fast"]),
     "kernels_gain": ("socp_amd/csrc/kernels_gain.hip", ["-ffp-contract=off"]),

@@ -126,6 +126,7 @@ def lib():
         L.socp_ctx_get_integrator.argtypes = [_vp, _ip, _ip, _dp]
         L.socp_ctx_set_switching_times.argtypes = [_vp, _dp, C.c_int]
         L.socp_ctx_set_variant.argtypes = [_vp, C.c_int]
+        L.socp_ctx_set_exact_hooks.argtypes = [_vp, C.c_int]
         L.socp_ctx_set_stream.argtypes = [_vp, _vp, C.c_int]
         L.socp_ctx_aux_stream.argtypes = [_vp, C.POINTER(C.c_void_p)]
         L.socp_ctx_dims.argtypes = [_vp, _ip, _ip, _ip]
@@ -512,6 +513,11 @@ class Context:
 
     def set_variant(self, v):
         self._chk(self.L.socp_ctx_set_variant(self.h, int(v)))
+
+    def set_exact_hooks(self, on=True):
+        """vtolUAV only: switch the context's exact fields / exact Jacobian / Newton jac = 2 on (they are off in a new context, which
+        then answers as before the model had them: socp_ctx_set_exact_hooks)."""
+        self._chk(self.L.socp_ctx_set_exact_hooks(self.h, int(bool(on))))
 
     def get_variant(self):
         return int(self.L.socp_ctx_get_variant(self.h))
@@ -940,7 +946,7 @@ class Context:
     # -- batched exact fields
     def has_fields(self):
         """Whether this model has an exact-fields kernel (socp_ctx_has_fields): the in-tree Goddard, double integrator and covid19,
-        and a plugin with the rhs_t trait; not the interceptor, not vtolUAV."""
+        vtolUAV after set_exact_hooks() (both flavours read one reference-order object), and a plugin with the rhs_t trait; not the interceptor."""
         return self.L.socp_ctx_has_fields(self.h) == 1
 
     def fields_batch_dev(self, B, d_Z, cols, stride, skip, cap, d_tq, d_det, d_count, d_nchange, d_tconj, d_Phi=None):
@@ -1164,7 +1170,8 @@ class Context:
     # -- batched exact shooting Jacobian
     def has_exact_jacobian(self):
         """Whether this model has the exact shooting-Jacobian kernel (socp_ctx_has_exact_jacobian): the in-tree Goddard, double integrator
-        and covid19, and a plugin with the rhs_t, hamiltonian_t and switching_fn_t traits; not the interceptor, not vtolUAV."""
+        and covid19, vtolUAV after set_exact_hooks() (custom final rows and switching_state rows through final_row_t / switching_state_t), and a plugin with the
+        rhs_t, hamiltonian_t and switching_fn_t traits; not the interceptor."""
         return self.L.socp_ctx_has_exact_jacobian(self.h) == 1
 
     def exact_jacobian_batch_dev(self, B, d_Z, d_Fjac, d_F=None):

@@ -49,6 +49,9 @@ struct DevBuf {
 
 struct socp_ctx {
     int model_id = 0;
+    // vtolUAV: its fields / exact_jacobian entries count only once the context asked for them (socp_ctx_set_exact_hooks); before
+    // that the context answers as it did when the model had neither entry
+    bool exact_hooks = false;
     const ModelLaunchers *vt = nullptr;   // the model's launch table (in-tree model or out-of-tree plugin), reference operation order
     const ModelLaunchers *vt_fast = nullptr;   // the same model's throughput flavour, when it has one
     int device = 0;
@@ -320,6 +323,7 @@ int socp_ctx_clone(const socp_ctx *proto, int device, socp_ctx **out)
     c->P = proto->P;                                   // parameters, switching times, step number, integrator, tolerance
     c->P.map = nullptr; c->P.n_map = 0;                // the table pointer is the prototype's: the clone gets its own copy
     c->variant = proto->variant;
+    c->exact_hooks = proto->exact_hooks;
     if (!proto->map_table.empty())
         rc = socp_ctx_set_map(c, (int)(proto->map_table.size() / kMapStride), proto->map_table.data());
     if (rc != SOCP_OK) { g_create_error = c->err; socp_ctx_destroy(c); return rc; }
@@ -448,6 +452,15 @@ int socp_ctx_set_variant(socp_ctx *c, int variant)
     if (!c) return SOCP_ERR_ARG;
     if (variant < SOCP_VARIANT_AUTO || variant > SOCP_VARIANT_LANE_FAST) return fail(c, SOCP_ERR_ARG, "set_variant: unknown variant");
     c->variant = variant;
+    return SOCP_OK;
+}
+
+int socp_ctx_set_exact_hooks(socp_ctx *c, int on)
+{
+    if (!c) return SOCP_ERR_ARG;
+    if (c->model_id != SOCP_MODEL_VTOLUAV)
+        return fail(c, SOCP_ERR_UNSUPPORTED, "set_exact_hooks: only vtolUAV's exact entries are switched per context");
+    c->exact_hooks = on != 0;
     return SOCP_OK;
 }
 
@@ -1467,7 +1480,10 @@ int socp_jacobi_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
 
 /* ---- batched exact fields ------------------------------------------------------------------ */
 
-int socp_ctx_has_fields(const socp_ctx *c) { return c ? (table_of(c)->fields ? 1 : 0) : SOCP_ERR_ARG; }
+// an entry of the exact-derivative stack as this context offers it: vtolUAV's only after socp_ctx_set_exact_hooks(ctx, 1)
+static bool exact_entry_on(const socp_ctx *c, bool has) { return has && (c->model_id != SOCP_MODEL_VTOLUAV || c->exact_hooks); }
+
+int socp_ctx_has_fields(const socp_ctx *c) { return c ? (exact_entry_on(c, table_of(c)->fields != nullptr) ? 1 : 0) : SOCP_ERR_ARG; }
 
 namespace {
 int fields_args(socp_ctx *c, const char *who, int B, int cols, int stride, int skip, int cap)
@@ -1478,8 +1494,8 @@ int fields_args(socp_ctx *c, const char *who, int B, int cols, int stride, int s
     if (stride < 1) return fail(c, SOCP_ERR_ARG, w + ": stride >= 1 is required");
     if (skip < 0) return fail(c, SOCP_ERR_ARG, w + ": skip >= 0 is required");
     if (cap < 1) return fail(c, SOCP_ERR_ARG, w + ": cap >= 1 is required");
-    return args_tail(c, w, table_of(c)->fields != nullptr,
-                     "fields entry (a model with its own ComputeTraj, or one without the rhs_t trait)", "the exact fields follow");
+    return args_tail(c, w, exact_entry_on(c, table_of(c)->fields != nullptr),
+                     "fields entry (a model with its own ComputeTraj, one without the rhs_t trait, or vtolUAV before socp_ctx_set_exact_hooks)", "the exact fields follow");
 }
 }  // namespace
 
@@ -1543,19 +1559,22 @@ int socp_fields_batch_blocks(socp_ctx *c, int B, const double *Z, const double *
 
 /* ---- batched exact shooting Jacobian ------------------------------------------------------- */
 
-int socp_ctx_has_exact_jacobian(const socp_ctx *c) { return c ? (table_of(c)->exact_jacobian ? 1 : 0) : SOCP_ERR_ARG; }
+int socp_ctx_has_exact_jacobian(const socp_ctx *c) { return c ? (exact_entry_on(c, table_of(c)->exact_jacobian != nullptr) ? 1 : 0) : SOCP_ERR_ARG; }
 
 namespace {
 int exact_jacobian_args(socp_ctx *c, const char *who, int B)
 {
     const std::string w(who);
     if (const int rc = args_head(c, w, B >= 0, "B >= 0 is required")) return rc;
-    if (const int rc = args_tail(c, w, table_of(c)->exact_jacobian != nullptr,
-                                 "exact_jacobian entry (a model without the rhs_t, hamiltonian_t and switching_fn_t traits, or one with a "
-                                 "switching_state hook, custom final rows or its own ComputeTraj)",
+    if (const int rc = args_tail(c, w, exact_entry_on(c, table_of(c)->exact_jacobian != nullptr),
+                                 "exact_jacobian entry (a model without the rhs_t, hamiltonian_t and switching_fn_t traits, one with its own "
+                                 "ComputeTraj, one with custom final rows and no final_row_t, or one with a switching_state hook and no "
+                                 "switching_state_t with kSwitchingStateXpContinuous, or vtolUAV before socp_ctx_set_exact_hooks)",
                                  "the exact Jacobian follows"))
         return rc;
-    // a FREE state component of an interior node: its rows are the model's SwitchingStateFunction, which the definition does not cover
+    // a FREE state component of an interior node: its rows are the model's SwitchingStateFunction.  vtolUAV's entry covers them
+    // (switching_state_t, models_vtol.hpp); the launch table does not say whether another model's does, so those stay refused
+    if (c->model_id == SOCP_MODEL_VTOLUAV) return SOCP_OK;
     for (int k = 1; k < c->M; k++)
         for (int j = 0; j < c->dim; j++)
             if (c->mode_x[(size_t)k * c->dim + j] == SOCP_FREE)

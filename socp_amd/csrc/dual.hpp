@@ -74,5 +74,12 @@ __device__ __forceinline__ Dual d_exp(const Dual &a)
     const double e = exp_glibc(a.v);
     return Dual(e, e * a.d);
 }
+// tanh a: th = tanh(a.v), the device library's; (th, (1.0 - th th) a.d)
+__device__ __forceinline__ double d_tanh(double a) { return tanh(a); }
+__device__ __forceinline__ Dual d_tanh(const Dual &a)
+{
+    const double th = tanh(a.v);
+    return Dual(th, (1.0 - th * th) * a.d);
+}
 
 }  // namespace socp

@@ -26,6 +26,33 @@ namespace socp {
 template <class M, class = void> struct switching_reads_xp : std::false_type {};
 template <class M> struct switching_reads_xp<M, std::void_t<decltype(M::kSwitchingReadsXp)>> : std::bool_constant<M::kSwitchingReadsXp> {};
 
+// optional trait final_row_t: the text of a custom final row (kCustomFinal: final_row, final_h_offset) over a number type -- the rows of
+// the last node are then final_row_t on the dual end state and H + final_h_offset, as segment_residual forms them
+template <class M, class = void> struct has_final_row_t : std::false_type {};
+template <class M>
+struct has_final_row_t<M, std::void_t<decltype(M::template final_row_t<Dual>(std::declval<const ModelParams &>(), 0, 0,
+                                                                             std::declval<const Dual (&)[M::S]>(), (const double *)nullptr))>>
+    : std::true_type {};
+
+// optional trait switching_state_t: the switching_state hook with the arriving state X over a number type and the node's unknowns Xp
+// as plain doubles -- the two rows of a FREE state component of an interior node, differentiated by the lanes of the segment that ENDS
+// there.  The model must also declare kSwitchingStateXpContinuous = true: the promise that the hook reads Xp only as -Xp[j] in f_state
+// and -Xp[j + D] in f_costate, so that the lanes of the NEXT segment store the same -1 entries they store for a CONTINUOUS row
+template <class M, class = void> struct switching_state_xp_continuous : std::false_type {};
+template <class M>
+struct switching_state_xp_continuous<M, std::void_t<decltype(M::kSwitchingStateXpContinuous)>> : std::bool_constant<M::kSwitchingStateXpContinuous> {};
+template <class M, class = void> struct has_switching_state_t : std::false_type {};
+template <class M>
+struct has_switching_state_t<M, std::void_t<decltype(M::template switching_state_t<Dual>(
+                                    std::declval<const ModelParams &>(), 0.0, 0, std::declval<const Dual (&)[M::S]>(),
+                                    std::declval<const double (&)[M::S]>(), (const double *)nullptr, std::declval<Dual &>(), std::declval<Dual &>()))>>
+    : std::bool_constant<switching_state_xp_continuous<M>::value> {};
+
+// the hooks the definition covers: custom final rows through final_row_t, a switching_state hook through switching_state_t
+template <class M>
+struct exact_jacobian_covers_hooks : std::bool_constant<(!has_custom_final<M>::value || has_final_row_t<M>::value) &&
+                                                        (!has_switching_state<M>::value || has_switching_state_t<M>::value)> {};
+
 // c(j, f): the weight of junction f's time in node j's (Timeline::nt): 1.0 for j == f; (double)(j - a) / (double)(b - a) for
 // f == b, 1.0 minus that for f == a when node j is interpolated between the junctions a and b; 0.0 otherwise
 __device__ __forceinline__ double time_weight(const ProblemDev &pb, int j, int f)
@@ -42,7 +69,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                                                                const double *__restrict__ Z, double *__restrict__ Fjac,
                                                                double *__restrict__ Fout)
 {
-    static_assert(!has_custom_traj<Mdl>::value && !has_custom_final<Mdl>::value && !has_switching_state<Mdl>::value,
+    static_assert(!has_custom_traj<Mdl>::value && exact_jacobian_covers_hooks<Mdl>::value,
                   "the exact Jacobian of such a model needs a definition of its own");
     constexpr int S = Mdl::S;
     constexpr int D = Mdl::D;
@@ -156,21 +183,39 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             const double xdj = xd[j];
             const Dual a = X[j] - (fixed ? xdj : Xp[j]);
             const Dual bb(fixed ? Xp[j] - xdj : X[j + D].v - Xp[j + D], X[j + D].d);      // FIXED: only the value is read
-            emit(row, a, true);
-            emit(row + D, bb, !fixed);
+            if constexpr (has_switching_state<Mdl>::value) {
+                // FREE: the model's SwitchingStateFunction on the dual end state (segment_residual's third arm).  The hook is
+                // evaluated for every mode and its two numbers are SELECTED part by part: the store sites stay the two emits.  The
+                // -1 of Xp[j] and of Xp[j + D] belong to the next segment's lanes, which store them for every mode != FIXED
+                Dual fs, fc;
+                Mdl::template switching_state_t<Dual>(Pq, t2, j, X, Xp, xd, fs, fc);
+                const bool hook = mx[j] == 1;
+                emit(row, Dual(hook ? fs.v : a.v, hook ? fs.d : a.d), true);
+                emit(row + D, Dual(hook ? fc.v : bb.v, hook ? fc.d : bb.d), !fixed);
+            } else {
+                emit(row, a, true);
+                emit(row + D, bb, !fixed);
+            }
         }
     }
     if (i == M - 1) {
         // model.hpp:90-122 FinalFunction / :133-185 FinalHFunction on duals
         const int *mx = pq.mode_x + M * D;
         const double *xd = pq.xnode + M * S;
+        if constexpr (has_custom_final<Mdl>::value) {
+            // the model's own final rows (segment_residual's custom arm): final_row_t returns a COMPUTED number in either mode
 #pragma unroll
-        for (int j = 0; j < D; j++) {
-            const bool fr = mx[j] == 1;                                   // two gated emits, not a select: see the initial rows
-            emit(D + j, X[j + D], true, fr);
-            emit(D + j, X[j] - xd[j], true, !fr);
+            for (int j = 0; j < D; j++) emit(D + j, Mdl::template final_row_t<Dual>(Pq, j, mx[j], X, xd), true);
+            if (pq.ft_row[M] >= 0) emit(pq.ft_row[M], Mdl::template hamiltonian_t<Dual>(Pq, sw0, sw1, t2, X) + Mdl::final_h_offset(Pq), true);
+        } else {
+#pragma unroll
+            for (int j = 0; j < D; j++) {
+                const bool fr = mx[j] == 1;                               // two gated emits, not a select: see the initial rows
+                emit(D + j, X[j + D], true, fr);
+                emit(D + j, X[j] - xd[j], true, !fr);
+            }
+            if (pq.ft_row[M] >= 0) emit(pq.ft_row[M], Mdl::template hamiltonian_t<Dual>(Pq, sw0, sw1, t2, X), true);
         }
-        if (pq.ft_row[M] >= 0) emit(pq.ft_row[M], Mdl::template hamiltonian_t<Dual>(Pq, sw0, sw1, t2, X), true);
     }
 }
 

@@ -8,7 +8,12 @@ namespace socp {
 
 const ModelLaunchers *vtol_launchers()
 {
-    static const ModelLaunchers t = plugin::table<VtolExact>(VP_COUNT, 100, SOCP_VTOL_DEFAULTS);
+    static const ModelLaunchers t = [] {
+        ModelLaunchers t = plugin::table<VtolExact, false>(VP_COUNT, 100, SOCP_VTOL_DEFAULTS);
+        t.fields = &fields_vtol;                     // kernels_vtol_exact.hip: the same reference-order object in both flavours
+        t.exact_jacobian = &exact_jacobian_vtol;     // likewise
+        return t;
+    }();
     return &t;
 }
 

@@ -7,7 +7,12 @@ namespace socp {
 
 const ModelLaunchers *vtol_launchers_fast()
 {
-    static const ModelLaunchers t = plugin::table<VtolFast>(VP_COUNT, 100, SOCP_VTOL_DEFAULTS);
+    static const ModelLaunchers t = [] {
+        ModelLaunchers t = plugin::table<VtolFast, false>(VP_COUNT, 100, SOCP_VTOL_DEFAULTS);
+        t.fields = &fields_vtol;                     // kernels_vtol_exact.hip: the reference-order object, the same bits
+        t.exact_jacobian = &exact_jacobian_vtol;     // likewise
+        return t;
+    }();
     return &t;
 }
 

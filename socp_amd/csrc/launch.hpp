@@ -116,8 +116,9 @@ struct ModelLaunchers {
                           double *, int *, int *);
     // batched exact shooting Jacobian (socp_exact_jacobian_batch): Z[B][n] -> Fjac[B][n*n] column-major (zero-filled on the stream,
     // then ONE launch) and, unless null, F[B][n]; fixed-step integrator only.  Null: the model lacks one of the traits rhs_t,
-    // hamiltonian_t, switching_fn_t, or has a switching_state hook, custom final rows or its own ComputeTraj (plugin_impl.hpp).  The
-    // in-tree models' entries live in kernels_exact_jacobian.hip, one object without contraction that both flavours' tables point to
+    // hamiltonian_t, switching_fn_t, or has its own ComputeTraj, custom final rows without final_row_t or a switching_state hook without
+    // switching_state_t (plugin_impl.hpp).  The in-tree models' entries live in kernels_exact_jacobian.hip and kernels_vtol_exact.hip,
+    // objects without contraction that both flavours' tables point to
     hipError_t (*exact_jacobian)(hipStream_t, const ModelParams &, const ProblemDev &, int, const double *, double *, double *);
     // batched observables (socp_observe_batch): Z[B][n] -> ymin, ymax, tmin, tmax, integral [B][M][NO] (tmin, tmax, integral may be
     // null), count[B][M], nbad[B][M] (may be null), NO = observables; both integrators, one launch.  observables = 0 and null
@@ -346,6 +347,12 @@ hipError_t guide_covid_fast(hipStream_t st, const ModelParams &P, const ProblemD
 hipError_t exact_jacobian_goddard(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
 hipError_t exact_jacobian_dint(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
 hipError_t exact_jacobian_covid(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
+
+// socp_fields_batch and socp_exact_jacobian_batch of the vtolUAV model (kernels_vtol_exact.hip: one object without contraction, for
+// both flavours; instantiated on VtolExact)
+hipError_t fields_vtol(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, int cols, int stride, int skip,
+                       int cap, double *tq, double *det, int *count, int *nchange, double *tconj, double *Phi);
+hipError_t exact_jacobian_vtol(hipStream_t st, const ModelParams &P, const ProblemDev &pb, int B, const double *Z, double *Fjac, double *F);
 
 // socp_sensitivity_batch of the in-tree models (kernels_sensitivity.hip: one object without contraction, for both flavours), and its
 // model-independent finish: the XNODE directions' -1.0 into G[B][K][n] (kind / index: 2 and 16 bits per direction, the index

@@ -24,6 +24,7 @@
 // a position exactly on a box's centre plane makes the term NaN and the isnan reset then zeroes the WHOLE
 // component; normV = 0 gives NaN in rows 9..11 (0 / 0) and nowhere else, in both flavours.
 #pragma once
+#include "dual.hpp"
 #include "integrator.hpp"
 
 namespace socp {
@@ -321,6 +322,138 @@ struct VtolT {
     // vtolUAV.cpp:268-278
     __device__ static __forceinline__ void switching_state(const ModelParams &P, double, int j, const double (&X)[S], const double (&Xp)[S],
                                                           const double *Xd, double &f_state, double &f_costate)
+    {
+        f_state = X[j] - Xp[j];
+        f_costate = (X[j + D] - Xp[j + D]) - P.p[VP_INVSIGMAXWP]*(X[j] - Xd[j]);
+    }
+
+    // ---- the texts over a number type T (socp_fields_batch, socp_exact_jacobian_batch: T = Dual, dual.hpp) -------------------
+    // control_only, map_exact, rhs (the reference-order arm), hamiltonian, switching_fn, final_row and switching_state operation
+    // for operation, d_sqrt / d_abs / d_tanh for the functions; the parameters, the table and the literals stay plain doubles.
+    // With T = double: the bits of the plain texts.  Decisions read value parts: the saturation differentiates the branch taken,
+    // the NaN reset tests the value and zeroes the whole number (a NaN derivative under a finite value stays).  The quirks stay.
+    template <class T>
+    __device__ static __forceinline__ void control_t(const ModelParams &P, const T (&X)[S], T (&u)[3])
+    {
+        const double a_max = P.p[VP_AMAX], u_max = P.p[VP_UMAX];
+        u[0] = -X[9] / a_max;  u[1] = -X[10] / a_max;  u[2] = -X[11] / a_max;
+        const T norm_u = d_sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
+        if (d_val(norm_u) > u_max) {
+            u[0] = u[0] / norm_u * u_max;
+            u[1] = u[1] / norm_u * u_max;
+            u[2] = u[2] / norm_u * u_max;
+        }
+    }
+
+    template <bool WANT_F, bool WANT_G, class T>
+    __device__ static __forceinline__ void map_exact_t(const ModelParams &P, const T &px, const T &py, const T &pz, T &func, T (&grad)[3])
+    {
+        const double mu = P.p[VP_MUOBS];
+        T f = T(0.0), g0 = T(0.0), g1 = T(0.0), g2 = T(0.0);
+        const MapTable tab = map_table(P);
+        for (int i = 0; i < P.n_map; i++) {
+            const MapTable o = tab + (long)i * kMapStride;
+            const double type = o[0], x = o[1], y = o[2], z = o[3], radx = o[4], rady = o[5], radz = o[6];
+            if (type == 0) {
+                const T hx = px - x, hy = py - y, hz = pz - z;
+                const T d = d_sqrt(hx*hx + hy*hy + hz*hz);
+                if constexpr (WANT_F) {
+                    const T rad = d / d_sqrt(hx*hx / radx / radx + hy*hy / rady / rady + hz*hz / radz / radz);
+                    const T h = (d - rad) / mu;
+                    f = f + (1 - d_tanh(h)) / 2;
+                }
+                if constexpr (WANT_G) {
+                    const T q = d_sqrt(hx*hx / radx / radx + hy*hy / rady / rady);
+                    const T rad = d / q;                        // the z term is missing upstream (obstacle.cpp:258)
+                    const T h = (d - rad) / mu;
+                    const T rho2 = (radx*radx - rady*rady) / (radx*radx*rady*rady) / q / q / q;
+                    const T th = d_tanh(h);
+                    g0 = g0 - hx / d*(1 - hy*hy*rho2) / mu*(1 - th*th) / 2;
+                    g1 = g1 - hy / d*(1 + hx*hx*rho2) / mu*(1 - th*th) / 2;
+                    g2 = g2 - 0;
+                }
+            } else if (type == 1) {
+                const T dx = px - x, dy = py - y, dz = pz - z;
+                const T thx = d_tanh((d_abs(dx) - radx) / mu);
+                const T thy = d_tanh((d_abs(dy) - rady) / mu);
+                const T thz = d_tanh((d_abs(dz) - radz) / mu);
+                if constexpr (WANT_F) f = f + (1 - thx)*(1 - thy)*(1 - thz) / 8;
+                if constexpr (WANT_G) {
+                    g0 = g0 - dx / d_abs(dx) / mu*(1 - thx*thx)*(1 - thy)*(1 - thz) / 8;
+                    g1 = g1 - dy / d_abs(dy) / mu*(1 - thy*thy)*(1 - thx)*(1 - thz) / 8;
+                    g2 = g2 - dz / d_abs(dz) / mu*(1 - thz*thz)*(1 - thx)*(1 - thy) / 8;
+                }
+            }
+        }
+        if (d_val(f) != d_val(f)) f = T(0.0);
+        if (d_val(g0) != d_val(g0)) g0 = T(0.0);
+        if (d_val(g1) != d_val(g1)) g1 = T(0.0);
+        if (d_val(g2) != d_val(g2)) g2 = T(0.0);
+        const double phi = P.p[VP_PHIOBS], psi = P.p[VP_PSIWP];
+        if constexpr (WANT_F) func = phi*f + psi*0.0;
+        if constexpr (WANT_G) { grad[0] = phi*g0 + psi*0.0; grad[1] = phi*g1 + psi*0.0; grad[2] = phi*g2 + psi*0.0; }
+    }
+
+    template <class T>
+    __device__ static __forceinline__ void rhs_t(const ModelParams &P, double, double, double, const T (&X)[S], T (&dX)[S])
+    {
+        const T vx = X[3], vy = X[4], vz = X[5], p_x = X[6], p_y = X[7], p_z = X[8], p_vx = X[9], p_vy = X[10], p_vz = X[11];
+        const double a_max = P.p[VP_AMAX], ca = P.p[VP_CA], alphaV = P.p[VP_ALPHAV], Vd = P.p[VP_VD];
+        T u[3], g[3], unused;
+        control_t<T>(P, X, u);
+        map_exact_t<false, true, T>(P, X[0], X[1], X[2], unused, g);
+        dX[0] = vx;  dX[1] = vy;  dX[2] = vz;
+        dX[6] = 0 - g[0];  dX[7] = 0 - g[1];  dX[8] = 0 - g[2];
+        const T normV = d_sqrt(vx*vx + vy*vy + vz*vz);
+        dX[3] = a_max*u[0] - ca*vx*normV;
+        dX[4] = a_max*u[1] - ca*vy*normV;
+        dX[5] = a_max*u[2] - ca*vz*normV;
+        dX[9]  = -p_x + ca*( p_vx*(normV + vx*vx/normV) + p_vy*(vy*vx/normV) + p_vz*(vz*vx/normV) ) - alphaV*vx/normV*(normV - Vd);
+        dX[10] = -p_y + ca*( p_vy*(normV + vy*vy/normV) + p_vx*(vx*vy/normV) + p_vz*(vz*vy/normV) ) - alphaV*vy/normV*(normV - Vd);
+        dX[11] = -p_z + ca*( p_vz*(normV + vz*vz/normV) + p_vx*(vx*vz/normV) + p_vy*(vy*vz/normV) ) - alphaV*vz/normV*(normV - Vd);
+    }
+
+    template <class T>
+    __device__ static __forceinline__ T hamiltonian_t(const ModelParams &P, double, double, double, const T (&X)[S])
+    {
+        const T vx = X[3], vy = X[4], vz = X[5], p_x = X[6], p_y = X[7], p_z = X[8], p_vx = X[9], p_vy = X[10], p_vz = X[11];
+        const double a_max = P.p[VP_AMAX], ca = P.p[VP_CA], alphaV = P.p[VP_ALPHAV], Vd = P.p[VP_VD];
+        const T normV = d_sqrt(vx*vx + vy*vy + vz*vz);
+        T u[3], g[3], obs = T(0.0);
+        control_t<T>(P, X, u);
+        const T norm_u = d_sqrt(u[0]*u[0] + u[1]*u[1] + u[2]*u[2]);
+        map_exact_t<true, false, T>(P, X[0], X[1], X[2], obs, g);
+        return P.p[VP_ALPHAT]*1
+             + alphaV / 2*(normV - Vd)*(normV - Vd)
+             + obs
+             + a_max*a_max*norm_u*norm_u / 2
+             + p_x*vx + p_y*vy + p_z*vz
+             + (p_vx*(a_max*u[0] - ca*vx*normV) + p_vy*(a_max*u[1] - ca*vy*normV) + p_vz*(a_max*u[2] - ca*vz*normV));
+    }
+
+    // H(t, X-) - H(t, X+): the lanes of the next segment own -grad H(X+)
+    static constexpr bool kSwitchingReadsXp = true;
+    template <class T>
+    __device__ static __forceinline__ T switching_fn_t(const ModelParams &P, double sw0, double sw1, double t, const T (&X)[S], const T (&Xp)[S])
+    {
+        return hamiltonian_t<T>(P, sw0, sw1, t, X) - hamiltonian_t<T>(P, sw0, sw1, t, Xp);
+    }
+
+    // final_row on T; final_h_offset stays plain
+    template <class T>
+    __device__ static __forceinline__ T final_row_t(const ModelParams &P, int j, int mode, const T (&X)[S], const double *xd)
+    {
+        const T dxj = X[j] - xd[j];
+        if (mode == 1) return X[j + D] - P.p[VP_INVSIGMAXWP]*(P.p[VP_NWP_TOT] - P.p[VP_NWP])*dxj - 0.02*dxj;
+        return dxj;
+    }
+
+    // switching_state with X on T and the node's unknowns Xp as the plain doubles they are: Xp enters only as -Xp[j] in f_state and
+    // -Xp[j + D] in f_costate, which is what kSwitchingStateXpContinuous promises (exact_jacobian.hpp)
+    static constexpr bool kSwitchingStateXpContinuous = true;
+    template <class T>
+    __device__ static __forceinline__ void switching_state_t(const ModelParams &P, double, int j, const T (&X)[S], const double (&Xp)[S],
+                                                            const double *Xd, T &f_state, T &f_costate)
     {
         f_state = X[j] - Xp[j];
         f_costate = (X[j + D] - Xp[j + D]) - P.p[VP_INVSIGMAXWP]*(X[j] - Xd[j]);

@@ -53,11 +53,22 @@
 //       // OPTIONAL -- with rhs_t, the Hamiltonian and the free-interior-time row over a number type (socp_exact_jacobian_batch: the
 //       // exact Jacobian of the shooting function).  With T = double: the bits of hamiltonian / switching_fn.  kSwitchingReadsXp says
 //       // whether the row is H(t, X) - H(t, Xp) (true: the library then takes -grad H(Xp) from hamiltonian_t) or does not read Xp
-//       // (false, the default).  A model with a switching_state hook, custom final rows or its own ComputeTraj does not get the entry.
+//       // (false, the default).  A model with its own ComputeTraj does not get the entry; one with custom final rows or a
+//       // switching_state hook gets it through the two traits below.
 //       template <class T> __device__ static T hamiltonian_t(const socp::ModelParams &P, double sw0, double sw1, double t, const T (&X)[S]);
 //       template <class T> __device__ static T switching_fn_t(const socp::ModelParams &P, double sw0, double sw1, double t,
 //                                                             const T (&X)[S], const T (&Xp)[S]);
 //       static constexpr bool kSwitchingReadsXp = ...;
+//       // OPTIONAL -- for a model with custom final rows (kCustomFinal): the text of final_row over a number type; final_h_offset
+//       // stays plain.  With it the exact Jacobian covers the model's final rows.
+//       template <class T> __device__ static T final_row_t(const socp::ModelParams &P, int j, int mode, const T (&X)[S], const double *xd);
+//       // OPTIONAL -- for a model with a switching_state hook: the hook with X over a number type and Xp as the plain doubles they
+//       // are.  The lanes of the segment that ENDS at the node differentiate the two rows; kSwitchingStateXpContinuous = true is the
+//       // model's promise that the hook reads Xp only as -Xp[j] in f_state and -Xp[j + D] in f_costate, so that the next segment's
+//       // lanes store the -1 entries of a CONTINUOUS row.  Both are required for the exact Jacobian of such a model.
+//       template <class T> __device__ static void switching_state_t(const socp::ModelParams &P, double t, int j, const T (&X)[S],
+//                                                                   const double (&Xp)[S], const double *Xd, T &f_state, T &f_costate);
+//       static constexpr bool kSwitchingStateXpContinuous = true;
 //       // OPTIONAL -- the same three texts generic in the PARAMETER view as well (socp_sensitivity_batch: exact dF/dtheta): a second
 //       // template argument for anything with p[i], locals that hold a parameter `auto`, comparisons through d_val.  With
 //       // socp::ModelParams the texts are what they were (tests/plugin/osc1d_sensitivity_plugin.hip):
@@ -310,7 +321,8 @@ hipError_t fields(hipStream_t st, const ModelParams &P, const ProblemDev &pb, in
 }
 
 // optional traits hamiltonian_t and switching_fn_t beside rhs_t, and none of the hooks the definition does not cover -> the model has
-// the exact shooting Jacobian (socp_exact_jacobian_batch)
+// the exact shooting Jacobian (socp_exact_jacobian_batch).  Custom final rows are covered iff the model has final_row_t, a
+// switching_state hook iff it has switching_state_t and declares kSwitchingStateXpContinuous (exact_jacobian.hpp)
 template <class M, class = void> struct has_exact_jacobian : std::false_type {};
 template <class M>
 struct has_exact_jacobian<M, std::void_t<decltype(M::template hamiltonian_t<Dual>(std::declval<const ModelParams &>(), 0.0, 0.0, 0.0,
@@ -318,7 +330,7 @@ struct has_exact_jacobian<M, std::void_t<decltype(M::template hamiltonian_t<Dual
                                          decltype(M::template switching_fn_t<Dual>(std::declval<const ModelParams &>(), 0.0, 0.0, 0.0,
                                                                                     std::declval<const Dual (&)[M::S]>(),
                                                                                     std::declval<const Dual (&)[M::S]>()))>>
-    : std::bool_constant<has_fields<M>::value && !has_custom_traj<M>::value && !has_custom_final<M>::value && !has_switching_state<M>::value> {};
+    : std::bool_constant<has_fields<M>::value && !has_custom_traj<M>::value && exact_jacobian_covers_hooks<M>::value> {};
 
 // batched exact shooting Jacobian: fixed-step integrator only.  The matrices are zero-filled on the stream, then ONE launch: one group of
 // S + 1 neighbouring lanes per (row, segment) (exact_jacobian.hpp).  The translation unit must be built without contraction
@@ -333,7 +345,8 @@ hipError_t exact_jacobian(hipStream_t st, const ModelParams &P, const ProblemDev
 }
 
 // optional: rhs_t, hamiltonian_t and switching_fn_t are generic in the parameter view too (they take SeededParams, sensitivity.hpp)
-// beside everything the exact Jacobian asks for -> the model has exact parameter sensitivities (socp_sensitivity_batch)
+// beside everything the exact Jacobian asks for, and neither custom final rows nor a switching_state hook (the sensitivities of those
+// rows need a definition of their own) -> the model has exact parameter sensitivities (socp_sensitivity_batch)
 template <class M, class = void> struct has_sensitivity : std::false_type {};
 template <class M>
 struct has_sensitivity<M, std::void_t<decltype(M::template rhs_t<Dual>(std::declval<const SeededParams &>(), 0.0, 0.0, 0.0,
@@ -343,7 +356,7 @@ struct has_sensitivity<M, std::void_t<decltype(M::template rhs_t<Dual>(std::decl
                                       decltype(M::template switching_fn_t<Dual>(std::declval<const SeededParams &>(), 0.0, 0.0, 0.0,
                                                                                  std::declval<const Dual (&)[M::S]>(),
                                                                                  std::declval<const Dual (&)[M::S]>()))>>
-    : std::bool_constant<has_exact_jacobian<M>::value> {};
+    : std::bool_constant<has_exact_jacobian<M>::value && !has_custom_final<M>::value && !has_switching_state<M>::value> {};
 
 // the integrating directions of ONE kind of socp_sensitivity_batch: fixed-step integrator only.  G is zero-filled by the caller; one
 // group of dirs.n neighbouring lanes per (row, segment), 64 / dirs.n groups per single-wave workgroup (sensitivity.hpp); always one wave
